@@ -8,14 +8,19 @@ batch, no per-step collective -- the only collective is one weight broadcast at 
 One "step" = one pass of the whole hot path (enc_p -> reverse flow -> generator -> iSTFT +
 band synthesis) over one batch of 32 synthetic utterances already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: starts its own N worker processes, one per GPU)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                                                                  (N > 1: starts its own N worker processes, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line (contract in the task description) including
+A plain run sets up, warms up, times the K steps, writes the last step's output if --dump-outputs is given, and
+rank 0 prints ONE JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+With --full the line also holds the legs that take runs of their own:
+  "steady_state" / "one_batch_at_a_time": the K steps timed again at the steady clock, and on one lane only;
   "roofline":     the dominant kernel's achieved TFLOP/s vs the gfx950 dense f16/bf16 MFMA peak,
                   from per-launch HIP events (qvc_infer_batch_timed) on the launch stream;
-  "cpu_baseline": the fp32 CPU oracle (a port of the reference path) timed on this host's
-                  cores on a bounded sample of the same workload (N=1 only).
+  "speaker_encoder": the time of one speaker-embedding call for the batch;
+  "cpu_baseline" / "parity": the fp32 CPU oracle (a port of the reference path) timed on this host's
+                  cores on a bounded sample of the same workload, and the GPU output against it (N=1 only).
 """
 from __future__ import annotations
 
@@ -97,6 +102,14 @@ def main() -> None:
                          "that give identical results; recorded in the JSON line")
     ap.add_argument("--rehearsal", action="store_true",
                     help="developer switch for a 1-GPU box: every rank on cuda:0 with gloo, to exercise the multi-rank control flow")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the waveforms of the last timed step (float32, (batch, 1, samples)) "
+                         "to DIR/audio.npy (rank r > 0 of a multi-rank run: DIR/audio_rank<r>.npy); the inputs are seeded, "
+                         "so two builds can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the diagnostic legs: roofline (per-launch events), steady-state and one-lane windows with "
+                         "the lane bit-identity check, speaker-encoder timing, CPU baseline and parity (--no-cpu-baseline "
+                         "drops the last two)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -167,7 +180,7 @@ def main() -> None:
     lanes = [make_lane(0)]
     unit, g, noise, out, stream, graph = (lanes[0][key] for key in ("unit", "g", "noise", "out", "stream", "graph"))
     agg, reps, total_ms = {}, 5, 0.0
-    if rank == 0:
+    if args.full and rank == 0:
         # ---- roofline leg, BEFORE a second lane exists: per-launch HIP events on lane 0's stream (qvc_infer_batch_timed),
         #      same workload, chip at its steady clock.  (Taken after the two-lane windows the very same eager launches
         #      measured 10 % longer -- 249 vs 225 us for the dominant kernel, rocprofv3 of the one-lane run: 225 us.)
@@ -211,43 +224,52 @@ def main() -> None:
         dist.barrier()
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
-    # A second window of K steps, 40 steps later, is reported next to `value` as `steady_state`: the two agree when the
-    # settle steps above did their job (with --settle 0 `value` contains the clock ramp: 2.24, 2.50, 2.35, 2.25, 2.16 ...
-    # -> 1.98 ms per step, tools/warmup_probe.py).
-    for _ in range(40):
-        step()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    wall_steady = time.perf_counter() - t1
-    # strictly one batch at a time, for comparison (and what the per-kernel profile under profiles/ is taken on)
-    wall_single = wall_steady
-    lanes_identical = True
-    if n_lanes > 1:
+    if args.dump_outputs:
+        # what a caller of the timed path receives from its last step: that lane's waveforms (the other lanes hold the
+        # same path's output for their own inputs).  10 MB at batch 32; larger batches keep their first utterances.
+        import numpy as np
+        last = lanes[(step_no[0] - 1) % n_lanes]["out"]
+        per_utt = last[0].numel() * 4
+        keep = max(1, min(last.shape[0], (64 << 20) // per_utt))
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "audio.npy" if rank == 0 else f"audio_rank{rank}.npy"),
+                last[:keep].float().cpu().numpy())
+    if args.full:
+        # A second window of K steps, 40 steps later, is reported next to `value` as `steady_state`: the two agree when
+        # the settle steps above did their job (with --settle 0 `value` contains the clock ramp: 2.24, 2.50, 2.35, 2.25,
+        # 2.16 ... -> 1.98 ms per step, tools/warmup_probe.py).
+        for _ in range(40):
+            step()
         torch.cuda.synchronize()
-        t2 = time.perf_counter()
+        t1 = time.perf_counter()
         for _ in range(args.steps):
-            step(1)
+            step()
         torch.cuda.synchronize()
-        wall_single = time.perf_counter() - t2
-        # overlap must not change a single bit: every lane's output against the same graph run alone
-        for lane in lanes:
-            before = lane["out"].clone()
-            run_lane(lane)
+        wall_steady = time.perf_counter() - t1
+        # strictly one batch at a time, for comparison (and what the per-kernel profile under profiles/ is taken on)
+        wall_single = wall_steady
+        lanes_identical = True
+        if n_lanes > 1:
             torch.cuda.synchronize()
-            lanes_identical = lanes_identical and bool(torch.equal(before, lane["out"]))
+            t2 = time.perf_counter()
+            for _ in range(args.steps):
+                step(1)
+            torch.cuda.synchronize()
+            wall_single = time.perf_counter() - t2
+            # overlap must not change a single bit: every lane's output against the same graph run alone
+            for lane in lanes:
+                before = lane["out"].clone()
+                run_lane(lane)
+                torch.cuda.synchronize()
+                lanes_identical = lanes_identical and bool(torch.equal(before, lane["out"]))
     wall = qd.max_over_ranks(wall, device)
-    wall_steady = qd.max_over_ranks(wall_steady, device)
-    wall_single = qd.max_over_ranks(wall_single, device)
+    if args.full:
+        wall_steady = qd.max_over_ranks(wall_steady, device)
+        wall_single = qd.max_over_ranks(wall_single, device)
     samples_per_step = world * B * FRAMES * engine.samples_per_frame
     value = samples_per_step * args.steps / wall
     ms_per_step = wall / args.steps * 1e3
 
-    steady = {"ms_per_step": wall_steady / args.steps * 1e3, "value": samples_per_step * args.steps / wall_steady,
-              "note": f"the same {args.steps} steps timed again after 40 more steps (device at its steady clock); "
-                      "`value` is the first window, right after the settle + warm-up steps"}
     result = {
         "metric": "audio samples/sec (16 kHz, 5 s utterances, batch 32 per GPU, whole hot path)",
         "value": value, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -262,15 +284,20 @@ def main() -> None:
                    "batches_in_flight": n_lanes,
                    **({"debug_switches": args.debug} if args.debug else {})},
         "rtf": wall / args.steps / (world * B * FRAMES * engine.samples_per_frame / SAMPLE_RATE),
-        "steady_state": steady, "settle_steps": args.settle,
-        "one_batch_at_a_time": {"ms_per_step": wall_single / args.steps * 1e3, "value": samples_per_step * args.steps / wall_single,
-                                "note": "the same graphs replayed on one lane only (steady clock); the per-launch durations of the "
-                                        "roofline leg and of the rocprofv3 summary are taken in this mode",
-                                "lanes_bit_identical_to_running_alone": lanes_identical},
+        "settle_steps": args.settle,
     }
+    if args.full:
+        result["steady_state"] = {
+            "ms_per_step": wall_steady / args.steps * 1e3, "value": samples_per_step * args.steps / wall_steady,
+            "note": f"the same {args.steps} steps timed again after 40 more steps (device at its steady clock); "
+                    "`value` is the first window, right after the settle + warm-up steps"}
+        result["one_batch_at_a_time"] = {
+            "ms_per_step": wall_single / args.steps * 1e3, "value": samples_per_step * args.steps / wall_single,
+            "note": "the same graphs replayed on one lane only (steady clock); the per-launch durations of the "
+                    "roofline leg and of the rocprofv3 summary are taken in this mode",
+            "lanes_bit_identical_to_running_alone": lanes_identical}
 
     if rank == 0:
-        # ---- roofline leg: measured by roofline_leg() above (per-launch HIP events on the launch stream)
         # the fork / join path exists only for stages whose ResBlock pairs do not run fused (qvc_plan_info()[7])
         import ctypes
         info = (ctypes.c_int32 * 8)()
@@ -278,6 +305,8 @@ def main() -> None:
         result["config"]["parallel_resblock_branches"] = bool(args.branches and not info[7])
         if args.branches and info[7]:
             print("bench.py: --branches has no effect on this configuration (every stage runs its three chains fused in one launch)", file=sys.stderr)
+    if args.full and rank == 0:
+        # ---- roofline leg: measured above, before the second lane was built (per-launch HIP events on the launch stream)
         dom_name, dom = max(agg.items(), key=lambda kv: kv[1]["ms"])
         achieved = dom["flops"] / (dom["ms"] * 1e-3) / 1e12 if dom["ms"] > 0 else 0.0
         # HBM traffic per launch comes from separate rocprofv3 --pmc passes (tools/profile_bench.sh writes
@@ -357,6 +386,7 @@ def main() -> None:
             result["parity"] = {"snr_db_min": min(snrs), "snr_db_mean": sum(snrs) / len(snrs),
                                 "linf": float((ref - out[:n_cpu].cpu()).abs().max()), "tolerance_db": 40.0,
                                 "checked_utterances": n_cpu}
+    if rank == 0:
         print(json.dumps(result))
         par = result.get("parity")
         if par and not (par["snr_db_min"] >= par["tolerance_db"]):

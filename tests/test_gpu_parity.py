@@ -1170,7 +1170,7 @@ def test_bench_starts_its_own_workers(lib, dev):
     from helpers import ROOT
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4",
-                          "--rehearsal", "--no-cpu-baseline"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+                          "--rehearsal", "--full", "--no-cpu-baseline"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, res.stdout[-2000:]
@@ -1179,8 +1179,44 @@ def test_bench_starts_its_own_workers(lib, dev):
     assert out["config"]["batch_per_gpu"] == 4 and "roofline" in out
     # a failing worker must fail the parent: --gpus 2 with an impossible batch
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--batch", "0",
-                          "--rehearsal", "--no-cpu-baseline"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+                          "--rehearsal", "--full", "--no-cpu-baseline"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert bad.returncode != 0
+
+
+def test_bench_plain_run_dumps_what_the_timed_path_computed(lib, dev, tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline line without the diagnostic legs, and --dump-outputs
+    writes the waveforms of the last timed step.  With --settle 0 --warmup 1 --steps 3 the last of the four steps runs
+    on lane 1 of two, whose inputs are seeded with seed0 = lane x batch: the file must hold exactly what the engine
+    computes for those inputs."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import quickvc_official_amd as q
+    from quickvc_official_amd.engine import QvcEngine
+    from quickvc_official_amd.synth import make_synthetic_state_dict, make_synthetic_inputs
+    from helpers import ROOT
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--settle", "0",
+                          "--batch", "4", "--in-flight", "2", "--dump-outputs", str(tmp_path / "dump")],
+                         env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["dtype"] == "bf16x" and out["unit"] == "samples/s" and out["higher_is_better"] is True
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and out["metric"].startswith("audio samples/sec")
+    assert not set(out) & {"roofline", "cpu_baseline", "parity", "steady_state", "one_batch_at_a_time", "speaker_encoder"}
+    assert os.listdir(tmp_path / "dump") == ["audio.npy"]
+    dumped = np.load(tmp_path / "dump" / "audio.npy")
+    assert dumped.dtype == np.float32 and dumped.shape == (4, 1, 80000)
+    cfg = dict(q.DEFAULT_MODEL_CONFIG)
+    model = q.SynthesizerTrn(641, 32, **cfg, operand_dtype="bf16x")
+    eng = QvcEngine(model.model_config, make_synthetic_state_dict(model, 1234), dev)
+    unit, g, noise = make_synthetic_inputs(4, 250, 256, cfg["inter_channels"], cfg["gin_channels"], seed0=1 * 4)
+    ref = eng.infer_batch(unit.to(dev), g.to(dev), noise.to(dev))
+    torch.cuda.synchronize()
+    assert np.array_equal(dumped, ref.cpu().numpy())
 
 
 def test_convert_cli_two_ranks_rehearsal(lib, dev, tmp_path):

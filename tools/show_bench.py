@@ -1,4 +1,4 @@
-"""Prints the headline numbers and the per-kernel table of a bench.py JSON line.  usage: python tools/show_bench.py file.json"""
+"""Prints the headline numbers and the per-kernel table of a `bench.py --full` JSON line.  usage: python tools/show_bench.py file.json"""
 import json
 import sys
 
