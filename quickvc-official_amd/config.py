@@ -83,3 +83,7 @@ MINI_MODEL_CONFIG = dict(DEFAULT_MODEL_CONFIG, inter_channels=64, hidden_channel
 # zero-padding path of the weight packer and the masked stores of the kernels.
 ODD_MODEL_CONFIG = dict(DEFAULT_MODEL_CONFIG, inter_channels=48, hidden_channels=40,
                         upsample_initial_channel=96, gin_channels=24)
+# The single-band iSTFT decoder (iSTFT_Generator, models.py:98-192, selected by istft_vits=True) at 16 kHz:
+# prod(upsample_rates) * hop 4 = 320 samples per unit frame, like the shipped multistream decoder.
+ISTFT_MODEL_CONFIG = dict(DEFAULT_MODEL_CONFIG, ms_istft_vits=False, istft_vits=True,
+                          upsample_rates=[10, 8], upsample_kernel_sizes=[20, 16])

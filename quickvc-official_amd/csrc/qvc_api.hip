@@ -91,6 +91,9 @@ struct HipBackend {
   int tail(const TailArgs& a) { return launch_tail(a, stream); }
   bool post_tail_ok(const ConvDesc& d) const { return debug_get(DBG_POST_TAIL) != 0 && post_tail_supported(d); }
   int post_tail(const ConvDesc& d, const PostTailArgs& a, int batch, int dtype) { return launch_post_tail(d, a, batch, dtype, stream); }
+  // single-band decoder: the launchers pick the kernels by TailArgs::bands / post_tail_bands(conv_post)
+  int tail1(const TailArgs& a) { return launch_tail(a, stream); }
+  int post_tail1(const ConvDesc& d, const PostTailArgs& a, int batch, int dtype) { return launch_post_tail(d, a, batch, dtype, stream); }
   int zero(void* p, size_t bytes) { return hipMemsetAsync(p, 0, bytes, stream) == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH; }
   int copy_batch(const CopyDesc* d, int n) { return launch_copy_batch(d, n, stream); }
 };
@@ -211,6 +214,19 @@ struct TimedBackend {
     std::snprintf(name, sizeof(name), "post_tail<%s>", dtype == QVC_F16 ? "f16" : "bf16");
     note(name, 2.0 * batch * (double)a.F * d.M * d.taps * d.Cin,
          (double)batch * ((double)a.c.T_in * d.Cin * 2 * 3 + 16.0 * (a.F - 1) * 4) + (double)d.w_bytes());
+    return st;
+  }
+  int tail1(const TailArgs& a) { if (ev.empty()) mark(); int st = launch_tail(a, stream); mark();
+    note("istft1", 0, (double)a.batch * ((double)a.F * 18 * 4 + 4.0 * (a.F - 1) * 4)); return st; }
+  int post_tail1(const ConvDesc& d, const PostTailArgs& a, int batch, int dtype) {
+    if (ev.empty()) mark();
+    int st = launch_post_tail(d, a, batch, dtype, stream);
+    mark();
+    char name[48];
+    std::snprintf(name, sizeof(name), "post_tail1<%s>", dtype == QVC_F16 ? "f16" : "bf16");
+    // algorithmic: the three stage-final ResBlock streams read once, the waveform written once, conv_post's 18 rows
+    note(name, 2.0 * batch * (double)a.F * d.M * d.taps * d.Cin,
+         (double)batch * ((double)a.c.T_in * d.Cin * 2 * 3 + 4.0 * (a.F - 1) * 4) + (double)d.w_bytes() / 2);
     return st;
   }
   int zero(void* p, size_t bytes) { if (ev.empty()) mark(); int st = hipMemsetAsync(p, 0, bytes, stream) == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH; mark();
@@ -587,6 +603,7 @@ int qvc_istft_synth(const qvc_config* cfg, const void* blob_dev, const float* po
   if (P.status != QVC_OK) return P.status;
   TailArgs ta{post_fm, reinterpret_cast<const float*>(static_cast<const char*>(blob_dev) + P.fir_off), out, y_mb, batch,
               post_frames};
+  if (cfg->decoder == QVC_DEC_ISTFT) { ta.fir = nullptr; ta.bands = 1; }
   return launch_tail(ta, stream);
 }
 

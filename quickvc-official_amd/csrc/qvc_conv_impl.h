@@ -551,8 +551,9 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
             const float4 old = *reinterpret_cast<const float4*>(p);
             out.x += old.x; out.y += old.y; out.z += old.z; out.w += old.w;
           }
-          *reinterpret_cast<float4*>(p) = out;
-        }
+          if (v + 4 <= a.M) *reinterpret_cast<float4*>(p) = out;
+          else { p[0] = out.x; if (v + 1 < a.M) p[1] = out.y; if (v + 2 < a.M) p[2] = out.z; }   // M % 4 != 0: the single-band
+        }                                                                                           // conv_post's 18 rows
         if (a.y16) {
           typename O::quad h;
           h[0] = O::cvt(lrelu(val.x, a.slope_out)); h[1] = O::cvt(lrelu(val.y, a.slope_out));

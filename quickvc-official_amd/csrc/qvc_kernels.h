@@ -214,29 +214,35 @@ struct SampleArgs {   // z = mu + noise * exp(logs)   (models.py:93-94)
   int32_t batch, frames, C;
 };
 
-struct TailArgs {     // models.py:394-406 / pqmf.py:106-117
+struct TailArgs {     // models.py:394-406 / pqmf.py:106-117; single band: models.py:171-176
   const float* post;  // [B][F][subbands*18]
-  const float* fir;   // [subbands][63], gain folded
+  const float* fir;   // [subbands][63], gain folded (unused for one band)
   float* out;         // [B][subbands*hop*(F-1)]
   float* y_mb;        // optional [B][subbands][hop*(F-1)]
   int32_t batch, F;
   Ragged rg;          // per-utterance frame count min(F, lens*mul + add); samples past it are written as zeros
+  int32_t bands = 4;  // 4: iSTFT per band + synthesis FIR; 1: the iSTFT output is the waveform (QVC_DEC_ISTFT)
 };
 
 // subband_conv_post + tail in one launch (qvc_post_tail_impl.h): `c` = the conv_post launch without an output
 // pointer, the rest = TailArgs.  The post-conv frames stay in the CU.
 struct PostTailArgs {
   ConvArgs c;
-  const float* fir = nullptr;   // [subbands][63], gain folded
-  float* out = nullptr;         // [B][16*(F-1)]
+  const float* fir = nullptr;   // [subbands][63], gain folded (four bands only)
+  float* out = nullptr;         // [B][16*(F-1)]; one band: [B][4*(F-1)]
   int32_t F = 0;                // post-conv frames (= c.T_in + 1)
   Ragged rg;                    // as TailArgs::rg
 };
-// the fused kernel walks conv_post's packed weights as 2 waves x 3 row fragments and a 128-frame tile
-inline bool post_tail_supported(const ConvDesc& d) {
-  return d.M == 72 && d.MF == 3 && d.WM == 2 && d.nchunk == 1 && d.up_s == 1 && d.dil == 1 && !d.gau && !d.lp &&
-         (int64_t)(128 + d.taps - 1) * d.CinP * 2 <= 96 * 1024;
+// Bands of the fused conv_post + tail kernel that walks `d` (0: none).  Four bands: conv_post's packed weights as 2
+// waves x 3 row fragments [72 -> 96 rows]; one band (QVC_DEC_ISTFT): the first wave's stream of a 4-wave x 2-fragment
+// packing [18 -> 128 rows], rows 0..31.  Both with a 128-frame tile.
+inline int post_tail_bands(const ConvDesc& d) {
+  if (d.nchunk != 1 || d.up_s != 1 || d.dil != 1 || d.gau || d.lp || (int64_t)(128 + d.taps - 1) * d.CinP * 2 > 96 * 1024) return 0;
+  if (d.M == 72 && d.MF == 3 && d.WM == 2) return 4;
+  if (d.M == 18 && d.MF == 2 && d.WM == 4) return 1;
+  return 0;
 }
+inline bool post_tail_supported(const ConvDesc& d) { return post_tail_bands(d) != 0; }
 
 // One LSTM layer's recurrence over all partials (models.py:510,516): gates = xp[t] + W_hh h[t-1], PyTorch gate
 // order i,f,g,o.  The input projection xp (with b_ih + b_hh) comes from a conv launch.
@@ -305,7 +311,7 @@ constexpr int kCopyBatchMax = 12;
 int launch_copy_batch(const CopyDesc* d, int n, void* stream);
 int launch_sample(const SampleArgs& a, void* stream);
 int launch_tail(const TailArgs& a, void* stream);
-int launch_post_tail(const ConvDesc& d, PostTailArgs a, int batch, int dtype, void* stream);
+int launch_post_tail(const ConvDesc& d, PostTailArgs a, int batch, int dtype, void* stream);   // bands = post_tail_bands(d)
 
 // Instantiation entry (one translation unit per operand dtype).
 template <typename T> int launch_conv_typed(const ConvDesc& d, const ConvArgs& a, int batch, int epi, void* stream, int* nf_out);

@@ -267,11 +267,13 @@ extern "C" int qvc_pack_weights(const qvc_config* cfg, const qvc_tensor* tensors
         pk.cur_dtype = dec_dtype(*cfg);
       }
   }
-  if (pk.status == QVC_OK) pk.pack_conv1d(P.conv_post, "dec.subband_conv_post");
+  // single band: conv_post with 2*(n_fft/2+1) rows (models.py:139), and no band synthesis to pack
+  const bool single = cfg->decoder == QVC_DEC_ISTFT;
+  if (pk.status == QVC_OK) pk.pack_conv1d(P.conv_post, single ? "dec.conv_post" : "dec.subband_conv_post");
 
   // ---- synthesis FIR (1, subbands, taps): learned (models.py:357) or fixed PQMF (pqmf.py:65-76,83);
   //      the zero-stuffing gain `subbands` (models.py:405, pqmf.py:116) is folded in.
-  if (pk.status == QVC_OK) {
+  if (pk.status == QVC_OK && !single) {
     std::vector<float> fir;
     if (cfg->decoder == QVC_DEC_MULTISTREAM) {
       fir = pk.weight("dec.multistream_conv_post", 1, cfg->subbands, cfg->fir_taps);

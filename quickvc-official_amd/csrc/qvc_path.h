@@ -12,14 +12,28 @@
 //                      int wn(const ConvDesc& in, const ConvDesc& rs, const WnArgs&, int batch, int dtype);
 //                      int gemv(const GemvArgs&); int sample(const SampleArgs&);
 //                      int tail(const TailArgs&); int zero(void* ptr, size_t bytes);
+//                      optional, the single-band decoder (QVC_DEC_ISTFT):  int tail1(const TailArgs&);
+//                      int post_tail1(const ConvDesc&, const PostTailArgs&, int batch, int dtype) -- a backend without
+//                      them (has_single_band_tail) returns QVC_ERR_BAD_CONFIG for that decoder
 //                      void fork(int n); void branch(int j); void branch_done(int j);
 //                      void wait_branch_done(int j); void join(int n);   (stream fork/join; no-ops on one stream)
 #pragma once
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
+#include <utility>
 #include "qvc_kernels.h"
 
 namespace qvc {
+
+// Does a backend run the single-band tail (tail1 / post_tail1)?  Detected at compile time, so that a backend written
+// before the single-band decoder existed keeps building and refuses that decoder instead of running the four-band tail.
+template <class B, class = void> struct has_single_band_tail : std::false_type {};
+template <class B>
+struct has_single_band_tail<B, std::void_t<decltype(std::declval<B&>().tail1(std::declval<const TailArgs&>())),
+                                           decltype(std::declval<B&>().post_tail1(std::declval<const ConvDesc&>(),
+                                                                                  std::declval<const PostTailArgs&>(), 0, 0))>>
+    : std::true_type {};
 
 template <class Backend>
 struct Path {
@@ -262,8 +276,10 @@ struct Path {
   // frames then never reach `post_buf`), else conv_post -> post_buf -> tail
   void dec_trunk_wave(const float* z, float* post_buf, float* wave) { dec_part(z, post_buf, 0, (int)P.stages.size(), true, true, wave); }
   void dec_back_wave(float* post_buf, float* wave) { dec_part(nullptr, post_buf, 1, (int)P.stages.size(), false, true, wave); }
+  bool single_band() const { return P.cfg.decoder == QVC_DEC_ISTFT; }
   void dec_part(const float* z, float* post_out, int stage_lo, int stage_hi, bool with_pre, bool with_post, float* wave = nullptr) {
     const qvc_config& c = P.cfg;
+    if (wave && single_band() && !has_single_band_tail<Backend>::value) status = QVC_ERR_BAD_CONFIG;
     const int C = c.inter_channels, C0 = c.upsample_initial_channel;
     if (with_pre) {   // conv_pre(k7) + cond(g), then the first stage's leaky ReLU fused into the store
       ConvArgs a = args(P.conv_pre);
@@ -278,12 +294,12 @@ struct Path {
     for (size_t i = 0; i < (size_t)stage_hi; ++i) {
       if ((int)i < stage_lo) {                       // geometry of the stages this call skips
         const int s_ = P.stages[i].up.up_s, p_ = P.stages[i].up.up_p, k_ = c.upsample_kernel_sizes[i];
-        t_in = (t_in - 1) * s_ - 2 * p_ + k_ + (1 - (int)i); ch_in = P.stages[i].ch; rate *= s_;
+        t_in = (t_in - 1) * s_ - 2 * p_ + k_ + up_output_padding(c, (int)i); ch_in = P.stages[i].ch; rate *= s_;
         continue;
       }
       const StagePlan& st = P.stages[i];
       const int s = st.up.up_s, p = st.up.up_p, k = c.upsample_kernel_sizes[i];
-      const int t_out = (t_in - 1) * s - 2 * p + k + (1 - (int)i);         // models.py:335
+      const int t_out = (t_in - 1) * s - 2 * p + k + up_output_padding(c, (int)i);   // models.py:335 / :124-127
       const int ch = st.ch;
       const int64_t bs = (int64_t)t_out * ch;
       {   // lrelu(0.1) -> ConvTranspose1d as `s` polyphase filters
@@ -414,7 +430,7 @@ struct Path {
       }
       t_in = t_out; ch_in = ch;
     }
-    if (with_post) {   // lrelu(0.01) -> ReflectionPad1d((1,0)) -> subband_conv_post(k7)
+    if (with_post) {   // lrelu(0.01) -> ReflectionPad1d((1,0)) -> subband_conv_post(k7) / conv_post (single band)
       ConvArgs a = args(P.conv_post);
       mean_input(a, P.stages.size() - 1);
       a.x_bs = (int64_t)t_in * ch_in; a.x_ts = ch_in;
@@ -423,9 +439,10 @@ struct Path {
       if (wave && be.post_tail_ok(P.conv_post)) {
         if (status != QVC_OK) return;
         PostTailArgs pt;
-        pt.c = a; pt.fir = reinterpret_cast<const float*>(blob + P.fir_off); pt.out = wave; pt.F = t_in + 1;
+        pt.c = a; pt.fir = single_band() ? nullptr : reinterpret_cast<const float*>(blob + P.fir_off); pt.out = wave; pt.F = t_in + 1;
         pt.rg = rg(P.total_up, 1);
-        status = be.post_tail(P.conv_post, pt, B, dtype_dec());
+        if (!single_band()) status = be.post_tail(P.conv_post, pt, B, dtype_dec());
+        else if constexpr (has_single_band_tail<Backend>::value) status = be.post_tail1(P.conv_post, pt, B, dtype_dec());
         return;
       }
       a.y32 = post_out; a.y32_bs = (int64_t)(t_in + 1) * P.post_channels; a.y32_ts = P.post_channels;
@@ -438,7 +455,10 @@ struct Path {
     if (status != QVC_OK) return;
     TailArgs ta{post, reinterpret_cast<const float*>(blob + P.fir_off), out, y_mb, B, F};
     ta.rg = rg(P.total_up, 1);
-    status = be.tail(ta);
+    if (!single_band()) { status = be.tail(ta); return; }
+    ta.fir = nullptr; ta.bands = 1;
+    if constexpr (has_single_band_tail<Backend>::value) status = be.tail1(ta);
+    else status = QVC_ERR_BAD_CONFIG;
   }
 };
 

@@ -204,7 +204,7 @@ struct Plan {
   // cond GEMV: fp32 weights [cond_rows][gin] + bias [cond_rows]
   int32_t cond_rows = 0;
   int64_t cond_w_off = 0, cond_b_off = 0;
-  // synthesis FIR: fp32 [subbands][fir_taps], zero-stuffing gain folded in
+  // synthesis FIR: fp32 [subbands][fir_taps], zero-stuffing gain folded in (empty for the single-band decoder)
   int64_t fir_off = 0;
   int64_t blob_bytes = 0;
 };
@@ -220,12 +220,15 @@ inline int validate(const qvc_config& c) {
   if (bad(c.n_ups < 1 || c.n_ups > QVC_MAX_UPS || c.n_resblocks != 3)) return QVC_ERR_BAD_CONFIG;   // the MRF mean is taken over three ResBlocks
   int ch = c.upsample_initial_channel;
   if (bad(ch <= 0 || ch % 8)) return QVC_ERR_BAD_CONFIG;
+  const bool single = c.decoder == QVC_DEC_ISTFT;
   for (int i = 0; i < c.n_ups; ++i) {
     int s = c.upsample_rates[i], k = c.upsample_kernel_sizes[i];
     if (bad(s < 1 || s > 16 || k < s || k > 64)) return QVC_ERR_BAD_CONFIG;
     // models.py:335: padding (k-s+1-i)//2 with output_padding 1-i gives T_out = s*T_in only when k-s+1-i is even;
-    // the workspace carve-up, the tail and the output shape all assume s*T_in (and PyTorch rejects output_padding < 0)
-    if (bad((k - s + 1 - i) < 0 || (k - s + 1 - i) % 2 != 0 || i > 1)) return QVC_ERR_BAD_CONFIG;
+    // the workspace carve-up, the tail and the output shape all assume s*T_in (and PyTorch rejects output_padding < 0).
+    // The single-band decoder (models.py:124-127): padding (k-s)//2, no output_padding -> s*T_in when k-s is even.
+    if (single) { if (bad((k - s) % 2 != 0)) return QVC_ERR_BAD_CONFIG; }
+    else if (bad((k - s + 1 - i) < 0 || (k - s + 1 - i) % 2 != 0 || i > 1)) return QVC_ERR_BAD_CONFIG;
     if (bad(ch % 2)) return QVC_ERR_BAD_CONFIG;
     ch /= 2;
     if (bad(ch % 8)) return QVC_ERR_BAD_CONFIG;
@@ -236,11 +239,20 @@ inline int validate(const qvc_config& c) {
     for (int p = 0; p < 3; ++p) if (bad(c.resblock_dilations[j][p] < 1 || c.resblock_dilations[j][p] > 16)) return QVC_ERR_BAD_CONFIG;
   }
   if (bad(c.n_fft != 16 || c.hop != 4)) return QVC_ERR_BAD_CONFIG;           // the tail kernel is built for 16/4
-  if (bad(c.decoder != QVC_DEC_MULTISTREAM && c.decoder != QVC_DEC_MULTIBAND)) return QVC_ERR_BAD_CONFIG;
-  if (bad(c.subbands != 4 || c.fir_taps != 63)) return QVC_ERR_BAD_CONFIG;
+  if (bad(c.decoder != QVC_DEC_MULTISTREAM && c.decoder != QVC_DEC_MULTIBAND && c.decoder != QVC_DEC_ISTFT)) return QVC_ERR_BAD_CONFIG;
+  if (single) { if (bad(c.subbands != 1)) return QVC_ERR_BAD_CONFIG; }      // no band synthesis: fir_taps is ignored
+  else if (bad(c.subbands != 4 || c.fir_taps != 63)) return QVC_ERR_BAD_CONFIG;
   if (bad(c.operand_dtype != QVC_BF16 && c.operand_dtype != QVC_F16 && c.operand_dtype != QVC_BF16X)) return QVC_ERR_BAD_CONFIG;
   return QVC_OK;
 }
+
+// Up-sampler i as a ConvTranspose1d: padding and output_padding.  Multistream / multiband: (k-s+1-i)//2 and 1-i
+// (models.py:333-335); single band: (k-s)//2 and none (models.py:124-127).  Both give s*T_in frames (validate()).
+inline int up_padding(const qvc_config& c, int i) {
+  const int s = c.upsample_rates[i], k = c.upsample_kernel_sizes[i];
+  return c.decoder == QVC_DEC_ISTFT ? (k - s) / 2 : (k - s + 1 - i) / 2;
+}
+inline int up_output_padding(const qvc_config& c, int i) { return c.decoder == QVC_DEC_ISTFT ? 0 : 1 - i; }
 
 inline ConvDesc make_conv(int M, int Cin, int taps, int dil, bool gau = false) {
   ConvDesc d;
@@ -338,7 +350,7 @@ inline Plan build_plan(const qvc_config& c) {
   for (int i = 0; i < c.n_ups; ++i) {
     StagePlan st;
     int s = c.upsample_rates[i], k = c.upsample_kernel_sizes[i];
-    int p = (k - s + 1 - i) / 2;              // models.py:335 (output_padding 1-i only sets T_out)
+    int p = up_padding(c, i);                 // (the output_padding only sets T_out)
     st.up = make_upconv(ch, ch / 2, k, s, p); place(st.up);
     ch /= 2; st.ch = ch; st.rate = s; P.total_up *= s;
     for (int j = 0; j < c.n_resblocks; ++j)
@@ -352,12 +364,17 @@ inline Plan build_plan(const qvc_config& c) {
     P.stages.push_back(st);
   }
   P.post_channels = c.subbands * 2 * (c.n_fft / 2 + 1);
-  P.conv_post = make_conv(P.post_channels, ch, 7, 1); place(P.conv_post);
-  // ---- cond GEMV table and FIR
+  P.conv_post = make_conv(P.post_channels, ch, 7, 1);
+  // single band: 18 rows packed as 4 waves x 2 fragments (the generic conv kernel's MF 2 / WM 4 variant, 128 rows);
+  // the fused tail kernel walks wave 0's stream only (rows 0..31, the only real ones) -- post_tail_supported()
+  if (c.decoder == QVC_DEC_ISTFT) { P.conv_post.MF = 2; P.conv_post.WM = 4; P.conv_post.nchunk = 1; }
+  place(P.conv_post);
+  // ---- cond GEMV table and FIR (none for the single-band decoder)
   P.cond_rows = cond_rows;
   P.cond_w_off = off; off = align_up(off + (int64_t)cond_rows * c.gin_channels * 4, 256);
   P.cond_b_off = off; off = align_up(off + (int64_t)cond_rows * 4, 256);
-  P.fir_off = off; off = align_up(off + (int64_t)c.subbands * c.fir_taps * 4, 256);
+  P.fir_off = off;
+  if (c.decoder != QVC_DEC_ISTFT) off = align_up(off + (int64_t)c.subbands * c.fir_taps * 4, 256);
   P.blob_bytes = off;
   return P;
 }

@@ -12,34 +12,47 @@
 //   OLA     band samples [a0 - 7, a0 + OT/4 + 7]
 //   FIR     OT output samples, 16-byte stores
 // Uses conv_post's packed weights as they are (ConvDesc MF 3 / WM 2 / 1 chunk, checked by post_tail_supported).
+//
+// NB = 1, the single-band decoder (models.py:164-176: conv_post with 18 channels, its iSTFT output IS the waveform):
+// 4 waves along the frames, each multiplying the row fragments of wave 0 of conv_post's packing [18 -> 32 rows] for
+// NF*16 frames; the tile's NT - 4 output frames sit between a +-2-frame overlap-add halo (the conv's +-3 frames are
+// the input tile's halo rows), and the OLA phase writes 4 waveform samples per frame, 16 bytes per lane.  No FIR.
 #pragma once
 #include "qvc_conv_impl.h"
 #include "qvc_tail_impl.h"
 
 namespace qvc {
 
-template <int NF> struct PostTailGeom {
-  static constexpr int NT = 2 * NF * 16;        // post-conv frames of the tile
-  static constexpr int OF = NT - 7;             // output frames owned
-  static constexpr int OT = OF * 16;            // output samples owned
-  static constexpr int NY = OT / 4 + 15;        // band samples needed
+template <int NF, int NB = kBands> struct PostTailGeom {
+  static constexpr int MF = NB == 1 ? 2 : 3;    // row fragments per wave in conv_post's packed stream
+  static constexpr int WM = NB == 1 ? 1 : 2;    // waves of this kernel along the rows (the other 4/WM split the frames);
+                                                // one band: every wave reads the packing's wave-0 stream (rows 0..31)
+  static constexpr int NT = (4 / WM) * NF * 16; // post-conv frames of the tile
+  static constexpr int HL = NB == 1 ? 2 : 3;    // post-conv frames in front of the first output frame
+  static constexpr int OF = NT - (NB == 1 ? 4 : 7);   // output frames owned
+  static constexpr int SPF = NB == 1 ? 4 : 16;  // output samples per frame
+  static constexpr int OT = OF * SPF;           // output samples owned
+  static constexpr int NY = NB == 1 ? 0 : OT / 4 + 15;   // band samples needed (band synthesis only)
+  static constexpr int PC = NB * 2 * kBins;     // post-conv channels
+  static constexpr int PS = NB == 1 ? 20 : PC;  // LDS floats per post-conv frame (one band: 16-byte rows)
 };
-inline size_t post_tail_lds(int nf, int taps, int CinP) {
-  const int NT = 2 * nf * 16, NY = (NT - 7) * 4 + 15;
-  const size_t tile = std::max<size_t>((size_t)(NT + taps - 1) * CinP * 2, (size_t)NT * kPostC * 4);
-  return align_up((int64_t)tile, 16) + (size_t)kBands * (NY + 1) * 4;
+template <int NF, int NB = kBands>
+inline size_t post_tail_lds(int taps, int CinP) {
+  using G = PostTailGeom<NF, NB>;
+  const size_t tile = std::max<size_t>((size_t)(G::NT + taps - 1) * CinP * 2, (size_t)G::NT * G::PS * 4);
+  return align_up((int64_t)tile, 16) + (size_t)NB * (G::NY + 1) * 4 * (NB > 1 ? 1 : 0);
 }
 
-template <typename T, int NF>
+template <typename T, int NF, int NB = kBands>
 // (three workgroups per CU at NF 4, four at NF 2: the phases of one workgroup are serial -- memory, MFMA, VALU/LDS
 //  in turn -- so it is the neighbours that fill each unit; measured 94 -> 78 us going from two to three)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NF == 2 ? 4 : 3, NF == 2 ? 4 : 3)))
 void post_tail_kernel(const PostTailArgs A) {
   using O = Op<T>;
   using frag = typename O::frag;
-  using G = PostTailGeom<NF>;
+  using G = PostTailGeom<NF, NB>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int MF = 3, WM = 2;
+  constexpr int MF = G::MF, WM = G::WM, PS = G::PS;
   constexpr int NT = G::NT, OT = G::OT, NY = G::NY;
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -48,10 +61,10 @@ void post_tail_kernel(const PostTailArgs A) {
   const int lrow = lane & 15, lq = lane >> 4;
   const int b = blockIdx.y;
   const int o0 = blockIdx.x * OT;
-  const int a0 = o0 >> 2;                       // first band sample owned by this block
-  const int f_lo = (o0 >> 4) - 3;               // first post-conv frame of the tile
+  const int a0 = NB == 1 ? o0 : o0 >> 2;        // first band sample owned by this block (one band: = output sample)
+  const int f_lo = (a0 >> 2) - G::HL;           // first post-conv frame of the tile
   const int Lpad = 4 * (A.F - 1);
-  const int n_out = 4 * Lpad;
+  const int n_out = NB * Lpad;
   const int Fb = ragged_len(A.rg, b, A.F);      // this utterance's post-conv frames are [Flo, Fb)
   const int Flo = ragged_lo(A.rg, b);
   const int L = Fb > 0 ? 4 * (Fb - 1) : 0;
@@ -74,7 +87,7 @@ void post_tail_kernel(const PostTailArgs A) {
   const int t_base = f_lo - A.c.left;           // input frame (after the reflect pad) of tile row 0
   const int Tin = ragged_len(A.c.rg, b, A.c.T_in);
   const int Tlo = ragged_lo(A.c.rg, b);
-  const int in_bytes = R * rowbytes, post_bytes = NT * kPostC * 4;
+  const int in_bytes = R * rowbytes, post_bytes = NT * PS * 4;
   const int tile_bytes = ((in_bytes > post_bytes ? in_bytes : post_bytes) + 15) & ~15;   // == post_tail_lds()'s first region
   float* s_post = reinterpret_cast<float*>(smem);
   float* s_y = reinterpret_cast<float*>(smem + tile_bytes);       // [band][NY + 1]
@@ -136,19 +149,20 @@ void post_tail_kernel(const PostTailArgs A) {
 #pragma unroll
     for (int n = 0; n < NF; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
   const frag* ap = static_cast<const frag*>(A.c.w) + ((size_t)wm * A.c.nIt * MF) * 64 + lane;
-  if (wm == 0) {
+  if (NB == 4 && wm == 0) {
     gemm_loop<T, MF, NF, QVC_PF_CONV>(acc, ap, A.c.nIt, A.c.KS, 1, smem, rowbytes, sm, wn * (NF * 16) + lrow, lq, 0);
-  } else {        // rows 48..95: the third fragment (80..95) is all padding -- 72 channels -- and is neither loaded nor multiplied
+  } else {        // four bands, rows 48..95: the third fragment (80..95) is all padding -- 72 channels -- and is neither
+                  // loaded nor multiplied; one band: rows 0..31 (18 channels), the packing's waves 1..3 are never read
     f32x4 (&acc2)[2][NF] = reinterpret_cast<f32x4 (&)[2][NF]>(acc);
     gemm_loop<T, 2, NF, QVC_PF_CONV, MF>(acc2, ap, A.c.nIt, A.c.KS, 1, smem, rowbytes, sm, wn * (NF * 16) + lrow, lq, 0);
   }
   __syncthreads();                              // every wave is done with the input tile
 
-  // ------------------------------------------------------------------ post-conv frames -> LDS fp32 [frame][72]
+  // ------------------------------------------------------------------ post-conv frames -> LDS fp32 [frame][PS]
 #pragma unroll
-  for (int m = 0; m < MF; ++m) {
+  for (int m = 0; m < (NB == 1 ? 2 : MF); ++m) {
     const int v = (wm * MF + m) * 16 + lq * 4;
-    if (v >= kPostC) continue;
+    if (v >= G::PC) continue;                   // (one band: rows 16..19 land in the frame's padded 20-float row)
     float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
     if (A.c.bias) bias = *reinterpret_cast<const float4*>(A.c.bias + v);
 #pragma unroll
@@ -157,15 +171,15 @@ void post_tail_kernel(const PostTailArgs A) {
       const int t = f_lo + fr;
       float4 val = make_float4(0.f, 0.f, 0.f, 0.f);
       if (t >= Flo && t < Fb) val = make_float4(acc[m][n][0] + bias.x, acc[m][n][1] + bias.y, acc[m][n][2] + bias.z, acc[m][n][3] + bias.w);
-      *reinterpret_cast<float4*>(&s_post[fr * kPostC + v]) = val;
+      *reinterpret_cast<float4*>(&s_post[fr * PS + v]) = val;
     }
   }
   __syncthreads();
 
   // ------------------------------------------------------------------ per (frame, band): polar -> inverse DFT -> window, in place
-  for (int item = tid; item < NT * kBands; item += 256) {
-    const int fr = item >> 2, k = item & 3;
-    float* sp = &s_post[fr * kPostC + k * 2 * kBins];
+  for (int item = tid; item < NT * NB; item += 256) {
+    const int fr = item / NB, k = item % NB;
+    float* sp = &s_post[fr * PS + k * 2 * kBins];
     float xw[16];
     tail_dft(sp, xw);
 #pragma unroll
@@ -173,11 +187,24 @@ void post_tail_kernel(const PostTailArgs A) {
   }
   __syncthreads();
 
+  if constexpr (NB == 1) {
+    // ---------------------------------------------------------------- overlap-add + envelope = the waveform: 4 samples per item
+    for (int j = tid; j < OT / 4; j += 256) {
+      const int n = a0 + 4 * j;
+      float y[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) y[r] = tail_ola(n + r, Flo, Fb, L, [&](int t, int m) { return s_post[(t - f_lo) * PS + m]; });
+      if (n + 3 < n_out) *reinterpret_cast<float4*>(outb + n) = make_float4(y[0], y[1], y[2], y[3]);
+      else for (int r = 0; r < 4; ++r) if (n + r < n_out) outb[n + r] = y[r];
+    }
+    return;
+  }
+
   // ------------------------------------------------------------------ overlap-add + envelope: band samples n = a0 - 7 + i
   for (int item = tid; item < NY * kBands; item += 256) {
     const int k = item / NY, i = item - k * NY;
     const int n = a0 - 7 + i;
-    s_y[k * (NY + 1) + i] = tail_ola(n, Flo, Fb, L, [&](int t, int m) { return s_post[(t - f_lo) * kPostC + k * 2 * kBins + m]; });
+    s_y[k * (NY + 1) + i] = tail_ola(n, Flo, Fb, L, [&](int t, int m) { return s_post[(t - f_lo) * PS + k * 2 * kBins + m]; });
   }
   __syncthreads();
 
@@ -196,24 +223,28 @@ void post_tail_kernel(const PostTailArgs A) {
   }
 }
 
-template <typename T, int NF>
+template <typename T, int NF, int NB>
 inline int launch_post_tail_nf(const ConvDesc& d, const PostTailArgs& a, int batch, hipStream_t stream) {
-  auto kern = post_tail_kernel<T, NF>;
-  const size_t lds = post_tail_lds(NF, d.taps, d.CinP);
+  auto kern = post_tail_kernel<T, NF, NB>;
+  const size_t lds = post_tail_lds<NF, NB>(d.taps, d.CinP);
   if (lds > 160 * 1024) return QVC_ERR_BAD_CONFIG;
   static std::atomic<uint32_t> lds_ok{0};
   if (!allow_big_lds(lds_ok, reinterpret_cast<const void*>(kern))) return QVC_ERR_LAUNCH;
-  const int n_out = 16 * (a.F - 1);
-  hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n_out, PostTailGeom<NF>::OT), (unsigned)batch), dim3(256), lds, stream, a);
+  const int n_out = NB * 4 * (a.F - 1);
+  hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n_out, PostTailGeom<NF, NB>::OT), (unsigned)batch), dim3(256), lds, stream, a);
   return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
 }
 
 template <typename T>
 int launch_post_tail_typed(const ConvDesc& d, const PostTailArgs& a, int batch, void* stream_v) {
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
-  if (!post_tail_supported(d) || a.F < 2 || !a.c.x2 || !a.c.x3 || a.c.x_kind != XK_OP_FM) return QVC_ERR_BAD_CONFIG;
-  if (debug_get(DBG_POST_TAIL_NF) == 2) return launch_post_tail_nf<T, 2>(d, a, batch, stream);
-  return launch_post_tail_nf<T, 4>(d, a, batch, stream);
+  const int nb = post_tail_bands(d);
+  if (!nb || a.F < 2 || !a.c.x2 || !a.c.x3 || a.c.x_kind != XK_OP_FM) return QVC_ERR_BAD_CONFIG;
+  // one band: 4 waves along the frames at NF 2 = the same 128-frame tile as the four-band default
+  if (nb == 1) return launch_post_tail_nf<T, 2, 1>(d, a, batch, stream);
+  if (!a.fir) return QVC_ERR_BAD_CONFIG;
+  if (debug_get(DBG_POST_TAIL_NF) == 2) return launch_post_tail_nf<T, 2, kBands>(d, a, batch, stream);
+  return launch_post_tail_nf<T, 4, kBands>(d, a, batch, stream);
 }
 
 }  // namespace qvc

@@ -3,11 +3,13 @@
 //   * sample_kernel      : z_p = mu + noise*exp(logs) (models.py:93-94), noise read in (B,C,T)
 //   * istft_synth_kernel : exp / pi*sin / 16-point inverse real DFT / Hann overlap-add /
 //                          envelope / x4 zero-stuff / 63-tap synthesis FIR in ONE pass
+//                          (single-band decoder: the overlap-add output is the waveform)
 //                          (models.py:394-406, pqmf.py:106-117) -- no complex tensors, no
 //                          zero-stuffed intermediate, each post-conv frame read once (+halo).
 //   * fm_to_cm_kernel    : frame-major -> (B,C,T) for the unit-test conv entry point.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <type_traits>
 #include "qvc_launch_util.h"
 #include "qvc_kernels.h"
 #include "qvc_tail_impl.h"
@@ -140,71 +142,103 @@ int launch_sample(const SampleArgs& a, void* stream) {
 
 // ------------------------------------------------------------------ iSTFT + band synthesis tail
 // (formulas and the per-item math: qvc_tail_impl.h)
-// One block = kOT consecutive output samples = kOT/4 band samples (+-7/8 halo) = kOT/16 frames (+-3/4).
-constexpr int kOT = 912;                   // output samples per block: 57 + 7 = 64 frames x 4 bands = exactly one
+// Four bands: one block = OT consecutive output samples = OT/4 band samples (+-7/8 halo) = OT/16 frames (+-3/4).
+// One band (QVC_DEC_ISTFT, models.py:171-176): the iSTFT output is the waveform, one block = OT samples = OT/4 frames
+// (+-2: the overlap-add's reach), no FIR.
+template <int NB> struct SynthTile;
+template <> struct SynthTile<kBands> {
+  static constexpr int OT = 912;           // output samples per block: 57 + 7 = 64 frames x 4 bands = exactly one
                                            // (frame, band) item per thread in the DFT phase (1024 needed two rounds)
-constexpr int kNY = kOT / 4 + 15;          // band samples needed: [a0-7, a0+kOT/4+7]
-constexpr int kNFR = kOT / 16 + 7;         // frames needed: [f0-3, f0+kOT/16+3]
+  static constexpr int NY = OT / 4 + 15;   // band samples needed: [a0-7, a0+OT/4+7]
+  static constexpr int NFR = OT / 16 + 7;  // frames needed: [f0-3, f0+OT/16+3]
+  static constexpr int HL = 3;
+};
+template <> struct SynthTile<1> {
+  static constexpr int OT = 1008;          // 252 + 4 = 256 frames: one DFT item per thread
+  static constexpr int NY = 1;             // (no band-sample buffer)
+  static constexpr int NFR = OT / 4 + 4;   // frames needed: [f0-2, f0+OT/4+2)
+  static constexpr int HL = 2;
+};
 
+template <int NB>
 __global__ __launch_bounds__(256) void istft_synth_kernel(const TailArgs a) {
-  __shared__ __attribute__((aligned(16))) float s_post[kNFR * kPostC];    // 20.4 KB
-  __shared__ float s_xw[kBands][kNFR][17];                                // windowed frames (padded)
-  __shared__ float s_y[kBands][kNY + 1];
+  using G = SynthTile<NB>;
+  constexpr int PC = NB * 2 * kBins;       // post-conv channels per frame
+  constexpr int VW = NB == 1 ? 2 : 4;      // staging vector width (a single band's 18-float frames are 8-byte aligned)
+  using V = typename std::conditional<NB == 1, float2, float4>::type;
+  __shared__ __attribute__((aligned(16))) float s_post[G::NFR * PC];     // 20.4 KB (one band: 18 KB)
+  __shared__ float s_xw[NB][G::NFR][17];                                 // windowed frames (padded)
+  __shared__ float s_y[NB][G::NY + 1];
 
   const int tid = threadIdx.x;
   const int b = blockIdx.y;
-  const int o0 = blockIdx.x * kOT;
-  const int a0 = o0 >> 2;                   // first band sample owned by this block
-  const int f_lo = (o0 >> 4) - 3;           // first frame staged
-  const int Lpad = 4 * (a.F - 1);           // band signal length of the (padded) buffers
+  const int o0 = blockIdx.x * G::OT;
+  const int a0 = NB == 1 ? o0 : o0 >> 2;   // first band sample owned by this block
+  const int f_lo = (a0 >> 2) - G::HL;      // first frame staged
+  const int Lpad = 4 * (a.F - 1);          // band signal length of the (padded) buffers
   const int Fb = ragged_len(a.rg, b, a.F);  // this utterance's frames are [Flo, Fb) of the buffer (ragged batches,
   const int Flo = ragged_lo(a.rg, b);       // streaming windows): its iSTFT envelope starts / ends there
   const int L = Fb > 0 ? 4 * (Fb - 1) : 0;  // its band signal is [4*Flo, L); samples outside are zeros
-  const float* pb = a.post + (size_t)b * a.F * kPostC;
+  const float* pb = a.post + (size_t)b * a.F * PC;
 
-  // ---- stage frames [f_lo, f_lo+kNFR) x 72 channels (contiguous in memory), float4 coalesced
+  // ---- stage frames [f_lo, f_lo+NFR) x PC channels (contiguous in memory), vector loads, coalesced
   {   // all of a thread's loads go out before its first LDS store (one per loop trip = serialised round trips)
-    constexpr int kChunks = kNFR * (kPostC / 4), kPer = (kChunks + 255) / 256;
-    float4 v[kPer];
+    constexpr int kChunks = G::NFR * (PC / VW), kPer = (kChunks + 255) / 256;
+    V v[kPer];
 #pragma unroll
     for (int u = 0; u < kPer; ++u) {
       const int i = tid + u * 256;
-      const int fr = i / (kPostC / 4), c4 = i - fr * (kPostC / 4);
+      const int fr = i / (PC / VW), c4 = i - fr * (PC / VW);
       const int t = f_lo + fr;
-      v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (i < kChunks && t >= Flo && t < Fb) v[u] = *reinterpret_cast<const float4*>(pb + (size_t)t * kPostC + c4 * 4);
+      v[u] = V{};
+      if (i < kChunks && t >= Flo && t < Fb) v[u] = *reinterpret_cast<const V*>(pb + (size_t)t * PC + c4 * VW);
     }
 #pragma unroll
     for (int u = 0; u < kPer; ++u) {
       const int i = tid + u * 256;
-      if (i < kChunks) *reinterpret_cast<float4*>(&s_post[i * 4]) = v[u];
+      if (i < kChunks) *reinterpret_cast<V*>(&s_post[i * VW]) = v[u];
     }
   }
   __syncthreads();
 
   // ---- per (frame, band): polar -> 16-point inverse real DFT -> Hann window
-  for (int item = tid; item < kNFR * kBands; item += 256) {
-    const int fr = item >> 2, k = item & 3;
+  for (int item = tid; item < G::NFR * NB; item += 256) {
+    const int fr = item / NB, k = item % NB;
     float xw[16];
-    tail_dft(&s_post[fr * kPostC + k * 2 * kBins], xw);
+    tail_dft(&s_post[fr * PC + k * 2 * kBins], xw);
 #pragma unroll
     for (int m = 0; m < 16; ++m) s_xw[k][fr][m] = xw[m];
   }
   __syncthreads();
 
+  if constexpr (NB == 1) {
+    // ---- overlap-add + envelope = the waveform: thread -> 4 consecutive samples n = a0 + 4*j + r
+    for (int j = tid; j < G::OT / 4; j += 256) {
+      const int n = a0 + 4 * j;
+      float y[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) y[r] = tail_ola(n + r, Flo, Fb, L, [&](int t, int m) { return s_xw[0][t - f_lo][m]; });
+      float* ob = a.out + (size_t)b * Lpad;
+      if (n + 3 < Lpad) *reinterpret_cast<float4*>(ob + n) = make_float4(y[0], y[1], y[2], y[3]);
+      else for (int r = 0; r < 4; ++r) if (n + r < Lpad) ob[n + r] = y[r];
+      if (a.y_mb) for (int r = 0; r < 4; ++r) if (n + r < Lpad) a.y_mb[(size_t)b * Lpad + n + r] = y[r];
+    }
+    return;
+  }
+
   // ---- overlap-add + envelope: band samples n = a0 - 7 + i
-  for (int item = tid; item < kNY * kBands; item += 256) {
-    const int k = item / kNY, i = item - k * kNY;
+  for (int item = tid; item < G::NY * NB; item += 256) {
+    const int k = item / G::NY, i = item - k * G::NY;
     const int n = a0 - 7 + i;
     const float y = tail_ola(n, Flo, Fb, L, [&](int t, int m) { return s_xw[k][t - f_lo][m]; });
     s_y[k][i] = y;
-    if (a.y_mb && i >= 7 && i < 7 + kOT / 4 && n < Lpad)
-      a.y_mb[((size_t)b * kBands + k) * Lpad + n] = y;
+    if (a.y_mb && i >= 7 && i < 7 + G::OT / 4 && n < Lpad)
+      a.y_mb[((size_t)b * NB + k) * Lpad + n] = y;
   }
   __syncthreads();
 
   // ---- polyphase synthesis FIR: thread -> 4 consecutive outputs o = o0 + 4*tid + r
-  if (tid < kOT / 4) {
+  if (tid < G::OT / 4) {
     const int ia = tid + 7;                                  // s_y index of band sample a = a0 + tid
     float out[4];
     tail_fir<kTaps>([&](int k, int d) { return s_y[k][ia + d]; }, a.fir, out);
@@ -220,10 +254,15 @@ __global__ __launch_bounds__(256) void istft_synth_kernel(const TailArgs a) {
 }
 
 int launch_tail(const TailArgs& a, void* stream) {
-  const int n_out = 16 * (a.F - 1);
+  if (a.bands != 1 && a.bands != kBands) return QVC_ERR_BAD_ARG;
+  const int n_out = a.bands * 4 * (a.F - 1);
   if (n_out <= 0) return QVC_ERR_BAD_ARG;
-  hipLaunchKernelGGL(istft_synth_kernel, dim3((unsigned)ceil_div(n_out, kOT), (unsigned)a.batch), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), a);
+  if (a.bands == 1)
+    hipLaunchKernelGGL(istft_synth_kernel<1>, dim3((unsigned)ceil_div(n_out, SynthTile<1>::OT), (unsigned)a.batch), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), a);
+  else
+    hipLaunchKernelGGL(istft_synth_kernel<kBands>, dim3((unsigned)ceil_div(n_out, SynthTile<kBands>::OT), (unsigned)a.batch), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), a);
   return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
 }
 

@@ -37,6 +37,9 @@ inline StreamGeom stream_geom(const Plan& P, int hop) {
   const qvc_config& c = P.cfg;
   if (P.status != QVC_OK) { G.status = P.status; return G; }
   if (hop < 1 || c.n_ups != 2 || c.n_flows > 16) { G.status = hop < 1 ? QVC_ERR_BAD_ARG : QVC_ERR_BAD_CONFIG; return G; }
+  // the halo / lag arithmetic below is the band-synthesis decoders' (63-tap FIR, output_padding 1-i): streaming the
+  // single-band decoder is not built
+  if (c.decoder == QVC_DEC_ISTFT) { G.status = QVC_ERR_BAD_CONFIG; return G; }
   const int K2 = (c.wn_kernel_size - 1) / 2;
   G.hop = hop; G.nf = c.n_flows; G.r0 = c.upsample_rates[0];
   G.He = c.enc_layers * K2;
