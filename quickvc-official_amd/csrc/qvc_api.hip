@@ -190,9 +190,10 @@ struct TimedBackend {
     if (ev.empty()) mark();
     int st = launch_wn_stack(din, a, batch, dtype, stream);
     mark();
-    char name[48];
-    std::snprintf(name, sizeof(name), "%s<%s,W%d,L%d%s>", wn_stack_variant(din, a) == 2 ? "wn_stack2" : "wn_stack", dtype == QVC_F16 ? "f16" : "bf16",
-                  din.WM, a.layers, dpre ? ",pre+post" : "");
+    char name[56];
+    const int v = wn_stack_variant(din, a, batch);
+    std::snprintf(name, sizeof(name), "%s<%s,W%d,L%d%s%s>", v >= 2 ? "wn_stack2" : "wn_stack", dtype == QVC_F16 ? "f16" : "bf16",
+                  din.WM, a.layers, dpre ? ",pre+post" : "", v == 3 ? ",64f" : "");
     const double cols = (double)batch * a.T;
     const double fl = 2.0 * cols * a.H * (a.layers * 2.0 * a.H * a.taps + (a.layers - (a.final_layer ? 1 : 0)) * (double)drs.M + (a.final_layer ? (double)drs_last.M : 0.0));
     const double fuse_fl = (dpre ? 2.0 * cols * dpre->M * dpre->Cin : 0.0) + (dpost ? 2.0 * cols * dpost->M * dpost->Cin : 0.0);

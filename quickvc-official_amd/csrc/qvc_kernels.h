@@ -199,6 +199,7 @@ struct WnStackArgs {
   float* z = nullptr; int64_t z_bs = 0; int32_t z_ts = 0;
   float post_sign = -1.f;   // -1: reverse flow, x1 - m (modules.py:217); +1: forward flow, m + x1
   Ragged rg;
+  int32_t wide = 0;          // the 64-frame tile of the continuous-stream kernel may be used (launch_wn_stack decides)
 #ifdef QVC_STAMP
   unsigned long long* stamps = nullptr;   // developer build only (tools/conv_bench): [workgroup][16 waves][32] phase stamps
 #endif
@@ -272,7 +273,7 @@ enum DebugSwitch : int32_t {
   DBG_WN_CHUNK,             // 0 (default): 4 WaveNet layers per stack launch; n > 0: n layers; -1: one launch per layer, pre / post as convs
   DBG_PAIR_CHAIN3,          // 0 (default): off; 1: the three pairs of a short-kernel ResBlock chained in one launch (qvc_chain_impl.h:
                             //    bit-identical, measured SLOWER -- the k 3 pairs cost less riding in the three-chain launches)
-  DBG_WN_KERNEL,            // WaveNet stack kernel variant (0 = default)
+  DBG_WN_KERNEL,            // WaveNet stack kernel variant (0 = default; 1 generic, 2 / 3 the 32- / 64-frame continuous-stream tile)
   DBG_COUNT
 };
 inline std::atomic<int32_t>* debug_table() {
@@ -294,7 +295,7 @@ int launch_pair3(const ConvDesc* d1, const ConvDesc* d2, const PairArgs3& a, int
 int launch_chain(const ConvDesc* d1, const ConvDesc* d2, const ChainArgs& a, int batch, int dtype, void* stream, int* nf_out = nullptr);
 bool wn_stack_supported(const ConvDesc& din, int layers);
 int launch_wn_stack(const ConvDesc& din, const WnStackArgs& a, int batch, int dtype, void* stream);
-int wn_stack_variant(const ConvDesc& din, const WnStackArgs& a);   // 2: the continuous-stream kernel (qvc_wn2_impl.h), 1: the generic one
+int wn_stack_variant(const ConvDesc& din, const WnStackArgs& a, int batch);   // 3 / 2: the continuous-stream kernel (qvc_wn2_impl.h) in its 64- / 32-frame tile, 1: the generic one
 int launch_wn(const ConvDesc& din, WnArgs a, int batch, int dtype, void* stream, int* nf_out = nullptr);
 int launch_gemv(const GemvArgs& a, void* stream);
 

@@ -55,6 +55,9 @@ struct Path {
   bool unit_fm = false;
   // streaming: stage-0 ResBlock outputs handed over from a previous window instead of this call's own (dec_back)
   const void* s0_override[3] = {nullptr, nullptr, nullptr};
+  // the WaveNet stacks may run in the continuous-stream kernel's 64-frame tile (launch_wn_stack picks it where the grid
+  // is large); the streaming windows keep the 32-frame tile, not measured there
+  bool wn_wide = true;
 
   template <typename U> U* wsp(int64_t off) const { return reinterpret_cast<U*>(ws + off); }
   int dtype_wn() const { return wn_dtype(P.cfg); }     // enc_p / enc_q / flow
@@ -113,7 +116,7 @@ struct Path {
         a.layers = chunk; a.taps = wn.in_conv[0].taps; a.KS = wn.in_conv[0].KS(); a.nIt1 = wn.in_conv[0].nIt();
         a.final_layer = l0 + chunk == wn.layers ? 1 : 0;
         a.accum = l0 > 0 ? 1 : 0;
-        a.rg = rg(1);
+        a.rg = rg(1); a.wide = wn_wide ? 1 : 0;
         a.x_out = a.final_layer ? nullptr : wsp<float>(part % 2 == 0 ? W.xw2 : W.xw);
         if (status == QVC_OK) status = be.wn_stack(wn.in_conv[0], wn.rs_conv[0], wn.rs_conv[wn.layers - 1], a, B, dtype_wn(), nullptr, nullptr);
       }
@@ -231,7 +234,7 @@ struct Path {
         a.w_post = blob + f.post.w_off; a.b_post = reinterpret_cast<const float*>(blob + f.post.b_off);
         a.post_m = f.post.M; a.post_c0 = f.out_c0; a.post_mf = f.post.MF;
         a.z = z; a.z_bs = (int64_t)T * C; a.z_ts = C; a.post_sign = sign;
-        a.rg = rg(1);
+        a.rg = rg(1); a.wide = wn_wide ? 1 : 0;
         if (status == QVC_OK)
           status = be.wn_stack(din, f.wn.rs_conv[0], f.wn.rs_conv[f.wn.layers - 1], a, B, dtype_wn(), &f.pre, &f.post);
         return;

@@ -371,15 +371,27 @@ int launch_post_tail(const ConvDesc& d, PostTailArgs a, int batch, int dtype, vo
 
 bool wn_stack_supported(const ConvDesc& din, int layers) { return wn_stack_ok(din, layers); }
 
-// qvc_wn2.hip: the continuous-stream stack kernel for the shipped shape (debug switch "wn_kernel" = 1: always the generic one)
-template <typename T> int launch_wn_stack2_typed(const ConvDesc& din, const WnStackArgs& a, int batch, void* stream);
+// qvc_wn2.hip: the continuous-stream stack kernel for the shipped shape, in a 32- and a 64-frame tile.  The 64-frame
+// tile where the caller allows it (a.wide: not the streaming windows) and the 32-frame grid would fill the chip: there
+// it takes the same time per layer on half the CUs.  Smaller grids keep the 32-frame tile: their CUs are
+// free anyway, and a tile twice as wide takes longer per layer.  Debug switch "wn_kernel": 1 = the generic kernel,
+// 2 = always the 32-frame tile, 3 = always the 64-frame tile (where the kernel applies).
+template <typename T> int launch_wn_stack2_typed(const ConvDesc& din, const WnStackArgs& a, int batch, void* stream, bool wide);
 bool wn_stack2_supported(const ConvDesc& din, const WnStackArgs& a);
-int wn_stack_variant(const ConvDesc& din, const WnStackArgs& a) { return debug_get(DBG_WN_KERNEL) == 0 && wn_stack2_supported(din, a) ? 2 : 1; }
+constexpr long kWnWideMinTiles = 256;        // 32-frame workgroups (one per CU) from which the 64-frame tile is used
+int wn_stack_variant(const ConvDesc& din, const WnStackArgs& a, int batch) {
+  const int sw = debug_get(DBG_WN_KERNEL);
+  if (sw == 1 || !wn_stack2_supported(din, a)) return 1;
+  if (sw == 2) return 2;
+  if (sw == 3) return 3;
+  return a.wide && (long)batch * ceil_div(a.T, kWnOutFrames) >= kWnWideMinTiles ? 3 : 2;
+}
 
 int launch_wn_stack(const ConvDesc& din, const WnStackArgs& a, int batch, int dtype, void* stream) {
-  if (wn_stack_variant(din, a) == 2) {
-    if (dtype == QVC_F16) return launch_wn_stack2_typed<_Float16>(din, a, batch, stream);
-    if (dtype == QVC_BF16) return launch_wn_stack2_typed<__bf16>(din, a, batch, stream);
+  const int v = wn_stack_variant(din, a, batch);
+  if (v >= 2) {
+    if (dtype == QVC_F16) return launch_wn_stack2_typed<_Float16>(din, a, batch, stream, v == 3);
+    if (dtype == QVC_BF16) return launch_wn_stack2_typed<__bf16>(din, a, batch, stream, v == 3);
     return QVC_ERR_BAD_ARG;
   }
   if (dtype == QVC_F16) return launch_wn_stack_typed<_Float16>(din, a, batch, stream);

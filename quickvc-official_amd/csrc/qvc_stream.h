@@ -152,6 +152,7 @@ int stream_step(const Plan& P, const char* blob, char* state, char* ws, const fl
   auto make = [&](int T, int lag_before) {
     Path<Backend> p{P, blob, ws, carve_workspace(P, B, T), B, T, be};
     p.lens = lens; p.pos = pos; p.off = lag_before + (T - h);      // buffer row `off` is absolute frame pos[b]
+    p.wn_wide = false;
     return p;
   };
   const size_t zrow = (size_t)C * 4;                               // one frame of z

@@ -36,6 +36,10 @@ __device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make
 #ifndef QVC_WN2_SYNC
 #define QVC_WN2_SYNC 0
 #endif
+// register ring depth (k-steps) of the 64-frame tile; must divide a layer's 36 k-steps
+#ifndef QVC_WN2_WIDE_RING
+#define QVC_WN2_WIDE_RING 4
+#endif
 
 // the shapes this kernel is built for
 inline bool wn2_supported(const ConvDesc& din, const WnStackArgs& a) {
@@ -43,24 +47,43 @@ inline bool wn2_supported(const ConvDesc& din, const WnStackArgs& a) {
          a.HP == 192 && a.H <= 192 && a.KS == 6 && a.nIt1 == 30 && (!a.w_post || a.post_mf == 1) && (!a.w_pre || a.pre_KS <= 6);
 }
 
-template <typename T, int KS, int TAPS, int PM>
+// Window of NF x 16 columns: NB - 16 produced frames + up to 2 x 8 halo (4 layers of a k-5 conv).  NF = 3 (32 frames
+// per workgroup) is the kernel above; NF = 5 is the wide tile (64 frames, half the workgroups at batch 32): each weight
+// fragment feeds five MFMAs instead of three and a third fewer of them recompute halo, so the launch pulls half the
+// L2 -> CU traffic and leaves half the CUs to whatever shares the chip.  To fit its 80 columns into 160 KiB of LDS the
+// wide tile writes the gated activations over the x tile (x is dead after GEMM1 and rebuilt from the fp32 residual
+// slots after GEMM2), which costs two barriers per layer: before the gate's stores and before put_x.  RING: k-steps in
+// flight per wave (at five MFMAs per fragment four of them hold as many bytes in flight per CU-cycle as six at three).
+template <int KS, int TAPS, int NF>
+constexpr size_t wn2_lds_bytes() {
+  constexpr int RB = KS * 64, R = NF * 16 + TAPS - 1, NTH = KS * 2 * 64;
+  return (size_t)(NF > 3 ? R : R + NF * 16) * RB + (size_t)2 * NF * NTH * 16;    // x (+ gated) tile, fp32 residual + skip slots
+}
+
+template <typename T, int KS, int TAPS, int PM, int NF = 3, int RING = 6>
 __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArgs a) {
   using O = Op<T>;
   using frag = typename O::frag;
   using quad = typename O::quad;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int HP = KS * 32, RB = HP * 2, CPR = HP / 8;
-  constexpr int NF = 3, NB = NF * 16, OUTF = kWnOutFrames, ON = 3;
+  constexpr int NB = NF * 16, OUTF = NB - 16, ON = NF;
+  constexpr bool ALIAS = NF > 3;              // gated tile over the x tile (see above)
+  // B fragments: NF = 3 double-buffers a whole k-step (all of k+1 requested before k's MFMAs); the wide tile keeps ONE
+  // buffer and refills column block n for k+1 right behind k's two MFMAs on it (20 registers fewer: no scratch at 168)
+  constexpr bool ROLL = NF > 3;
+  constexpr int NBUF = ROLL ? 1 : 2;
   constexpr int LEFT = (TAPS - 1) / 2, R = NB + TAPS - 1;
   constexpr int NK1 = TAPS * KS, NK2 = KS, NKL = NK1 + NK2;
-  constexpr int RING = 6, PF = RING;          // a k-step's slot is refilled right after its MFMAs: six k-steps (12 KiB per wave) in flight
+  constexpr int PF = RING;                    // a k-step's slot is refilled right after its MFMAs: RING k-steps (2 KiB each per wave) in flight
   static_assert(NKL % RING == 0, "a layer must start on ring slot 0");
   static_assert(CPR % 8 == 0 && CPR % 16 != 0, "row swizzle = row & 7 (see swz_mode)");
-  constexpr int ACTS = R * RB;                // byte offset of the gated-activation tile
+  constexpr int ACTS = ALIAS ? 0 : R * RB;    // byte offset of the gated-activation tile
   constexpr int NTH = KS * 2 * 64;
   // fp32 residual stream and skip sum of the window: lane-private 16-byte slots in LDS ([n][thread]), touched only in a
   // layer's epilogue -- in registers (24 per lane) they pushed the K loops' ring into scratch memory
-  constexpr int XRES = ACTS + NB * RB, OACC = XRES + NF * NTH * 16;
+  constexpr int XRES = ALIAS ? R * RB : ACTS + NB * RB, OACC = XRES + NF * NTH * 16;
+  static_assert(OACC + NF * NTH * 16 == (int)wn2_lds_bytes<KS, TAPS, NF>(), "LDS layout");
   const Swz sm{0, 7, 0};
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -104,8 +127,10 @@ __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArg
   float4* const xres = reinterpret_cast<float4*>(smem + XRES) + tid;     // [n * NTH]
   float4* const oacc = reinterpret_cast<float4*>(smem + OACC) + tid;
 
-  // zero the x tile once: rows outside the window and K-padding channels must stay finite zeros
-  for (int i = tid; i < (R * RB) >> 4; i += NTH) reinterpret_cast<uint4*>(smem)[i] = make_uint4(0u, 0u, 0u, 0u);
+  // zero the x tile once: rows outside the window and K-padding channels must stay finite zeros (the wide tile: after
+  // the fused pre conv, which stages z in the gated tile = the x tile)
+  auto zero_x = [&] { for (int i = tid; i < (R * RB) >> 4; i += NTH) reinterpret_cast<uint4*>(smem)[i] = make_uint4(0u, 0u, 0u, 0u); };
+  if constexpr (!ALIAS) zero_x();
 
   f32x4 xr[NF];
   if (a.w_pre) {
@@ -141,7 +166,9 @@ __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArg
       xr[n] = in ? f32x4{pacc[0][n][0] + bp.x, pacc[0][n][1] + bp.y, pacc[0][n][2] + bp.z, pacc[0][n][3] + bp.w}
                  : f32x4{0.f, 0.f, 0.f, 0.f};
     }
+    if constexpr (ALIAS) __syncthreads();     // every wave is done reading z from the tile
   }
+  if constexpr (ALIAS) zero_x();
 #pragma unroll
   for (int n = 0; n < NF; ++n) {
     const int q = w0 + n * 16 + lrow;
@@ -209,24 +236,29 @@ __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArg
       for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int n = 0; n < NF; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-      frag bf[2][NF];
-      auto read_b = [&](auto k_c, frag (&dst)[NF]) {
+      frag bf[NBUF][NF];
+      auto read_bn = [&](auto k_c, int n, frag& dst) {
         constexpr int k = decltype(k_c)::value;
         constexpr int tap = k / KS, ks = k % KS;
         const char* bp = smem + ((ks & 1) ? (boff[tap] ^ 64) : boff[tap]) + (ks >> 1) * 128;
+        dst = *reinterpret_cast<const frag*>(bp + n * 16 * RB);
+      };
+      auto read_b = [&](auto k_c, frag (&dst)[NF]) {
 #pragma unroll
-        for (int n = 0; n < NF; ++n) dst[n] = *reinterpret_cast<const frag*>(bp + n * 16 * RB);
+        for (int n = 0; n < NF; ++n) read_bn(k_c, n, dst[n]);
       };
       read_b(std::integral_constant<int, 0>{}, bf[0]);
       auto step = [&](auto k_c) {
         constexpr int k = decltype(k_c)::value;
-        if constexpr (k + 1 < NK1) { if (!QVC_ABL(6)) read_b(std::integral_constant<int, k + 1>{}, bf[(k + 1) & 1]); }
+        if constexpr (!ROLL && k + 1 < NK1) { if (!QVC_ABL(6)) read_b(std::integral_constant<int, k + 1>{}, bf[(k + 1) & 1]); }
         if constexpr (k == NK1 - 6) { bt = *reinterpret_cast<const float4*>(bb); bs = *reinterpret_cast<const float4*>(bb + a.H); }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int n = 0; n < NF; ++n)
+        for (int n = 0; n < NF; ++n) {
 #pragma unroll
-          for (int m = 0; m < 2; ++m) acc[m][n] = O::mfma(ring[k % RING][m], bf[k & 1][n], acc[m][n]);
+          for (int m = 0; m < 2; ++m) acc[m][n] = O::mfma(ring[k % RING][m], bf[(k & 1) % NBUF][n], acc[m][n]);
+          if constexpr (ROLL && k + 1 < NK1) { if (!QVC_ABL(6)) read_bn(std::integral_constant<int, k + 1>{}, n, bf[0][n]); }
+        }
         __builtin_amdgcn_sched_barrier(0);
         if (!QVC_ABL(5)) prefetch(std::integral_constant<int, k + PF>{});      // into the slot these MFMAs have just read
         if constexpr (QVC_WN2_SYNC > 0 && (k + 1) % (QVC_WN2_SYNC > 0 ? QVC_WN2_SYNC : 1) == 0 && k + 1 < NK1) __builtin_amdgcn_s_barrier();
@@ -235,9 +267,7 @@ __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArg
 #ifdef QVC_STAMP
       if (l < 4) QVC_ST(2 + 6 * l);
 #endif
-#pragma unroll
-      for (int n = 0; n < NF; ++n) {
-        const int j = n * 16 + lrow;
+      auto gate = [&](int n) {
         const f32x4 t = acc[0][n], sg = acc[1][n];
         quad o;
         if (ch0 < a.H) {
@@ -248,7 +278,22 @@ __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArg
         } else {
           o[0] = o[1] = o[2] = o[3] = (T)0.f;
         }
+        return o;
+      };
+      auto put_acts = [&](int n, const quad& o) {
+        const int j = n * 16 + lrow;
         *reinterpret_cast<quad*>(acts + j * RB + ((rotc(ch0 >> 3, sm) ^ swz(j, sm)) << 4) + (ch0 & 7) * 2) = o;
+      };
+      if constexpr (!ALIAS) {
+#pragma unroll
+        for (int n = 0; n < NF; ++n) put_acts(n, gate(n));
+      } else {
+        quad o[NF];
+#pragma unroll
+        for (int n = 0; n < NF; ++n) o[n] = gate(n);
+        __syncthreads();                      // every wave is done reading the x tile
+#pragma unroll
+        for (int n = 0; n < NF; ++n) put_acts(n, o[n]);
       }
     }
     // res / skip biases: requested before the barrier, used after GEMM2
@@ -260,7 +305,7 @@ __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArg
 #ifdef QVC_STAMP
     if (l < 4) QVC_ST(3 + 6 * l);
 #endif
-    __syncthreads();                          // acts complete; every wave is done reading the x tile
+    __syncthreads();                          // acts complete; every wave is done reading the x tile (NF = 3)
 #ifdef QVC_STAMP
     if (l < 4) QVC_ST(4 + 6 * l);
 #endif
@@ -270,26 +315,37 @@ __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArg
       for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int n = 0; n < NF; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-      frag bf[2][NF];
-      auto read_b = [&](auto k_c, frag (&dst)[NF]) {
+      frag bf[NBUF][NF];
+      auto read_bn = [&](auto k_c, int n, frag& dst) {
         constexpr int ks = decltype(k_c)::value;
         const char* bp = smem + ((ks & 1) ? (boff[0] ^ 64) : boff[0]) + (ACTS + (ks >> 1) * 128);
+        dst = *reinterpret_cast<const frag*>(bp + n * 16 * RB);
+      };
+      auto read_b = [&](auto k_c, frag (&dst)[NF]) {
 #pragma unroll
-        for (int n = 0; n < NF; ++n) dst[n] = *reinterpret_cast<const frag*>(bp + n * 16 * RB);
+        for (int n = 0; n < NF; ++n) read_bn(k_c, n, dst[n]);
       };
       read_b(std::integral_constant<int, 0>{}, bf[0]);
       auto step = [&](auto k_c) {
         constexpr int k = decltype(k_c)::value;       // k-step of GEMM2; stream position NK1 + k
-        if constexpr (k + 1 < NK2) { if (!QVC_ABL(6)) read_b(std::integral_constant<int, k + 1>{}, bf[(k + 1) & 1]); }
+        if constexpr (!ROLL && k + 1 < NK2) { if (!QVC_ABL(6)) read_b(std::integral_constant<int, k + 1>{}, bf[(k + 1) & 1]); }
         __builtin_amdgcn_sched_barrier(0);
+        auto next = [&](int n) {
+          if constexpr (ROLL && k + 1 < NK2) { if (!QVC_ABL(6)) read_bn(std::integral_constant<int, k + 1>{}, n, bf[0][n]); }
+        };
         if (!last) {
 #pragma unroll
-          for (int n = 0; n < NF; ++n)
+          for (int n = 0; n < NF; ++n) {
 #pragma unroll
-            for (int m = 0; m < 2; ++m) acc[m][n] = O::mfma(ring[(NK1 + k) % RING][m], bf[k & 1][n], acc[m][n]);
+            for (int m = 0; m < 2; ++m) acc[m][n] = O::mfma(ring[(NK1 + k) % RING][m], bf[(k & 1) % NBUF][n], acc[m][n]);
+            next(n);
+          }
         } else {
 #pragma unroll
-          for (int n = 0; n < NF; ++n) acc[0][n] = O::mfma(ring[(NK1 + k) % RING][0], bf[k & 1][n], acc[0][n]);
+          for (int n = 0; n < NF; ++n) {
+            acc[0][n] = O::mfma(ring[(NK1 + k) % RING][0], bf[(k & 1) % NBUF][n], acc[0][n]);
+            next(n);
+          }
         }
         __builtin_amdgcn_sched_barrier(0);
         if (!QVC_ABL(5)) prefetch(std::integral_constant<int, NK1 + k + PF>{});
@@ -315,7 +371,7 @@ __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArg
             xres[n * NTH] = make_float4(xn[n][0], xn[n][1], xn[n][2], xn[n][3]);
             oacc[n * NTH] = oo;
           }
-          put_x(xn);                          // safe: all waves are past GEMM1 of this layer
+          if constexpr (!ALIAS) put_x(xn);    // safe: all waves are past GEMM1 of this layer
         } else {
 #pragma unroll
           for (int n = 0; n < NF; ++n) {
@@ -323,6 +379,15 @@ __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArg
             oo.x += acc[0][n][0] + b0.x; oo.y += acc[0][n][1] + b0.y; oo.z += acc[0][n][2] + b0.z; oo.w += acc[0][n][3] + b0.w;
             oacc[n * NTH] = oo;
           }
+        }
+      }
+      if constexpr (ALIAS) {
+        if (!last) {
+          __syncthreads();                    // every wave is done reading the gated tile = the x tile
+          f32x4 xn[NF];                       // back from the lane's own slots: not held in registers across the barrier
+#pragma unroll
+          for (int n = 0; n < NF; ++n) { const float4 v = xres[n * NTH]; xn[n] = f32x4{v.x, v.y, v.z, v.w}; }
+          put_x(xn);
         }
       }
     }
@@ -336,12 +401,16 @@ __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArg
 #endif
   }
 
+  // the epilogue's per-column values from an opaque copy of the lane's row: the wide tile otherwise carries the
+  // prologue's identical expressions across the layer loop, in scratch memory
+  int lrow_e = lrow;
+  if constexpr (ALIAS) asm volatile("" : "+v"(lrow_e));
   if constexpr (PM > 0) {
     if (a.w_post) {
       // fused `post` 1x1 + coupling update (modules.py:214-217)
 #pragma unroll
       for (int n = 0; n < ON; ++n) {
-        const int j = n * 16 + lrow;
+        const int j = n * 16 + lrow_e;
         quad h;
         if (ch0 < a.H) {
           const float4 oo = oacc[n * NTH];
@@ -358,7 +427,7 @@ __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArg
 #pragma unroll
         for (int n = 0; n < ON; ++n) qacc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
       const frag* apq = static_cast<const frag*>(a.w_post) + ((size_t)wm * KS * PM) * 64 + lane;
-      gemm_loop<T, PM, ON, QVC_PF_STACK>(qacc, apq, KS, KS, 1, acts, RB, sm, lrow, lq, 0);
+      gemm_loop<T, PM, ON, QVC_PF_STACK>(qacc, apq, KS, KS, 1, acts, RB, sm, lrow_e, lq, 0);
 #pragma unroll
       for (int m = 0; m < PM; ++m) {
         const int v = (wm * PM + m) * 16 + lq * 4;
@@ -367,14 +436,14 @@ __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArg
         float4 zin[ON];                      // all loads of the read-modify-write before its first store
 #pragma unroll
         for (int n = 0; n < ON; ++n) {
-          const int q = w0 + n * 16 + lrow;
+          const int q = w0 + n * 16 + lrow_e;
           zin[n] = make_float4(0.f, 0.f, 0.f, 0.f);
           if (q >= q0 && q < q0 + OUTF && q < Tb)
             zin[n] = *reinterpret_cast<const float4*>(a.z + (size_t)b * a.z_bs + (size_t)q * a.z_ts + a.post_c0 + v);
         }
 #pragma unroll
         for (int n = 0; n < ON; ++n) {
-          const int q = w0 + n * 16 + lrow;
+          const int q = w0 + n * 16 + lrow_e;
           if (q >= q0 && q < q0 + OUTF && q < Tb) {
             float* p = a.z + (size_t)b * a.z_bs + (size_t)q * a.z_ts + a.post_c0 + v;
             float4 zz = zin[n];
@@ -391,7 +460,7 @@ __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArg
   if (ch0 < a.H) {
 #pragma unroll
     for (int n = 0; n < ON; ++n) {
-      const int q = w0 + n * 16 + lrow;
+      const int q = w0 + n * 16 + lrow_e;
       if (q >= q0 && q < q0 + OUTF && q < Tb) {
         const size_t off = (size_t)b * a.bs + (size_t)q * a.H + ch0;
         *reinterpret_cast<float4*>(a.out + off) = oacc[n * NTH];
@@ -405,25 +474,32 @@ __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArg
 #endif
 }
 
-template <typename T>
-int launch_wn_stack2_typed(const ConvDesc& din, const WnStackArgs& a, int batch, void* stream_v) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_v);
-  if (!wn2_supported(din, a)) return QVC_ERR_BAD_CONFIG;
+template <typename T, int NF, int RING>
+int launch_wn_stack2_nf(const WnStackArgs& a, int batch, hipStream_t stream) {
   constexpr int KS = 6, TAPS = 5;
-  const size_t lds = (size_t)(48 + TAPS - 1 + 48) * KS * 64 + (size_t)2 * 3 * (KS * 2 * 64) * 16;   // tiles + fp32 residual / skip slots
-  const dim3 grid((unsigned)ceil_div(a.T, kWnOutFrames), (unsigned)batch), block(KS * 2 * 64);
+  constexpr size_t lds = wn2_lds_bytes<KS, TAPS, NF>();
+  static_assert(lds <= 160 * 1024, "one workgroup per CU");
+  const dim3 grid((unsigned)ceil_div(a.T, NF * 16 - 16), (unsigned)batch), block(KS * 2 * 64);
   if (a.w_post) {
-    auto kern = wn_stack2_kernel<T, KS, TAPS, 1>;
+    auto kern = wn_stack2_kernel<T, KS, TAPS, 1, NF, RING>;
     static std::atomic<uint32_t> lds_ok{0};                  // > 64 KiB dynamic LDS: opt in once per device
     if (!allow_big_lds(lds_ok, reinterpret_cast<const void*>(kern))) return QVC_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, grid, block, lds, stream, a);
   } else {
-    auto kern = wn_stack2_kernel<T, KS, TAPS, 0>;
+    auto kern = wn_stack2_kernel<T, KS, TAPS, 0, NF, RING>;
     static std::atomic<uint32_t> lds_ok{0};
     if (!allow_big_lds(lds_ok, reinterpret_cast<const void*>(kern))) return QVC_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, grid, block, lds, stream, a);
   }
   return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
+}
+
+// wide: the 64-frame tile (NF = 5), else the 32-frame one
+template <typename T>
+int launch_wn_stack2_typed(const ConvDesc& din, const WnStackArgs& a, int batch, void* stream_v, bool wide) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  if (!wn2_supported(din, a)) return QVC_ERR_BAD_CONFIG;
+  return wide ? launch_wn_stack2_nf<T, 5, QVC_WN2_WIDE_RING>(a, batch, stream) : launch_wn_stack2_nf<T, 3, 6>(a, batch, stream);
 }
 
 }  // namespace qvc
