@@ -120,7 +120,10 @@ int qvc_device_check(void);
 /* Developer / test switches (launch-shape and kernel-selection variants that must give identical results; the GPU
  * tests flip them in-process).  The library never reads environment variables: a switch changes only through this
  * call.  Names: "post_tail", "post_tail_nf", "pair_wide_launch", "pair_cm4", "conv_cl", "wn_chunk", "pair_chain3",
- * "wn_kernel".  Unknown name: QVC_ERR_BAD_ARG.  No reference counterpart. */
+ * "wn_kernel", "launch_stop" (-1 = off; n >= 0: the whole-path entry points -- qvc_infer_batch[_ex|_timed|_ragged[_fm]],
+ * qvc_enc_q, qvc_flow_forward -- issue only their first n launches).  qvc_debug_get also reads "launch_steps" (read-only:
+ * the launches the last such call would have issued without a stop).  Unknown name: QVC_ERR_BAD_ARG.  No reference
+ * counterpart. */
 int qvc_debug_set(const char* name, int32_t value);
 int qvc_debug_get(const char* name, int32_t* value);
 /* fp32 -> f16 conversions that SATURATED (|x| > 65504) since the last reset, summed over all kernels.  Counted only

@@ -10,6 +10,7 @@
 // the MI355X is each kernel against this emulation's per-launch semantics.
 // The product library never links or calls this file.
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <vector>
 #include "../quickvc-official_amd/csrc/qvc_path.h"
@@ -258,8 +259,15 @@ struct EmuBackend {
     }
     return QVC_OK;
   }
+  // The decisions HipBackend takes from the library's debug switches (csrc/qvc_api.hip), at the library's defaults
+  // unless a windowed entry point sets them: both backends then issue the same step sequence.
+  int32_t pair_chain3 = 0, post_tail_sw = 1, wn_chunk = 0;
   bool use_wn_stack(int, int) const { return true; }
-  int wn_stack_chunk(int layers) const { return layers % 4 == 0 ? 4 : layers; }
+  int wn_stack_chunk(int layers) const {
+    if (wn_chunk < 0) return 0;
+    if (wn_chunk > 0) return wn_chunk <= layers ? wn_chunk : layers;
+    return layers % 4 == 0 ? 4 : layers;
+  }
   // whole stack = the layers one after the other (x ping-pong in temporaries)
   int wn_stack(const ConvDesc& din, const ConvDesc& drs, const ConvDesc& drs_last, const WnStackArgs& s, int B, int dtype,
                const ConvDesc* dpre, const ConvDesc* dpost) {
@@ -345,7 +353,7 @@ struct EmuBackend {
     return QVC_OK;
   }
   // a whole ResBlock in one launch (qvc_chain_impl.h): replayed pair by pair through the buffers the arguments name
-  bool chain_ok(const ConvDesc* d1, const ConvDesc* d2, int n) const { return chain_supported(d1, d2, n); }
+  bool chain_ok(const ConvDesc* d1, const ConvDesc* d2, int n) const { return pair_chain3 != 0 && chain_supported(d1, d2, n); }
   int chain(const ConvDesc* d1, const ConvDesc* d2, const ChainArgs& a, int B, int dtype) {
     for (int q = 0; q < a.n; ++q) pair(d1[q], d2[q], a.p[q], B, dtype, a.rg);
     return QVC_OK;
@@ -369,7 +377,7 @@ struct EmuBackend {
     return QVC_OK;
   }
   // conv_post + tail as one backend op (qvc_post_tail_impl.h): the same two steps through a host buffer
-  bool post_tail_ok(const ConvDesc&) const { return true; }
+  bool post_tail_ok(const ConvDesc& d) const { return post_tail_sw != 0 && post_tail_supported(d); }
   int post_tail(const ConvDesc& d, const PostTailArgs& a, int batch, int dtype) {
     std::vector<float> post((size_t)batch * a.F * 72, 0.f);
     ConvArgs c = a.c;
@@ -520,7 +528,15 @@ struct Run {
     if (ws_bytes < W.bytes) return QVC_ERR_SMALL_BUFFER;
     return QVC_OK;
   }
+  // sw: {pair_chain3, post_tail, wn_chunk} as the library's debug switches (null = their defaults)
+  void switches(const int32_t* sw) {
+    if (!sw) return;
+    be.pair_chain3 = sw[0]; be.post_tail_sw = sw[1]; be.wn_chunk = sw[2];
+  }
 };
+template <class B> void window(Path<B>& c, int32_t lo, int32_t hi, int32_t* kinds, int32_t max_kinds) {
+  c.step_lo = lo; c.step_hi = hi; c.step_kinds = kinds; c.max_step_kinds = max_kinds;
+}
 }  // namespace
 
 extern "C" {
@@ -602,6 +618,108 @@ int qvc_emu_speaker_embed(const qvc_config* cfg, const void* spk_blob, const flo
   EmuBackend be;
   return spk_path(S, dec_dtype(*cfg), static_cast<const char*>(spk_blob), static_cast<char*>(workspace), W, mel, g,
                   utterances, mel_frames, be);
+}
+
+// ---- windowed twins (the GPU step test): the same paths, issuing only steps [lo, hi) (Path::step) from whatever the
+// workspace and output buffers hold.  sw = {pair_chain3, post_tail, wn_chunk} as the library's debug switches (null:
+// their defaults); kinds (optional) receives the StepKind of every step.  Returns the step count of the whole path, or
+// a negative status.
+int qvc_emu_infer_window(const qvc_config* cfg, const void* blob, const float* unit, const float* g, const float* noise, float* out,
+                         int32_t batch, int32_t frames, const int32_t* lens, void* workspace, int64_t workspace_bytes,
+                         const int32_t* sw, int32_t lo, int32_t hi, int32_t* kinds, int32_t max_kinds) {
+  Run r;
+  int st = r.prepare(cfg, batch, frames, workspace_bytes);
+  if (st != QVC_OK) return st;
+  r.switches(sw);
+  Path<EmuBackend> c{r.P, static_cast<const char*>(blob), static_cast<char*>(workspace), r.W, batch, frames, r.be};
+  c.lens = lens;
+  window(c, lo, hi, kinds, max_kinds);
+  c.cond_table(g);
+  c.enc_p(unit, noise, c.wsp<float>(r.W.z));
+  c.flow(c.wsp<float>(r.W.z));
+  c.dec_trunk_wave(c.wsp<float>(r.W.z), c.wsp<float>(r.W.post), out);
+  return c.status != QVC_OK ? c.status : c.step_n;
+}
+
+int qvc_emu_enc_q_window(const qvc_config* cfg, const void* encq_blob, const float* spec, const float* g, const float* noise,
+                         float* z_fm, int32_t batch, int32_t frames, void* workspace, int64_t workspace_bytes,
+                         const int32_t* sw, int32_t lo, int32_t hi, int32_t* kinds, int32_t max_kinds) {
+  Run r;
+  int st = r.prepare(cfg, batch, frames, workspace_bytes);
+  if (st != QVC_OK) return st;
+  const EncQPlan Q = build_encq_plan(*cfg);
+  if (Q.status != QVC_OK) return Q.status;
+  r.switches(sw);
+  Path<EmuBackend> c{r.P, static_cast<const char*>(encq_blob), static_cast<char*>(workspace), r.W, batch, frames, r.be};
+  window(c, lo, hi, kinds, max_kinds);
+  c.enc_q(Q, static_cast<const char*>(encq_blob), spec, g, noise, z_fm);
+  return c.status != QVC_OK ? c.status : c.step_n;
+}
+
+int qvc_emu_flow_forward_window(const qvc_config* cfg, const void* blob, float* z_fm, const float* g, int32_t batch, int32_t frames,
+                                void* workspace, int64_t workspace_bytes, const int32_t* sw, int32_t lo, int32_t hi, int32_t* kinds,
+                                int32_t max_kinds) {
+  Run r;
+  int st = r.prepare(cfg, batch, frames, workspace_bytes);
+  if (st != QVC_OK) return st;
+  r.switches(sw);
+  Path<EmuBackend> c{r.P, static_cast<const char*>(blob), static_cast<char*>(workspace), r.W, batch, frames, r.be};
+  window(c, lo, hi, kinds, max_kinds);
+  c.cond_table(g);
+  c.flow(z_fm, /*forward=*/true);
+  return c.status != QVC_OK ? c.status : c.step_n;
+}
+
+// Every buffer of the Workspace (carve_workspace) for (cfg, batch, frames): what the step test compares.
+//   elem: 0 = fp32, 1 = f16, 2 = bf16 (the 2-byte type the buffer holds in this operand mode);
+//   layout [groups][batch][rows][channels] (groups > 1: the unfused conv1 outputs of a stage, one block per ResBlock);
+//   valid rows of a ragged member b: min(rows, lens[b] * mul + add) (mul = 0: every row, not indexed by frame).
+struct qvc_emu_buffer {
+  char name[24];
+  int64_t offset, bytes;
+  int32_t elem, groups, rows, channels, mul, add;
+};
+
+int qvc_emu_workspace_map(const qvc_config* cfg, int32_t batch, int32_t frames, qvc_emu_buffer* out, int32_t max_out) {
+  if (!cfg || batch <= 0 || frames <= 1 || (!out && max_out > 0)) return QVC_ERR_BAD_ARG;
+  const Plan P = build_plan(*cfg);
+  if (P.status != QVC_OK) return P.status;
+  const Workspace W = carve_workspace(P, batch, frames);
+  const qvc_config& c = P.cfg;
+  const int op = dec_dtype(c) == QVC_F16 ? 1 : 2;   // every 2-byte buffer holds the generator's stream type (bf16x: f16, pairs included)
+  int n = 0;
+  auto add = [&](const char* name, int64_t off, int elem, int groups, int rows, int ch, int mul, int add_) {
+    if (n < max_out) {
+      qvc_emu_buffer& e = out[n];
+      std::snprintf(e.name, sizeof(e.name), "%s", name);
+      e.offset = off; e.elem = elem; e.groups = groups; e.rows = rows; e.channels = ch; e.mul = mul; e.add = add_;
+      e.bytes = (int64_t)groups * batch * rows * ch * (elem == 0 ? 4 : 2);
+    }
+    ++n;
+  };
+  const int H = c.hidden_channels, C = c.inter_channels;
+  add("bb", W.bb, 0, 1, 1, (int)std::max<int64_t>(P.cond_rows, (int64_t)c.enc_layers * 2 * H), 0, 0);
+  add("xw", W.xw, 0, 1, frames, H, 1, 0);
+  add("xw2", W.xw2, 0, 1, frames, H, 1, 0);
+  add("oacc", W.oacc, 0, 1, frames, H, 1, 0);
+  add("acts", W.acts, op, 1, frames, H, 1, 0);
+  add("stats", W.stats, 0, 1, frames, 2 * C, 1, 0);
+  add("z", W.z, 0, 1, frames, C, 1, 0);
+  add("c0", W.c0, op, 1, frames, c.upsample_initial_channel, 1, 0);
+  int t = frames, rate = 1;
+  char name[24];
+  for (size_t i = 0; i < P.stages.size(); ++i) {
+    t *= P.stages[i].rate; rate *= P.stages[i].rate;
+    const int ch = P.stages[i].ch;
+    std::snprintf(name, sizeof(name), "u%d", (int)i); add(name, W.u[i], op, 1, t, ch, rate, 0);
+    for (int j = 0; j < c.n_resblocks; ++j) {
+      std::snprintf(name, sizeof(name), "ra%d.%d", (int)i, j); add(name, W.ra[i][(size_t)j], op, 1, t, ch, rate, 0);
+      std::snprintf(name, sizeof(name), "rb%d.%d", (int)i, j); add(name, W.rb[i][(size_t)j], op, 1, t, ch, rate, 0);
+    }
+    std::snprintf(name, sizeof(name), "xt%d", (int)i); add(name, W.xt[i], op, c.n_resblocks, t, ch, rate, 0);
+  }
+  add("post", W.post, 0, 1, t + 1, P.post_channels, rate, 1);
+  return n;
 }
 
 // Stage taps for debugging: copies frame-major fp32 buffers out of the workspace after a run.

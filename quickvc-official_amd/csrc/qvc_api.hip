@@ -99,6 +99,13 @@ struct HipBackend {
 };
 using Ctx = Path<HipBackend>;
 
+// launch_stop / launch_steps: the step window of the whole-path entry points.  Host-side bookkeeping only.
+template <class Backend> void window_from_switch(Path<Backend>& c) {
+  const int stop = debug_get(DBG_LAUNCH_STOP);
+  if (stop >= 0) c.step_hi = stop;
+}
+template <class Backend> void record_steps(const Path<Backend>& c) { debug_launch_steps().store(c.step_n, std::memory_order_relaxed); }
+
 // Same launches, each bracketed by events on the stream (diagnostics only).
 struct TimedBackend {
   void fork(int) {} void branch(int) {} void branch_done(int) {} void wait_branch_done(int) {} void join(int) {}
@@ -267,10 +274,12 @@ int infer_ragged(const qvc_config* cfg, const void* blob_dev, const float* unit,
   Ctx c{P, static_cast<const char*>(blob_dev), static_cast<char*>(workspace), W, batch, max_frames, be};
   c.lens = frames_dev;
   c.unit_fm = unit_fm;
+  window_from_switch(c);
   c.cond_table(g);
   c.enc_p(unit, noise, c.wsp<float>(W.z));
   c.flow(c.wsp<float>(W.z));
   c.dec_trunk_wave(c.wsp<float>(W.z), c.wsp<float>(W.post), out);
+  record_steps(c);
   return c.status != QVC_OK ? c.status : (be.br.ok ? QVC_OK : QVC_ERR_LAUNCH);
 }
 
@@ -305,6 +314,7 @@ int qvc_debug_get(const char* name, int32_t* value) {
   if (!name || !value) return QVC_ERR_BAD_ARG;
   for (int i = 0; i < DBG_COUNT; ++i)
     if (std::strcmp(name, debug_names()[i]) == 0) { *value = debug_get(i); return QVC_OK; }
+  if (std::strcmp(name, "launch_steps") == 0) { *value = debug_launch_steps().load(std::memory_order_relaxed); return QVC_OK; }
   return QVC_ERR_BAD_ARG;
 }
 
@@ -397,10 +407,12 @@ int qvc_infer_batch_ex(const qvc_config* cfg, const void* blob_dev, const float*
   if (st != QVC_OK) return st;
   HipBackend be; be.stream = be.stream0 = static_cast<hipStream_t>(stream); be.br.aux = aux;
   Ctx c{P, static_cast<const char*>(blob_dev), static_cast<char*>(workspace), W, batch, frames, be};
+  window_from_switch(c);
   c.cond_table(g);
   c.enc_p(unit, noise, c.wsp<float>(W.z));
   c.flow(c.wsp<float>(W.z));
   c.dec_trunk_wave(c.wsp<float>(W.z), c.wsp<float>(W.post), out);
+  record_steps(c);
   return c.status != QVC_OK ? c.status : (be.br.ok ? QVC_OK : QVC_ERR_LAUNCH);
 }
 
@@ -498,10 +510,12 @@ int qvc_infer_batch_timed(const qvc_config* cfg, const void* blob_dev, const flo
   if (st != QVC_OK) return st;
   TimedBackend be{static_cast<hipStream_t>(stream), records, max_records};
   Path<TimedBackend> c{P, static_cast<const char*>(blob_dev), static_cast<char*>(workspace), W, batch, frames, be};
+  window_from_switch(c);
   c.cond_table(g);
   c.enc_p(unit, noise, c.wsp<float>(W.z));
   c.flow(c.wsp<float>(W.z));
   c.dec_trunk_wave(c.wsp<float>(W.z), c.wsp<float>(W.post), out);
+  record_steps(c);
   const int fin = be.finish();
   *n_records = be.n;
   return c.status != QVC_OK ? c.status : fin;
@@ -565,8 +579,10 @@ int qvc_flow_forward(const qvc_config* cfg, const void* blob_dev, float* z_fm, c
   if (st != QVC_OK) return st;
   HipBackend be; be.stream = be.stream0 = static_cast<hipStream_t>(stream);
   Ctx c{P, static_cast<const char*>(blob_dev), static_cast<char*>(workspace), W, batch, frames, be};
+  window_from_switch(c);
   c.cond_table(g);
   c.flow(z_fm, /*forward=*/true);
+  record_steps(c);
   return c.status;
 }
 
@@ -580,7 +596,9 @@ int qvc_enc_q(const qvc_config* cfg, const void* encq_blob_dev, const float* spe
   if (Q.status != QVC_OK) return Q.status;
   HipBackend be; be.stream = be.stream0 = static_cast<hipStream_t>(stream);
   Ctx c{P, static_cast<const char*>(encq_blob_dev), static_cast<char*>(workspace), W, batch, frames, be};
+  window_from_switch(c);
   c.enc_q(Q, static_cast<const char*>(encq_blob_dev), spec, g, noise, z_fm);
+  record_steps(c);
   return c.status;
 }
 

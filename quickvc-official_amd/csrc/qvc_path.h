@@ -19,6 +19,7 @@
 //                      void wait_branch_done(int j); void join(int n);   (stream fork/join; no-ops on one stream)
 #pragma once
 #include <algorithm>
+#include <climits>
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
@@ -34,6 +35,12 @@ struct has_single_band_tail<B, std::void_t<decltype(std::declval<B&>().tail1(std
                                            decltype(std::declval<B&>().post_tail1(std::declval<const ConvDesc&>(),
                                                                                   std::declval<const PostTailArgs&>(), 0, 0))>>
     : std::true_type {};
+
+// Kinds of the steps a Path issues (one per backend call that enqueues device work), in the order they are counted.
+enum StepKind : int32_t {
+  STEP_CONV = 0, STEP_ZERO, STEP_GEMV, STEP_SAMPLE, STEP_WN, STEP_WN_STACK, STEP_CHAIN, STEP_PAIR3, STEP_POST_TAIL,
+  STEP_POST_TAIL1, STEP_TAIL, STEP_TAIL1, STEP_KINDS
+};
 
 template <class Backend>
 struct Path {
@@ -58,6 +65,17 @@ struct Path {
   // the WaveNet stacks may run in the continuous-stream kernel's 64-frame tile (launch_wn_stack picks it where the grid
   // is large); the streaming windows keep the 32-frame tile, not measured there
   bool wn_wide = true;
+  // Step window (tests): every backend call that enqueues device work is one step, numbered from 0 in issue order.
+  // Steps outside [step_lo, step_hi) are counted but not issued; nothing else the path does changes.  The whole-path
+  // state lives in the workspace and the output buffers, so a run can be stopped after any step and resumed from a
+  // copy of those buffers (the GPU test replays each launch on the host emulation from such a snapshot).
+  int step_n = 0, step_lo = 0, step_hi = INT_MAX;
+  int32_t* step_kinds = nullptr; int max_step_kinds = 0;   // optional: the kind of every counted step
+  bool step(StepKind k) {
+    const int s = step_n++;
+    if (step_kinds && s < max_step_kinds) step_kinds[s] = k;
+    return s >= step_lo && s < step_hi;
+  }
 
   template <typename U> U* wsp(int64_t off) const { return reinterpret_cast<U*>(ws + off); }
   int dtype_wn() const { return wn_dtype(P.cfg); }     // enc_p / enc_q / flow
@@ -78,11 +96,11 @@ struct Path {
     if (status != QVC_OK) return;
     const ConvDesc g = generic_layout(d);
     ConvArgs ga = a; ga.nchunk = g.nchunk;
-    status = be.conv(g, ga, B, epi, dt);
+    if (step(STEP_CONV)) status = be.conv(g, ga, B, epi, dt);
   }
   void zero(int64_t off, int64_t bytes) {
     if (status != QVC_OK) return;
-    status = be.zero(ws + off, (size_t)bytes);
+    if (step(STEP_ZERO)) status = be.zero(ws + off, (size_t)bytes);
   }
 
   // ---- conditioning table: bb[b][row] for every cond row (flow WN layers + dec.cond)
@@ -90,7 +108,7 @@ struct Path {
     if (status != QVC_OK) return;
     GemvArgs ga{reinterpret_cast<const float*>(blob + P.cond_w_off), reinterpret_cast<const float*>(blob + P.cond_b_off),
                 g, wsp<float>(W.bb), P.cond_rows, P.cfg.gin_channels, B};
-    status = be.gemv(ga);
+    if (step(STEP_GEMV)) status = be.gemv(ga);
   }
 
   // ---- WN stack over xw (in place) accumulating into oacc (modules.py:69-114)
@@ -118,7 +136,7 @@ struct Path {
         a.accum = l0 > 0 ? 1 : 0;
         a.rg = rg(1); a.wide = wn_wide ? 1 : 0;
         a.x_out = a.final_layer ? nullptr : wsp<float>(part % 2 == 0 ? W.xw2 : W.xw);
-        if (status == QVC_OK) status = be.wn_stack(wn.in_conv[0], wn.rs_conv[0], wn.rs_conv[wn.layers - 1], a, B, dtype_wn(), nullptr, nullptr);
+        if (status == QVC_OK && step(STEP_WN_STACK)) status = be.wn_stack(wn.in_conv[0], wn.rs_conv[0], wn.rs_conv[wn.layers - 1], a, B, dtype_wn(), nullptr, nullptr);
       }
       return;
     }
@@ -136,7 +154,7 @@ struct Path {
       a.bbias = bb + (int64_t)l * 2 * H; a.bbias_bs = bb_bs;
       a.taps = din.taps; a.KS = din.KS(); a.nIt1 = din.nIt(); a.last = l == wn.layers - 1 ? 1 : 0;
       a.rg = rg(1);
-      if (status == QVC_OK) status = be.wn(din, drs, a, B, dtype_wn());
+      if (status == QVC_OK && step(STEP_WN)) status = be.wn(din, drs, a, B, dtype_wn());
     }
   }
 
@@ -163,7 +181,7 @@ struct Path {
     }
     if (status != QVC_OK) return;
     SampleArgs sa{wsp<float>(W.stats), noise, z_out, B, T, C};
-    status = be.sample(sa);
+    if (step(STEP_SAMPLE)) status = be.sample(sa);
   }
   // proj packed with paired [mu | log sigma] rows (make_proj): z = mu + noise * exp(log sigma) in the conv epilogue
   bool proj_and_sample(const ConvDesc& d, ConvArgs& a, const float* noise, float* z_out) {
@@ -182,7 +200,7 @@ struct Path {
     if (status != QVC_OK) return;
     GemvArgs ga{reinterpret_cast<const float*>(qblob + Q.cond_w_off), reinterpret_cast<const float*>(qblob + Q.cond_b_off),
                 g, wsp<float>(W.bb), Q.cond_rows, c.gin_channels, B};
-    status = be.gemv(ga);
+    if (step(STEP_GEMV)) status = be.gemv(ga);
     {
       ConvArgs a = args(Q.pre, qblob);
       a.x = spec; a.x_kind = XK_F32_CM; a.x_bs = (int64_t)Q.spec_channels * T; a.x_ts = T; a.T_in = T;
@@ -201,7 +219,7 @@ struct Path {
     }
     if (status != QVC_OK) return;
     SampleArgs sa{wsp<float>(W.stats), noise, z_out, B, T, C};
-    status = be.sample(sa);
+    if (step(STEP_SAMPLE)) status = be.sample(sa);
   }
 
   // ---- flow (models.py:39-51, modules.py:199-224); z updated in place.  reverse (the conversion path): the plan's
@@ -235,7 +253,7 @@ struct Path {
         a.post_m = f.post.M; a.post_c0 = f.out_c0; a.post_mf = f.post.MF;
         a.z = z; a.z_bs = (int64_t)T * C; a.z_ts = C; a.post_sign = sign;
         a.rg = rg(1); a.wide = wn_wide ? 1 : 0;
-        if (status == QVC_OK)
+        if (status == QVC_OK && step(STEP_WN_STACK))
           status = be.wn_stack(din, f.wn.rs_conv[0], f.wn.rs_conv[f.wn.layers - 1], a, B, dtype_wn(), &f.pre, &f.post);
         return;
       }
@@ -369,7 +387,7 @@ struct Path {
             cur = dst;
           }
           src[(size_t)j] = cur;
-          if (status == QVC_OK) status = be.chain(d1s, d2s, ca, B, dtype_pair());
+          if (status == QVC_OK && step(STEP_CHAIN)) status = be.chain(d1s, d2s, ca, B, dtype_pair());
           chained[j] = true;
         }
       }
@@ -393,7 +411,7 @@ struct Path {
             d1s[s_] = st.c1[(size_t)j * 3 + q]; d2s[s_] = st.c2[(size_t)j * 3 + q];
             src[(size_t)j] = dst;
           }
-          if (status == QVC_OK) status = be.pair3(d1s, d2s, a3, B, dtype_pair());
+          if (status == QVC_OK && step(STEP_PAIR3)) status = be.pair3(d1s, d2s, a3, B, dtype_pair());
         }
       } else {
       be.fork(NB);                                   // branches wait for everything enqueued so far
@@ -407,7 +425,7 @@ struct Path {
           if (pair_supported(d1, d2) && d1.lp && d2.lp) {
             PairArgs3 a1; a1.n = 1; a1.rg = rg(rate);
             a1.p[0] = pair_args(j, q, dst);
-            if (status == QVC_OK) status = be.pair3(&d1, &d2, a1, B, dtype_pair());
+            if (status == QVC_OK && step(STEP_PAIR3)) status = be.pair3(&d1, &d2, a1, B, dtype_pair());
           } else {
             void* xt = wsp<char>(W.xt[i]) + (size_t)j * (size_t)B * (size_t)bs * 2;
             {   // lrelu -> dilated conv -> lrelu (stored already activated)
@@ -444,8 +462,8 @@ struct Path {
         PostTailArgs pt;
         pt.c = a; pt.fir = single_band() ? nullptr : reinterpret_cast<const float*>(blob + P.fir_off); pt.out = wave; pt.F = t_in + 1;
         pt.rg = rg(P.total_up, 1);
-        if (!single_band()) status = be.post_tail(P.conv_post, pt, B, dtype_dec());
-        else if constexpr (has_single_band_tail<Backend>::value) status = be.post_tail1(P.conv_post, pt, B, dtype_dec());
+        if (!single_band()) { if (step(STEP_POST_TAIL)) status = be.post_tail(P.conv_post, pt, B, dtype_dec()); }
+        else if constexpr (has_single_band_tail<Backend>::value) { if (step(STEP_POST_TAIL1)) status = be.post_tail1(P.conv_post, pt, B, dtype_dec()); }
         return;
       }
       a.y32 = post_out; a.y32_bs = (int64_t)(t_in + 1) * P.post_channels; a.y32_ts = P.post_channels;
@@ -458,9 +476,9 @@ struct Path {
     if (status != QVC_OK) return;
     TailArgs ta{post, reinterpret_cast<const float*>(blob + P.fir_off), out, y_mb, B, F};
     ta.rg = rg(P.total_up, 1);
-    if (!single_band()) { status = be.tail(ta); return; }
+    if (!single_band()) { if (step(STEP_TAIL)) status = be.tail(ta); return; }
     ta.fir = nullptr; ta.bands = 1;
-    if constexpr (has_single_band_tail<Backend>::value) status = be.tail1(ta);
+    if constexpr (has_single_band_tail<Backend>::value) { if (step(STEP_TAIL1)) status = be.tail1(ta); }
     else status = QVC_ERR_BAD_CONFIG;
   }
 };

@@ -41,7 +41,7 @@ def lib():
 
 
 DEBUG_DEFAULTS = {"post_tail": 1, "post_tail_nf": 4, "pair_wide_launch": 1, "pair_cm4": 1, "conv_cl": 1, "wn_chunk": 0,
-                  "pair_chain3": 0, "wn_kernel": 0}
+                  "pair_chain3": 0, "wn_kernel": 0, "launch_stop": -1}
 
 
 @pytest.fixture(autouse=True)
