@@ -67,7 +67,8 @@ struct EmuBackend {
   static int row_of(const ConvDesc& d, int chunk, int wave, int mf, int i) {
     return d.lp ? conv_row(d, chunk, wave, mf, i) : ((chunk * d.WM + wave) * d.MF + mf) * 16 + i;
   }
-  void fork(int) {} void branch(int) {} void branch_done(int) {} void wait_branch_done(int) {} void join(int) {}
+  // (no kSingleBandTail: frozen before the single-band decoder, so the path refuses that decoder here)
+  void fork(int) {} void branch(int) {} void branch_done(int) {} void join(int) {}
   // ---- conv: dense weights are recovered from the fragment stream with the kernel's index math
   int conv(const ConvDesc& d, const ConvArgs& a, int B, int epi, int dtype) {
     const int KS = d.KS(), nIt = d.nIt(), MP = d.MP();
@@ -262,7 +263,6 @@ struct EmuBackend {
   // The decisions HipBackend takes from the library's debug switches (csrc/qvc_api.hip), at the library's defaults
   // unless a windowed entry point sets them: both backends then issue the same step sequence.
   int32_t pair_chain3 = 0, post_tail_sw = 1, wn_chunk = 0;
-  bool use_wn_stack(int, int) const { return true; }
   int wn_stack_chunk(int layers) const {
     if (wn_chunk < 0) return 0;
     if (wn_chunk > 0) return wn_chunk <= layers ? wn_chunk : layers;
@@ -271,13 +271,10 @@ struct EmuBackend {
   // whole stack = the layers one after the other (x ping-pong in temporaries)
   int wn_stack(const ConvDesc& din, const ConvDesc& drs, const ConvDesc& drs_last, const WnStackArgs& s, int B, int dtype,
                const ConvDesc* dpre, const ConvDesc* dpost) {
-    auto fill = [](ConvArgs& a, const ConvDesc& d) {
-      a.Cin = d.Cin; a.CinP = d.CinP; a.taps = d.taps; a.dil = d.dil; a.left = d.left; a.KS = d.KS(); a.nIt = d.nIt();
-      a.nchunk = d.nchunk; a.M = d.M; a.up_s = d.up_s; a.up_p = d.up_p; a.Cout = d.Cout; };
     std::vector<float> xa((size_t)B * s.bs, 0.f), xb((size_t)B * s.bs, 0.f), outbuf;
     float* out = s.out;
     if (s.w_pre) {   // fused pre 1x1: x0 = W_pre * z[in slice] + b
-      ConvArgs a; fill(a, *dpre);
+      ConvArgs a; conv_geometry(a, *dpre);
       a.w = s.w_pre; a.bias = s.b_pre; a.x = s.z; a.x_kind = XK_F32_FM; a.x_bs = s.z_bs; a.x_ts = s.z_ts; a.x_c0 = s.pre_c0;
       a.T_in = s.T; a.Nq = s.T; a.T_out = s.T; a.y32 = xa.data(); a.y32_bs = s.bs; a.y32_ts = s.H; a.rg = s.rg;
       conv(*dpre, a, B, EPI_STD, dtype);
@@ -298,7 +295,7 @@ struct EmuBackend {
     }
     if (s.x_out) std::memcpy(s.x_out, (s.layers % 2 ? xb : xa).data(), (size_t)B * s.bs * 4);
     if (s.w_post) {  // fused post 1x1: z[out slice] -= W_post * out + b
-      ConvArgs a; fill(a, *dpost);
+      ConvArgs a; conv_geometry(a, *dpost);
       a.w = s.w_post; a.bias = s.b_post; a.x = out; a.x_kind = XK_F32_FM; a.x_bs = s.bs; a.x_ts = s.H;
       a.T_in = s.T; a.Nq = s.T; a.T_out = s.T; a.rg = s.rg;
       a.res = s.z; a.res_bs = s.z_bs; a.res_ts = s.z_ts; a.res_c0 = s.post_c0; a.res_sign = s.post_sign;
@@ -307,18 +304,15 @@ struct EmuBackend {
     }
     return QVC_OK;
   }
-  // fused pair = the two convs back to back with the intermediate rounded to the operand type
+  // fused pair (helper of pair3 / chain) = the two convs back to back with the intermediate rounded to the operand type
   int pair(const ConvDesc& d1, const ConvDesc& d2, const PairArgs& p, int B, int dtype, const Ragged& rg = Ragged()) {
     if (dtype == QVC_BF16X) return pair_mixed(d1, d2, p, B, rg);
     std::vector<uint16_t> xt((size_t)B * p.bs);
-    auto fill = [](ConvArgs& a, const ConvDesc& d) {
-      a.Cin = d.Cin; a.CinP = d.CinP; a.taps = d.taps; a.dil = d.dil; a.left = d.left; a.KS = d.KS(); a.nIt = d.nIt();
-      a.nchunk = d.nchunk; a.M = d.M; a.up_s = d.up_s; a.up_p = d.up_p; a.Cout = d.Cout; };
-    ConvArgs a1; fill(a1, d1);
+    ConvArgs a1; conv_geometry(a1, d1);
     a1.w = p.w1; a1.bias = p.b1; a1.x = p.x; a1.x_kind = XK_OP_FM; a1.x_bs = p.bs; a1.x_ts = p.C; a1.T_in = p.T; a1.slope_in = p.slope;
     a1.rg = rg; a1.Nq = p.T; a1.T_out = p.T; a1.y16 = xt.data(); a1.y16_bs = p.bs; a1.y16_ts = p.C; a1.slope_out = p.slope;
     conv(d1, a1, B, EPI_STD, dtype);
-    ConvArgs a2; fill(a2, d2);
+    ConvArgs a2; conv_geometry(a2, d2);
     a2.w = p.w2; a2.bias = p.b2; a2.x = xt.data(); a2.x_kind = XK_OP_FM; a2.x_bs = p.bs; a2.x_ts = p.C; a2.T_in = p.T;
     a2.rg = rg; a2.Nq = p.T; a2.T_out = p.T; a2.res16 = p.x; a2.res_bs = p.bs; a2.res_ts = p.C;
     a2.y16 = p.y; a2.y16_bs = p.bs; a2.y16_ts = p.C; a2.slope_out = 1.f;
@@ -332,14 +326,11 @@ struct EmuBackend {
     const uint16_t* xs = static_cast<const uint16_t*>(p.x);
     for (size_t i = 0; i < n; ++i) xf[i] = from_f16(xs[i]);
     std::vector<uint16_t> xt(n);
-    auto fill = [](ConvArgs& a, const ConvDesc& d) {
-      a.Cin = d.Cin; a.CinP = d.CinP; a.taps = d.taps; a.dil = d.dil; a.left = d.left; a.KS = d.KS(); a.nIt = d.nIt();
-      a.nchunk = d.nchunk; a.M = d.M; a.up_s = d.up_s; a.up_p = d.up_p; a.Cout = d.Cout; };
-    ConvArgs a1; fill(a1, d1);
+    ConvArgs a1; conv_geometry(a1, d1);
     a1.w = p.w1; a1.bias = p.b1; a1.x = xf.data(); a1.x_kind = XK_F32_FM; a1.x_bs = p.bs; a1.x_ts = p.C; a1.T_in = p.T; a1.slope_in = p.slope;
     a1.rg = rg; a1.Nq = p.T; a1.T_out = p.T; a1.y16 = xt.data(); a1.y16_bs = p.bs; a1.y16_ts = p.C; a1.slope_out = p.slope;
     conv(d1, a1, B, EPI_STD, QVC_BF16);
-    ConvArgs a2; fill(a2, d2);
+    ConvArgs a2; conv_geometry(a2, d2);
     a2.w = p.w2; a2.bias = p.b2; a2.x = xt.data(); a2.x_kind = XK_OP_FM; a2.x_bs = p.bs; a2.x_ts = p.C; a2.T_in = p.T;
     a2.rg = rg; a2.Nq = p.T; a2.T_out = p.T; a2.res = xf.data(); a2.res_bs = p.bs; a2.res_ts = p.C;
     a2.y32 = yf.data(); a2.y32_bs = p.bs; a2.y32_ts = p.C;
@@ -519,65 +510,67 @@ struct EmuBackend {
   }
 };
 
-struct Run {
-  Plan P; Workspace W; EmuBackend be;
-  int prepare(const qvc_config* cfg, int B, int T, int64_t ws_bytes) {
-    P = build_plan(*cfg);
-    if (P.status != QVC_OK) return P.status;
-    W = carve_workspace(P, B, T);
-    if (ws_bytes < W.bytes) return QVC_ERR_SMALL_BUFFER;
-    return QVC_OK;
-  }
-  // sw: {pair_chain3, post_tail, wn_chunk} as the library's debug switches (null = their defaults)
-  void switches(const int32_t* sw) {
-    if (!sw) return;
-    be.pair_chain3 = sw[0]; be.post_tail_sw = sw[1]; be.wn_chunk = sw[2];
-  }
+// sw = {pair_chain3, post_tail, wn_chunk} as the library's debug switches (null: their defaults); [lo, hi): the step
+// window (Path::step), kinds (optional) receives the StepKind of every step.  The plain entry points run the full window.
+struct Window {
+  const int32_t* sw = nullptr;
+  int32_t lo = 0, hi = INT_MAX;
+  int32_t* kinds = nullptr; int32_t max_kinds = 0;
 };
-template <class B> void window(Path<B>& c, int32_t lo, int32_t hi, int32_t* kinds, int32_t max_kinds) {
-  c.step_lo = lo; c.step_hi = hi; c.step_kinds = kinds; c.max_step_kinds = max_kinds;
+// Every whole-path entry point: plan, workspace check, switches and window; `body` issues the path.  Returns the step
+// count of the whole path, or a negative status.
+template <class Body>
+int run_path(const qvc_config* cfg, const void* blob, int B, int T, void* ws, int64_t ws_bytes, const Window& w, Body body) {
+  const Plan P = build_plan(*cfg);
+  if (P.status != QVC_OK) return P.status;
+  const Workspace W = carve_workspace(P, B, T);
+  if (ws_bytes < W.bytes) return QVC_ERR_SMALL_BUFFER;
+  EmuBackend be;
+  if (w.sw) { be.pair_chain3 = w.sw[0]; be.post_tail_sw = w.sw[1]; be.wn_chunk = w.sw[2]; }
+  Path<EmuBackend> c{P, static_cast<const char*>(blob), static_cast<char*>(ws), W, B, T, be};
+  c.step_lo = w.lo; c.step_hi = w.hi; c.step_kinds = w.kinds; c.max_step_kinds = w.max_kinds;
+  body(c);
+  return c.status != QVC_OK ? c.status : c.step_n;
+}
+// lens == nullptr: the plain batch
+int infer(const qvc_config* cfg, const void* blob, const float* unit, const float* g, const float* noise, float* out, int B, int T,
+          const int32_t* lens, void* ws, int64_t ws_bytes, const Window& w) {
+  return run_path(cfg, blob, B, T, ws, ws_bytes, w, [&](Path<EmuBackend>& c) { c.lens = lens; c.infer(unit, g, noise, out); });
+}
+int enc_q(const qvc_config* cfg, const void* encq_blob, const float* spec, const float* g, const float* noise, float* z_fm, int B, int T,
+          void* ws, int64_t ws_bytes, const Window& w) {
+  return run_path(cfg, encq_blob, B, T, ws, ws_bytes, w, [&](Path<EmuBackend>& c) {
+    const EncQPlan Q = build_encq_plan(*cfg);
+    if (Q.status != QVC_OK) c.status = Q.status;
+    else c.enc_q(Q, c.blob, spec, g, noise, z_fm);
+  });
+}
+int flow_forward(const qvc_config* cfg, const void* blob, float* z_fm, const float* g, int B, int T, void* ws, int64_t ws_bytes,
+                 const Window& w) {
+  return run_path(cfg, blob, B, T, ws, ws_bytes, w, [&](Path<EmuBackend>& c) { c.cond_table(g); c.flow(z_fm, /*forward=*/true); });
 }
 }  // namespace
 
 extern "C" {
 
-// Same signature as qvc_infer_batch, host pointers everywhere, no stream.
+// Same signatures as qvc_infer_batch / qvc_infer_batch_ragged (the lengths on the host too), host pointers, no stream.
 int qvc_emu_infer_batch(const qvc_config* cfg, const void* blob, const float* unit, const float* g, const float* noise,
                         float* out, int32_t batch, int32_t frames, void* workspace, int64_t workspace_bytes) {
-  Run r;
-  int st = r.prepare(cfg, batch, frames, workspace_bytes);
-  if (st != QVC_OK) return st;
-  Path<EmuBackend> c{r.P, static_cast<const char*>(blob), static_cast<char*>(workspace), r.W, batch, frames, r.be};
-  c.cond_table(g);
-  c.enc_p(unit, noise, c.wsp<float>(r.W.z));
-  c.flow(c.wsp<float>(r.W.z));
-  c.dec_trunk_wave(c.wsp<float>(r.W.z), c.wsp<float>(r.W.post), out);
-  return c.status;
+  return std::min(0, infer(cfg, blob, unit, g, noise, out, batch, frames, nullptr, workspace, workspace_bytes, Window()));
 }
-
-// Same signature as qvc_infer_batch_ragged, host pointers (the lengths too), no stream.
 int qvc_emu_infer_batch_ragged(const qvc_config* cfg, const void* blob, const float* unit, const float* g, const float* noise,
                                float* out, int32_t batch, int32_t max_frames, const int32_t* frames_host, void* workspace,
                                int64_t workspace_bytes) {
-  Run r;
-  int st = r.prepare(cfg, batch, max_frames, workspace_bytes);
-  if (st != QVC_OK) return st;
-  Path<EmuBackend> c{r.P, static_cast<const char*>(blob), static_cast<char*>(workspace), r.W, batch, max_frames, r.be};
-  c.lens = frames_host;
-  c.cond_table(g);
-  c.enc_p(unit, noise, c.wsp<float>(r.W.z));
-  c.flow(c.wsp<float>(r.W.z));
-  c.dec_trunk_wave(c.wsp<float>(r.W.z), c.wsp<float>(r.W.post), out);
-  return c.status;
+  return std::min(0, infer(cfg, blob, unit, g, noise, out, batch, max_frames, frames_host, workspace, workspace_bytes, Window()));
 }
 
 // Same signature as qvc_stream_step, host pointers, no stream.
 int qvc_emu_stream_step(const qvc_config* cfg, const void* blob, void* state, int64_t state_bytes, const float* unit_new,
                         const float* g, const float* noise_new, float* out, int32_t batch, int32_t hop, const int32_t* pos,
                         const int32_t* lens, void* workspace, int64_t workspace_bytes) {
-  Plan P = build_plan(*cfg);
-  const StreamGeom G = stream_geom(P, hop);
-  if (G.status != QVC_OK) return G.status;
+  Plan P; StreamGeom G;
+  const int gs = stream_plan(cfg, hop, P, G);
+  if (gs != QVC_OK) return gs;
   if (state_bytes < carve_stream_state(P, G, batch).bytes || workspace_bytes < carve_stream_scratch(P, G, batch).bytes) return QVC_ERR_SMALL_BUFFER;
   EmuBackend be;
   return stream_step(P, static_cast<const char*>(blob), static_cast<char*>(state), static_cast<char*>(workspace), unit_new, g,
@@ -587,25 +580,11 @@ int qvc_emu_stream_step(const qvc_config* cfg, const void* blob, void* state, in
 // Same signatures as qvc_enc_q / qvc_flow_forward, host pointers, no stream.
 int qvc_emu_enc_q(const qvc_config* cfg, const void* encq_blob, const float* spec, const float* g, const float* noise,
                   float* z_fm, int32_t batch, int32_t frames, void* workspace, int64_t workspace_bytes) {
-  Run r;
-  int st = r.prepare(cfg, batch, frames, workspace_bytes);
-  if (st != QVC_OK) return st;
-  const EncQPlan Q = build_encq_plan(*cfg);
-  if (Q.status != QVC_OK) return Q.status;
-  Path<EmuBackend> c{r.P, static_cast<const char*>(encq_blob), static_cast<char*>(workspace), r.W, batch, frames, r.be};
-  c.enc_q(Q, static_cast<const char*>(encq_blob), spec, g, noise, z_fm);
-  return c.status;
+  return std::min(0, enc_q(cfg, encq_blob, spec, g, noise, z_fm, batch, frames, workspace, workspace_bytes, Window()));
 }
-
 int qvc_emu_flow_forward(const qvc_config* cfg, const void* blob, float* z_fm, const float* g, int32_t batch, int32_t frames,
                          void* workspace, int64_t workspace_bytes) {
-  Run r;
-  int st = r.prepare(cfg, batch, frames, workspace_bytes);
-  if (st != QVC_OK) return st;
-  Path<EmuBackend> c{r.P, static_cast<const char*>(blob), static_cast<char*>(workspace), r.W, batch, frames, r.be};
-  c.cond_table(g);
-  c.flow(z_fm, /*forward=*/true);
-  return c.status;
+  return std::min(0, flow_forward(cfg, blob, z_fm, g, batch, frames, workspace, workspace_bytes, Window()));
 }
 
 // Same signature as qvc_speaker_embed, host pointers, no stream.
@@ -621,53 +600,21 @@ int qvc_emu_speaker_embed(const qvc_config* cfg, const void* spk_blob, const flo
 }
 
 // ---- windowed twins (the GPU step test): the same paths, issuing only steps [lo, hi) (Path::step) from whatever the
-// workspace and output buffers hold.  sw = {pair_chain3, post_tail, wn_chunk} as the library's debug switches (null:
-// their defaults); kinds (optional) receives the StepKind of every step.  Returns the step count of the whole path, or
-// a negative status.
+// workspace and output buffers hold (see Window).  Return the step count of the whole path, or a negative status.
 int qvc_emu_infer_window(const qvc_config* cfg, const void* blob, const float* unit, const float* g, const float* noise, float* out,
                          int32_t batch, int32_t frames, const int32_t* lens, void* workspace, int64_t workspace_bytes,
                          const int32_t* sw, int32_t lo, int32_t hi, int32_t* kinds, int32_t max_kinds) {
-  Run r;
-  int st = r.prepare(cfg, batch, frames, workspace_bytes);
-  if (st != QVC_OK) return st;
-  r.switches(sw);
-  Path<EmuBackend> c{r.P, static_cast<const char*>(blob), static_cast<char*>(workspace), r.W, batch, frames, r.be};
-  c.lens = lens;
-  window(c, lo, hi, kinds, max_kinds);
-  c.cond_table(g);
-  c.enc_p(unit, noise, c.wsp<float>(r.W.z));
-  c.flow(c.wsp<float>(r.W.z));
-  c.dec_trunk_wave(c.wsp<float>(r.W.z), c.wsp<float>(r.W.post), out);
-  return c.status != QVC_OK ? c.status : c.step_n;
+  return infer(cfg, blob, unit, g, noise, out, batch, frames, lens, workspace, workspace_bytes, Window{sw, lo, hi, kinds, max_kinds});
 }
-
 int qvc_emu_enc_q_window(const qvc_config* cfg, const void* encq_blob, const float* spec, const float* g, const float* noise,
                          float* z_fm, int32_t batch, int32_t frames, void* workspace, int64_t workspace_bytes,
                          const int32_t* sw, int32_t lo, int32_t hi, int32_t* kinds, int32_t max_kinds) {
-  Run r;
-  int st = r.prepare(cfg, batch, frames, workspace_bytes);
-  if (st != QVC_OK) return st;
-  const EncQPlan Q = build_encq_plan(*cfg);
-  if (Q.status != QVC_OK) return Q.status;
-  r.switches(sw);
-  Path<EmuBackend> c{r.P, static_cast<const char*>(encq_blob), static_cast<char*>(workspace), r.W, batch, frames, r.be};
-  window(c, lo, hi, kinds, max_kinds);
-  c.enc_q(Q, static_cast<const char*>(encq_blob), spec, g, noise, z_fm);
-  return c.status != QVC_OK ? c.status : c.step_n;
+  return enc_q(cfg, encq_blob, spec, g, noise, z_fm, batch, frames, workspace, workspace_bytes, Window{sw, lo, hi, kinds, max_kinds});
 }
-
 int qvc_emu_flow_forward_window(const qvc_config* cfg, const void* blob, float* z_fm, const float* g, int32_t batch, int32_t frames,
                                 void* workspace, int64_t workspace_bytes, const int32_t* sw, int32_t lo, int32_t hi, int32_t* kinds,
                                 int32_t max_kinds) {
-  Run r;
-  int st = r.prepare(cfg, batch, frames, workspace_bytes);
-  if (st != QVC_OK) return st;
-  r.switches(sw);
-  Path<EmuBackend> c{r.P, static_cast<const char*>(blob), static_cast<char*>(workspace), r.W, batch, frames, r.be};
-  window(c, lo, hi, kinds, max_kinds);
-  c.cond_table(g);
-  c.flow(z_fm, /*forward=*/true);
-  return c.status != QVC_OK ? c.status : c.step_n;
+  return flow_forward(cfg, blob, z_fm, g, batch, frames, workspace, workspace_bytes, Window{sw, lo, hi, kinds, max_kinds});
 }
 
 // Every buffer of the Workspace (carve_workspace) for (cfg, batch, frames): what the step test compares.
@@ -722,30 +669,11 @@ int qvc_emu_workspace_map(const qvc_config* cfg, int32_t batch, int32_t frames, 
   return n;
 }
 
+// Layout decisions of the plan for `cfg` (plan_flags; test hook: the shipped configuration must actually take the fast paths)
+int qvc_emu_plan_flags(const qvc_config* cfg, int32_t* out) { return plan_flags(cfg, out); }
+
 // Stage taps for debugging: copies frame-major fp32 buffers out of the workspace after a run.
 // which: 0 = z (after flow), 1 = post (conv_post output), 2 = stage-0 MRF mean, 3 = stage-1 MRF mean
-// Layout decisions of the plan for `cfg` (test hook: the shipped configuration must actually take the fast paths):
-// out[0] enc_p.proj rows paired [mu | log sigma] (sampling in the epilogue), out[1] its fragments per wave,
-// out[2..3] up-samplers 0 / 1 lane-packed, out[4] conv_post + tail can run as one launch,
-// out[5..6] waves per workgroup of the stage 0 / 1 ResBlock pairs, out[7] all pairs fusable
-int qvc_emu_plan_flags(const qvc_config* cfg, int32_t* out) {
-  if (!cfg || !out) return QVC_ERR_BAD_ARG;
-  const Plan P = build_plan(*cfg);
-  if (P.status != QVC_OK) return P.status;
-  for (int i = 0; i < 8; ++i) out[i] = 0;
-  out[0] = P.enc_proj.gau; out[1] = P.enc_proj.MF;
-  for (size_t i = 0; i < P.stages.size() && i < 2; ++i) {
-    out[2 + i] = P.stages[i].up.lp;
-    out[5 + i] = block_waves(P.stages[i].c1[0]);
-  }
-  out[4] = post_tail_supported(P.conv_post) ? 1 : 0;
-  int all = 1;
-  for (const StagePlan& st : P.stages)
-    for (size_t j = 0; j < st.c1.size(); ++j) all = all && pair_supported(st.c1[j], st.c2[j]) && st.c1[j].lp;
-  out[7] = all;
-  return QVC_OK;
-}
-
 int64_t qvc_emu_tap_offset(const qvc_config* cfg, int32_t batch, int32_t frames, int32_t which) {
   Plan P = build_plan(*cfg);
   if (P.status != QVC_OK) return P.status;

@@ -4,6 +4,7 @@
 // allocation, no synchronisation, no host read of device data, so a whole qvc_infer_batch
 // call can be captured into a hipGraph by the caller.
 #include <hip/hip_runtime.h>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -57,7 +58,6 @@ struct Branches {
   }
   void branch(int j) { cur = of(j); }
   void branch_done(int j) { if (aux && j < 3 && hipEventRecord(aux->done[j], of(j)) != hipSuccess) ok = false; }
-  void wait_branch_done(int j) { if (aux && j < 3 && hipStreamWaitEvent(cur, aux->done[j], 0) != hipSuccess) ok = false; }
   void join(int n) {
     if (aux)     // branches 1 and 2 ran on the auxiliary streams (further ones, and branch 0, on main)
       for (int j = 1; j < n && j <= 2; ++j)
@@ -67,23 +67,22 @@ struct Branches {
 };
 
 struct HipBackend {
-  hipStream_t stream;
+  static constexpr bool kSingleBandTail = true;   // the launchers pick the kernels by TailArgs::bands / post_tail_bands(conv_post)
+  hipStream_t stream0, stream;                    // the caller's stream / the current branch's
   Branches br;
+  explicit HipBackend(void* s, qvc_aux* aux = nullptr) : stream0(static_cast<hipStream_t>(s)), stream(stream0) { br.aux = aux; }
   void fork(int n) { br.main = stream0; br.fork(n); stream = br.cur; }
   void branch(int j) { br.branch(j); stream = br.cur; }
   void branch_done(int j) { br.branch_done(j); }
-  void wait_branch_done(int j) { br.wait_branch_done(j); }
   void join(int n) { br.join(n); stream = stream0; }
-  hipStream_t stream0 = nullptr;
+  int finish() const { return br.ok ? QVC_OK : QVC_ERR_LAUNCH; }
   int conv(const ConvDesc& d, const ConvArgs& a, int batch, int epi, int dtype) { return launch_conv(d, a, batch, epi, dtype, stream); }
-  int pair(const ConvDesc& d1, const ConvDesc& d2, const PairArgs& a, int batch, int dtype) { return launch_pair(d1, d2, a, batch, dtype, stream); }
   int pair3(const ConvDesc* d1, const ConvDesc* d2, const PairArgs3& a, int batch, int dtype) { return launch_pair3(d1, d2, a, batch, dtype, stream); }
   bool chain_ok(const ConvDesc* d1, const ConvDesc* d2, int n) const { return debug_get(DBG_PAIR_CHAIN3) != 0 && chain_supported(d1, d2, n); }
   int chain(const ConvDesc* d1, const ConvDesc* d2, const ChainArgs& a, int batch, int dtype) { return launch_chain(d1, d2, a, batch, dtype, stream); }
   int wn(const ConvDesc& din, const ConvDesc&, const WnArgs& a, int batch, int dtype) { return launch_wn(din, a, batch, dtype, stream); }
-  // the stack kernel recomputes halo frames but a layer is bound by its weight stream, not by MFMA work: measured
-  // no slower than one launch per layer at any batch (16.4 vs 17.9 us per layer at batch 1)
-  bool use_wn_stack(int, int) const { return true; }
+  // (the stack kernel recomputes halo frames but a layer is bound by its weight stream, not by MFMA work: measured
+  // no slower than one launch per layer at any batch, 16.4 vs 17.9 us per layer at batch 1 -- so it runs wherever it applies)
   int wn_stack_chunk(int layers) const { return wn_chunk(layers); }
   int wn_stack(const ConvDesc& din, const ConvDesc&, const ConvDesc&, const WnStackArgs& a, int batch, int dtype, const ConvDesc*, const ConvDesc*) { return launch_wn_stack(din, a, batch, dtype, stream); }
   int gemv(const GemvArgs& a) { return launch_gemv(a, stream); }
@@ -91,40 +90,33 @@ struct HipBackend {
   int tail(const TailArgs& a) { return launch_tail(a, stream); }
   bool post_tail_ok(const ConvDesc& d) const { return debug_get(DBG_POST_TAIL) != 0 && post_tail_supported(d); }
   int post_tail(const ConvDesc& d, const PostTailArgs& a, int batch, int dtype) { return launch_post_tail(d, a, batch, dtype, stream); }
-  // single-band decoder: the launchers pick the kernels by TailArgs::bands / post_tail_bands(conv_post)
-  int tail1(const TailArgs& a) { return launch_tail(a, stream); }
-  int post_tail1(const ConvDesc& d, const PostTailArgs& a, int batch, int dtype) { return launch_post_tail(d, a, batch, dtype, stream); }
   int zero(void* p, size_t bytes) { return hipMemsetAsync(p, 0, bytes, stream) == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH; }
   int copy_batch(const CopyDesc* d, int n) { return launch_copy_batch(d, n, stream); }
 };
 using Ctx = Path<HipBackend>;
 
-// launch_stop / launch_steps: the step window of the whole-path entry points.  Host-side bookkeeping only.
-template <class Backend> void window_from_switch(Path<Backend>& c) {
-  const int stop = debug_get(DBG_LAUNCH_STOP);
-  if (stop >= 0) c.step_hi = stop;
-}
-template <class Backend> void record_steps(const Path<Backend>& c) { debug_launch_steps().store(c.step_n, std::memory_order_relaxed); }
-
-// Same launches, each bracketed by events on the stream (diagnostics only).
+// Same launches, each bracketed by events on the stream (diagnostics only).  Every method: the launch, then the
+// record's name and its algorithmic flops / bytes.
 struct TimedBackend {
-  void fork(int) {} void branch(int) {} void branch_done(int) {} void wait_branch_done(int) {} void join(int) {}
+  static constexpr bool kSingleBandTail = true;
+  void fork(int) {} void branch(int) {} void branch_done(int) {} void join(int) {}
   hipStream_t stream;
   qvc_launch_record* rec; int max_rec; int n = 0;
   std::vector<hipEvent_t> ev;
   bool ok = true;
   void mark() { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess || hipEventRecord(e, stream) != hipSuccess) ok = false; ev.push_back(e); }
-  void note(const char* name, double flops, double bytes) {
-    if (n < max_rec) { std::snprintf(rec[n].name, sizeof(rec[n].name), "%s", name); rec[n].flops = flops; rec[n].bytes = bytes; rec[n].ms = 0.f; }
+  template <class F> int timed(F launch) { if (ev.empty()) mark(); const int st = launch(); mark(); return st; }
+  void note(double flops, double bytes, const char* fmt, ...) {
+    if (n < max_rec) {
+      va_list ap; va_start(ap, fmt); std::vsnprintf(rec[n].name, sizeof(rec[n].name), fmt, ap); va_end(ap);
+      rec[n].flops = flops; rec[n].bytes = bytes; rec[n].ms = 0.f;
+    }
     ++n;
   }
+  static const char* tn(int dtype) { return dtype == QVC_F16 ? "f16" : (dtype == QVC_BF16X ? "bf16x" : "bf16"); }
   int conv(const ConvDesc& d, const ConvArgs& a, int batch, int epi, int dtype) {
-    if (ev.empty()) mark();
     int nf = 0;
-    int st = launch_conv(d, a, batch, epi, dtype, stream, &nf);
-    mark();
-    char name[48];
-    std::snprintf(name, sizeof(name), "conv<%s,MF%d,NF%d,WM%d,%s>", dtype == QVC_F16 ? "f16" : "bf16", d.MF, nf, d.WM, epi == EPI_GAU ? "gau" : (epi == EPI_SAMPLE ? "smp" : "std"));
+    const int st = timed([&] { return launch_conv(d, a, batch, epi, dtype, stream, &nf); });
     // algorithmic work: a transposed conv does k MACs per (input frame, ci, co), a conv taps MACs per output
     const double macs = d.up_s > 1 ? (double)batch * a.T_in * d.Cin * d.Cout * (double)d.ksize
                                    : (double)batch * a.Nq * (double)d.M * d.taps * d.Cin;
@@ -140,105 +132,85 @@ struct TimedBackend {
       if (a.res16) out_b += outs * 2;
       if (a.y32b) out_b += (double)batch * a.Nq * (d.M - a.split) * 8;
     }
-    note(name, 2.0 * macs, in_b + out_b + (double)d.w_bytes());
+    note(2.0 * macs, in_b + out_b + (double)d.w_bytes(), "conv<%s,MF%d,NF%d,WM%d,%s>", tn(dtype), d.MF, nf, d.WM,
+         epi == EPI_GAU ? "gau" : (epi == EPI_SAMPLE ? "smp" : "std"));
     return st;
   }
-  int pair(const ConvDesc& d1, const ConvDesc& d2, const PairArgs& a, int batch, int dtype) {
-    PairArgs3 a3; a3.p[0] = a; a3.n = 1;
-    return pair3(&d1, &d2, a3, batch, dtype);
-  }
   int pair3(const ConvDesc* d1, const ConvDesc* d2, const PairArgs3& a, int batch, int dtype) {
-    if (ev.empty()) mark();
     int nf = 0;
-    int st = launch_pair3(d1, d2, a, batch, dtype, stream, &nf);
-    mark();
-    char name[48];
+    const int st = timed([&] { return launch_pair3(d1, d2, a, batch, dtype, stream, &nf); });
     // one kernel symbol serves 1..3 chains per launch; the record's flops / bytes are those of the whole launch
-    const char* tn = dtype == QVC_F16 ? "f16" : (dtype == QVC_BF16X ? "bf16x" : "bf16");
-    if (nf >= 100) std::snprintf(name, sizeof(name), "rbpair_persist<%s,MF%d,NF%d>", tn, d1[0].MF, nf - 100);
-    else std::snprintf(name, sizeof(name), "rbpair<%s,MF%d,NF%d,WM%d>", tn, d1[0].MF, nf, d1[0].WM);
     double fl = 0, by = 0;
     for (int i = 0; i < a.n; ++i) {
       const double outs = (double)batch * a.p[i].T * a.p[i].C;
       fl += 2.0 * 2.0 * outs * a.p[i].C * a.p[i].k;
       by += outs * 2 * 2 + (double)d1[i].w_bytes() + (double)d2[i].w_bytes();   // algorithmic: the stream read once, written once (the kernel's second read of x for the residual is NOT counted: it shows up as traffic / algorithmic > 1)
     }
-    note(name, fl, by);
+    note(fl, by, "rbpair<%s,MF%d,NF%d,WM%d>", tn(dtype), d1[0].MF, nf, d1[0].WM);
     return st;
   }
   bool chain_ok(const ConvDesc* d1, const ConvDesc* d2, int n) const { return debug_get(DBG_PAIR_CHAIN3) != 0 && chain_supported(d1, d2, n); }
   int chain(const ConvDesc* d1, const ConvDesc* d2, const ChainArgs& a, int batch, int dtype) {
-    if (ev.empty()) mark();
     int nf = 0;
-    int st = launch_chain(d1, d2, a, batch, dtype, stream, &nf);
-    mark();
-    char name[48];
-    const char* tn = dtype == QVC_F16 ? "f16" : (dtype == QVC_BF16X ? "bf16x" : "bf16");
-    std::snprintf(name, sizeof(name), "rbchain<%s,MF%d,NF%d,WM%d,k%d>", tn, d1[0].MF, nf, d1[0].WM, d1[0].taps);
+    const int st = timed([&] { return launch_chain(d1, d2, a, batch, dtype, stream, &nf); });
     const double outs = (double)batch * a.p[0].T * a.p[0].C;
-    note(name, a.n * 2.0 * 2.0 * outs * a.p[0].C * a.p[0].k, outs * 2 * 2 + a.n * ((double)d1[0].w_bytes() + (double)d2[0].w_bytes()));
+    note(a.n * 2.0 * 2.0 * outs * a.p[0].C * a.p[0].k, outs * 2 * 2 + a.n * ((double)d1[0].w_bytes() + (double)d2[0].w_bytes()),
+         "rbchain<%s,MF%d,NF%d,WM%d,k%d>", tn(dtype), d1[0].MF, nf, d1[0].WM, d1[0].taps);
     return st;
   }
   int wn(const ConvDesc& din, const ConvDesc& drs, const WnArgs& a, int batch, int dtype) {
-    if (ev.empty()) mark();
     int nf = 0;
-    int st = launch_wn(din, a, batch, dtype, stream, &nf);
-    mark();
-    char name[48];
-    std::snprintf(name, sizeof(name), "wn_layer<%s,W%d,NF%d%s>", dtype == QVC_F16 ? "f16" : "bf16", din.WM, nf, a.last ? ",last" : "");
+    const int st = timed([&] { return launch_wn(din, a, batch, dtype, stream, &nf); });
     const double cols = (double)batch * a.T;
-    note(name, 2.0 * cols * a.H * (2.0 * a.H * a.taps + (double)drs.M), cols * a.H * 4 * (a.last ? 3 : 5) + (double)din.w_bytes() + (double)drs.w_bytes());
+    note(2.0 * cols * a.H * (2.0 * a.H * a.taps + (double)drs.M), cols * a.H * 4 * (a.last ? 3 : 5) + (double)din.w_bytes() + (double)drs.w_bytes(),
+         "wn_layer<%s,W%d,NF%d%s>", tn(dtype), din.WM, nf, a.last ? ",last" : "");
     return st;
   }
-  bool use_wn_stack(int, int) const { return true; }
   int wn_stack_chunk(int layers) const { return wn_chunk(layers); }
   int wn_stack(const ConvDesc& din, const ConvDesc& drs, const ConvDesc& drs_last, const WnStackArgs& a, int batch, int dtype,
                const ConvDesc* dpre, const ConvDesc* dpost) {
-    if (ev.empty()) mark();
-    int st = launch_wn_stack(din, a, batch, dtype, stream);
-    mark();
-    char name[56];
+    const int st = timed([&] { return launch_wn_stack(din, a, batch, dtype, stream); });
     const int v = wn_stack_variant(din, a, batch);
-    std::snprintf(name, sizeof(name), "%s<%s,W%d,L%d%s%s>", v >= 2 ? "wn_stack2" : "wn_stack", dtype == QVC_F16 ? "f16" : "bf16",
-                  din.WM, a.layers, dpre ? ",pre+post" : "", v == 3 ? ",64f" : "");
     const double cols = (double)batch * a.T;
     const double fl = 2.0 * cols * a.H * (a.layers * 2.0 * a.H * a.taps + (a.layers - (a.final_layer ? 1 : 0)) * (double)drs.M + (a.final_layer ? (double)drs_last.M : 0.0));
     const double fuse_fl = (dpre ? 2.0 * cols * dpre->M * dpre->Cin : 0.0) + (dpost ? 2.0 * cols * dpost->M * dpost->Cin : 0.0);
-    note(name, fl + fuse_fl, cols * a.H * 8 + a.layers * ((double)din.w_bytes() + (double)drs.w_bytes()));
+    note(fl + fuse_fl, cols * a.H * 8 + a.layers * ((double)din.w_bytes() + (double)drs.w_bytes()), "%s<%s,W%d,L%d%s%s>",
+         v >= 2 ? "wn_stack2" : "wn_stack", tn(dtype), din.WM, a.layers, dpre ? ",pre+post" : "", v == 3 ? ",64f" : "");
     return st;
   }
-  int gemv(const GemvArgs& a) { if (ev.empty()) mark(); int st = launch_gemv(a, stream); mark();
-    note("cond_gemv", 2.0 * a.rows * a.gin * a.batch, (double)a.rows * a.gin * 4 + (double)a.batch * (a.rows + a.gin) * 4); return st; }
-  int sample(const SampleArgs& a) { if (ev.empty()) mark(); int st = launch_sample(a, stream); mark();
-    note("sample", 0, (double)a.batch * a.frames * a.C * 16); return st; }
-  int tail(const TailArgs& a) { if (ev.empty()) mark(); int st = launch_tail(a, stream); mark();
-    note("istft_synth", 0, (double)a.batch * ((double)a.F * 72 * 4 + 16.0 * (a.F - 1) * 4)); return st; }
+  int gemv(const GemvArgs& a) {
+    const int st = timed([&] { return launch_gemv(a, stream); });
+    note(2.0 * a.rows * a.gin * a.batch, (double)a.rows * a.gin * 4 + (double)a.batch * (a.rows + a.gin) * 4, "cond_gemv");
+    return st;
+  }
+  int sample(const SampleArgs& a) {
+    const int st = timed([&] { return launch_sample(a, stream); });
+    note(0, (double)a.batch * a.frames * a.C * 16, "sample");
+    return st;
+  }
+  // per band and frame 18 fp32 rows in, 4 samples out (four bands, or the single-band decoder's one)
+  int tail(const TailArgs& a) {
+    const int st = timed([&] { return launch_tail(a, stream); });
+    const bool one = a.bands == 1;
+    note(0, (double)a.batch * ((double)a.F * (one ? 18 : 72) * 4 + (one ? 4.0 : 16.0) * (a.F - 1) * 4), one ? "istft1" : "istft_synth");
+    return st;
+  }
   bool post_tail_ok(const ConvDesc& d) const { return debug_get(DBG_POST_TAIL) != 0 && post_tail_supported(d); }
+  // algorithmic: the three stage-final ResBlock streams read once, the waveform written once, conv_post's weights
+  // (single band: its 18 rows, half of the packed stream)
   int post_tail(const ConvDesc& d, const PostTailArgs& a, int batch, int dtype) {
-    if (ev.empty()) mark();
-    int st = launch_post_tail(d, a, batch, dtype, stream);
-    mark();
-    char name[48];
-    std::snprintf(name, sizeof(name), "post_tail<%s>", dtype == QVC_F16 ? "f16" : "bf16");
-    note(name, 2.0 * batch * (double)a.F * d.M * d.taps * d.Cin,
-         (double)batch * ((double)a.c.T_in * d.Cin * 2 * 3 + 16.0 * (a.F - 1) * 4) + (double)d.w_bytes());
+    const int st = timed([&] { return launch_post_tail(d, a, batch, dtype, stream); });
+    const bool one = post_tail_bands(d) == 1;
+    note(2.0 * batch * (double)a.F * d.M * d.taps * d.Cin,
+         (double)batch * ((double)a.c.T_in * d.Cin * 2 * 3 + (one ? 4.0 : 16.0) * (a.F - 1) * 4) + (double)d.w_bytes() / (one ? 2 : 1),
+         one ? "post_tail1<%s>" : "post_tail<%s>", tn(dtype));
     return st;
   }
-  int tail1(const TailArgs& a) { if (ev.empty()) mark(); int st = launch_tail(a, stream); mark();
-    note("istft1", 0, (double)a.batch * ((double)a.F * 18 * 4 + 4.0 * (a.F - 1) * 4)); return st; }
-  int post_tail1(const ConvDesc& d, const PostTailArgs& a, int batch, int dtype) {
-    if (ev.empty()) mark();
-    int st = launch_post_tail(d, a, batch, dtype, stream);
-    mark();
-    char name[48];
-    std::snprintf(name, sizeof(name), "post_tail1<%s>", dtype == QVC_F16 ? "f16" : "bf16");
-    // algorithmic: the three stage-final ResBlock streams read once, the waveform written once, conv_post's 18 rows
-    note(name, 2.0 * batch * (double)a.F * d.M * d.taps * d.Cin,
-         (double)batch * ((double)a.c.T_in * d.Cin * 2 * 3 + 4.0 * (a.F - 1) * 4) + (double)d.w_bytes() / 2);
+  int zero(void* p, size_t bytes) {
+    const int st = timed([&] { return hipMemsetAsync(p, 0, bytes, stream) == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH; });
+    note(0, (double)bytes, "memset");
     return st;
   }
-  int zero(void* p, size_t bytes) { if (ev.empty()) mark(); int st = hipMemsetAsync(p, 0, bytes, stream) == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH; mark();
-    note("memset", 0, (double)bytes); return st; }
   int finish() {
     if (!ok || hipStreamSynchronize(stream) != hipSuccess) ok = false;
     for (int i = 0; i + 1 < (int)ev.size() && i < max_rec; ++i) {
@@ -251,36 +223,34 @@ struct TimedBackend {
   }
 };
 
-int check_common(const qvc_config* cfg, const void* blob, int batch, int frames, void* ws, int64_t ws_bytes, Plan& P,
-                 Workspace& W) {
-  if (!cfg || !blob || !ws || batch <= 0 || frames <= 1) return QVC_ERR_BAD_ARG;
-  P = build_plan(*cfg);
+// What every entry point that runs the path, or a stage of it, does: argument check, plan, workspace carve-up, the
+// path context on the caller's backend; `body` issues the launches.  whole: a whole-path entry point, which honours the
+// step window "launch_stop" and reports "launch_steps" (host-side bookkeeping only).
+template <class Backend, class Body>
+int run_path(Backend& be, bool whole, bool args_ok, const qvc_config* cfg, const void* blob, int batch, int frames, void* ws,
+             int64_t ws_bytes, Body body) {
+  if (!args_ok || !cfg || !blob || !ws || batch <= 0 || frames <= 1) return QVC_ERR_BAD_ARG;
+  const Plan P = build_plan(*cfg);
   if (P.status != QVC_OK) return P.status;
-  W = carve_workspace(P, batch, frames);
+  const Workspace W = carve_workspace(P, batch, frames);
   if (ws_bytes < W.bytes) return QVC_ERR_SMALL_BUFFER;
   if ((reinterpret_cast<uintptr_t>(ws) & 255) || (reinterpret_cast<uintptr_t>(blob) & 255)) return QVC_ERR_BAD_ARG;
-  return QVC_OK;
+  Path<Backend> c{P, static_cast<const char*>(blob), static_cast<char*>(ws), W, batch, frames, be};
+  const int stop = debug_get(DBG_LAUNCH_STOP);
+  if (whole && stop >= 0) c.step_hi = stop;
+  body(c);
+  if (whole) debug_launch_steps().store(c.step_n, std::memory_order_relaxed);
+  const int fin = be.finish();
+  return c.status != QVC_OK ? c.status : fin;
 }
 
 // qvc_infer_batch_ragged / _fm: the whole path over utterances of different lengths (unit_fm: units frame-major as on disk)
 int infer_ragged(const qvc_config* cfg, const void* blob_dev, const float* unit, bool unit_fm, const float* g, const float* noise,
                  float* out, int32_t batch, int32_t max_frames, const int32_t* frames_dev, void* workspace, int64_t workspace_bytes,
                  void* stream) {
-  if (!unit || !g || !noise || !out || !frames_dev) return QVC_ERR_BAD_ARG;
-  Plan P; Workspace W;
-  int st = check_common(cfg, blob_dev, batch, max_frames, workspace, workspace_bytes, P, W);
-  if (st != QVC_OK) return st;
-  HipBackend be; be.stream = be.stream0 = static_cast<hipStream_t>(stream);
-  Ctx c{P, static_cast<const char*>(blob_dev), static_cast<char*>(workspace), W, batch, max_frames, be};
-  c.lens = frames_dev;
-  c.unit_fm = unit_fm;
-  window_from_switch(c);
-  c.cond_table(g);
-  c.enc_p(unit, noise, c.wsp<float>(W.z));
-  c.flow(c.wsp<float>(W.z));
-  c.dec_trunk_wave(c.wsp<float>(W.z), c.wsp<float>(W.post), out);
-  record_steps(c);
-  return c.status != QVC_OK ? c.status : (be.br.ok ? QVC_OK : QVC_ERR_LAUNCH);
+  HipBackend be(stream);
+  return run_path(be, true, unit && g && noise && out && frames_dev, cfg, blob_dev, batch, max_frames, workspace, workspace_bytes,
+                  [&](Ctx& c) { c.lens = frames_dev; c.unit_fm = unit_fm; c.infer(unit, g, noise, out); });
 }
 
 }  // namespace
@@ -351,24 +321,7 @@ int64_t qvc_workspace_bytes(const qvc_config* cfg, int32_t batch, int32_t frames
   return carve_workspace(P, batch, frames).bytes;
 }
 
-int qvc_plan_info(const qvc_config* cfg, int32_t info[8]) {
-  if (!cfg || !info) return QVC_ERR_BAD_ARG;
-  const Plan P = build_plan(*cfg);
-  if (P.status != QVC_OK) return P.status;
-  for (int i = 0; i < 8; ++i) info[i] = 0;
-  info[0] = P.enc_proj.gau; info[1] = P.enc_proj.MF;
-  for (size_t i = 0; i < P.stages.size() && i < 2; ++i) {
-    info[2 + i] = P.stages[i].up.lp;
-    info[5 + i] = block_waves(P.stages[i].c1[0]);
-  }
-  info[4] = post_tail_supported(P.conv_post) ? 1 : 0;
-  int all = P.cfg.n_resblocks <= 3 ? 1 : 0;
-  for (const StagePlan& st : P.stages)
-    for (size_t j = 0; j < st.c1.size(); ++j)
-      all = all && pair_supported(st.c1[j], st.c2[j]) && st.c1[j].lp && st.c2[j].lp && st.c1[j].MF == st.c1[0].MF && st.c1[j].WM == st.c1[0].WM;
-  info[7] = all;
-  return QVC_OK;
-}
+int qvc_plan_info(const qvc_config* cfg, int32_t info[8]) { return plan_flags(cfg, info); }
 
 int qvc_aux_create(qvc_aux** out) {
   if (!out) return QVC_ERR_BAD_ARG;
@@ -401,19 +354,9 @@ int qvc_infer_batch(const qvc_config* cfg, const void* blob_dev, const float* un
 int qvc_infer_batch_ex(const qvc_config* cfg, const void* blob_dev, const float* unit, const float* g,
                        const float* noise, float* out, int32_t batch, int32_t frames, void* workspace,
                        int64_t workspace_bytes, void* stream, qvc_aux* aux) {
-  if (!unit || !g || !noise || !out) return QVC_ERR_BAD_ARG;
-  Plan P; Workspace W;
-  int st = check_common(cfg, blob_dev, batch, frames, workspace, workspace_bytes, P, W);
-  if (st != QVC_OK) return st;
-  HipBackend be; be.stream = be.stream0 = static_cast<hipStream_t>(stream); be.br.aux = aux;
-  Ctx c{P, static_cast<const char*>(blob_dev), static_cast<char*>(workspace), W, batch, frames, be};
-  window_from_switch(c);
-  c.cond_table(g);
-  c.enc_p(unit, noise, c.wsp<float>(W.z));
-  c.flow(c.wsp<float>(W.z));
-  c.dec_trunk_wave(c.wsp<float>(W.z), c.wsp<float>(W.post), out);
-  record_steps(c);
-  return c.status != QVC_OK ? c.status : (be.br.ok ? QVC_OK : QVC_ERR_LAUNCH);
+  HipBackend be(stream, aux);
+  return run_path(be, true, unit && g && noise && out, cfg, blob_dev, batch, frames, workspace, workspace_bytes,
+                  [&](Ctx& c) { c.infer(unit, g, noise, out); });
 }
 
 int qvc_infer_batch_ragged(const qvc_config* cfg, const void* blob_dev, const float* unit, const float* g,
@@ -429,58 +372,51 @@ int qvc_infer_batch_ragged_fm(const qvc_config* cfg, const void* blob_dev, const
 }
 
 int64_t qvc_stream_state_bytes(const qvc_config* cfg, int32_t batch, int32_t hop) {
-  if (!cfg || batch <= 0 || hop <= 0) return QVC_ERR_BAD_ARG;
-  Plan P = build_plan(*cfg);
-  const StreamGeom G = stream_geom(P, hop);
-  if (G.status != QVC_OK) return G.status;
-  return carve_stream_state(P, G, batch).bytes;
+  Plan P; StreamGeom G;
+  const int st = batch > 0 ? stream_plan(cfg, hop, P, G) : QVC_ERR_BAD_ARG;
+  return st != QVC_OK ? st : carve_stream_state(P, G, batch).bytes;
 }
 
 int64_t qvc_stream_workspace_bytes(const qvc_config* cfg, int32_t batch, int32_t hop) {
-  if (!cfg || batch <= 0 || hop <= 0) return QVC_ERR_BAD_ARG;
-  Plan P = build_plan(*cfg);
-  const StreamGeom G = stream_geom(P, hop);
-  if (G.status != QVC_OK) return G.status;
-  return carve_stream_scratch(P, G, batch).bytes;
+  Plan P; StreamGeom G;
+  const int st = batch > 0 ? stream_plan(cfg, hop, P, G) : QVC_ERR_BAD_ARG;
+  return st != QVC_OK ? st : carve_stream_scratch(P, G, batch).bytes;
 }
 
 int32_t qvc_stream_lag_frames(const qvc_config* cfg) {
-  if (!cfg) return QVC_ERR_BAD_ARG;
-  Plan P = build_plan(*cfg);
-  const StreamGeom G = stream_geom(P, 1);
-  return G.status != QVC_OK ? G.status : G.lag();
+  Plan P; StreamGeom G;
+  const int st = stream_plan(cfg, 1, P, G);
+  return st != QVC_OK ? st : G.lag();
 }
 
 int32_t qvc_stream_noise_lag_frames(const qvc_config* cfg) {
-  if (!cfg) return QVC_ERR_BAD_ARG;
-  Plan P = build_plan(*cfg);
-  const StreamGeom G = stream_geom(P, 1);
-  return G.status != QVC_OK ? G.status : G.He;
+  Plan P; StreamGeom G;
+  const int st = stream_plan(cfg, 1, P, G);
+  return st != QVC_OK ? st : G.He;
 }
 
 int qvc_stream_step(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
                     const float* g, const float* noise_new, float* out, int32_t batch, int32_t hop, const int32_t* pos_dev,
                     const int32_t* len_dev, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!cfg || !blob_dev || !state || !unit_new || !g || !noise_new || !out || !pos_dev || !len_dev || !workspace || batch <= 0 || hop <= 0)
-    return QVC_ERR_BAD_ARG;
-  Plan P = build_plan(*cfg);
-  const StreamGeom G = stream_geom(P, hop);
-  if (G.status != QVC_OK) return G.status;
+  if (!blob_dev || !state || !unit_new || !g || !noise_new || !out || !pos_dev || !len_dev || !workspace || batch <= 0) return QVC_ERR_BAD_ARG;
+  Plan P; StreamGeom G;
+  const int gs = stream_plan(cfg, hop, P, G);
+  if (gs != QVC_OK) return gs;
   if (state_bytes < carve_stream_state(P, G, batch).bytes || workspace_bytes < carve_stream_scratch(P, G, batch).bytes) return QVC_ERR_SMALL_BUFFER;
   if ((reinterpret_cast<uintptr_t>(workspace) & 255) || (reinterpret_cast<uintptr_t>(blob_dev) & 255) || (reinterpret_cast<uintptr_t>(state) & 255))
     return QVC_ERR_BAD_ARG;
-  HipBackend be; be.stream = be.stream0 = static_cast<hipStream_t>(stream);
+  HipBackend be(stream);
   const int st = stream_step(P, static_cast<const char*>(blob_dev), static_cast<char*>(state), static_cast<char*>(workspace), unit_new, g,
                              noise_new, out, batch, hop, pos_dev, len_dev, be);
-  return st != QVC_OK ? st : (be.br.ok ? QVC_OK : QVC_ERR_LAUNCH);
+  return st != QVC_OK ? st : be.finish();
 }
 
 int qvc_stream_reset_slot(const qvc_config* cfg, void* state, int64_t state_bytes, int32_t batch, int32_t hop, int32_t slot,
                           int32_t length, int32_t* pos_dev, int32_t* len_dev, void* stream) {
-  if (!cfg || !state || !pos_dev || !len_dev || batch <= 0 || hop <= 0 || slot < 0 || slot >= batch || length < 0) return QVC_ERR_BAD_ARG;
-  Plan P = build_plan(*cfg);
-  const StreamGeom G = stream_geom(P, hop);
-  if (G.status != QVC_OK) return G.status;
+  if (!state || !pos_dev || !len_dev || batch <= 0 || slot < 0 || slot >= batch || length < 0) return QVC_ERR_BAD_ARG;
+  Plan P; StreamGeom G;
+  const int gs = stream_plan(cfg, hop, P, G);
+  if (gs != QVC_OK) return gs;
   const StreamState S = carve_stream_state(P, G, batch);
   if (state_bytes < S.bytes) return QVC_ERR_SMALL_BUFFER;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -504,115 +440,67 @@ int qvc_infer_batch_timed(const qvc_config* cfg, const void* blob_dev, const flo
                           const float* noise, float* out, int32_t batch, int32_t frames, void* workspace,
                           int64_t workspace_bytes, void* stream, qvc_launch_record* records, int32_t max_records,
                           int32_t* n_records) {
-  if (!unit || !g || !noise || !out || !records || max_records <= 0 || !n_records) return QVC_ERR_BAD_ARG;
-  Plan P; Workspace W;
-  int st = check_common(cfg, blob_dev, batch, frames, workspace, workspace_bytes, P, W);
-  if (st != QVC_OK) return st;
   TimedBackend be{static_cast<hipStream_t>(stream), records, max_records};
-  Path<TimedBackend> c{P, static_cast<const char*>(blob_dev), static_cast<char*>(workspace), W, batch, frames, be};
-  window_from_switch(c);
-  c.cond_table(g);
-  c.enc_p(unit, noise, c.wsp<float>(W.z));
-  c.flow(c.wsp<float>(W.z));
-  c.dec_trunk_wave(c.wsp<float>(W.z), c.wsp<float>(W.post), out);
-  record_steps(c);
-  const int fin = be.finish();
-  *n_records = be.n;
-  return c.status != QVC_OK ? c.status : fin;
+  return run_path(be, true, unit && g && noise && out && records && max_records > 0 && n_records, cfg, blob_dev, batch, frames, workspace,
+                  workspace_bytes, [&](Path<TimedBackend>& c) { c.infer(unit, g, noise, out); *n_records = be.n; });
 }
 
 int qvc_enc_p(const qvc_config* cfg, const void* blob_dev, const float* unit, const float* noise, float* z_p_fm,
               int32_t batch, int32_t frames, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!unit || !noise || !z_p_fm) return QVC_ERR_BAD_ARG;
-  Plan P; Workspace W;
-  int st = check_common(cfg, blob_dev, batch, frames, workspace, workspace_bytes, P, W);
-  if (st != QVC_OK) return st;
-  HipBackend be; be.stream = be.stream0 = static_cast<hipStream_t>(stream);
-  Ctx c{P, static_cast<const char*>(blob_dev), static_cast<char*>(workspace), W, batch, frames, be};
-  c.enc_p(unit, noise, z_p_fm);
-  return c.status;
+  HipBackend be(stream);
+  return run_path(be, false, unit && noise && z_p_fm, cfg, blob_dev, batch, frames, workspace, workspace_bytes,
+                  [&](Ctx& c) { c.enc_p(unit, noise, z_p_fm); });
 }
 
 int qvc_wn_stack(const qvc_config* cfg, const void* blob_dev, int32_t which, const float* x_fm, const float* g,
                  float* out_fm, int32_t batch, int32_t frames, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!x_fm || !out_fm || which < 0 || (which > 0 && !g)) return QVC_ERR_BAD_ARG;
-  Plan P; Workspace W;
-  int st = check_common(cfg, blob_dev, batch, frames, workspace, workspace_bytes, P, W);
-  if (st != QVC_OK) return st;
-  if (which > cfg->n_flows) return QVC_ERR_BAD_ARG;
-  HipBackend be; be.stream = be.stream0 = static_cast<hipStream_t>(stream);
-  Ctx c{P, static_cast<const char*>(blob_dev), static_cast<char*>(workspace), W, batch, frames, be};
-  const size_t bytes = (size_t)batch * frames * cfg->hidden_channels * 4;
-  if (hipMemcpyAsync(c.wsp<float>(W.xw), x_fm, bytes, hipMemcpyDeviceToDevice, be.stream) != hipSuccess) return QVC_ERR_LAUNCH;
-  if (which == 0) {
-    c.wn(P.enc_wn, reinterpret_cast<const float*>(static_cast<const char*>(blob_dev) + P.enc_wn.inbias_off), 0);
-  } else {
+  HipBackend be(stream);
+  return run_path(be, false, x_fm && out_fm && which >= 0 && (which == 0 || g), cfg, blob_dev, batch, frames, workspace, workspace_bytes, [&](Ctx& c) {
+    const Plan& P = c.P;
     const FlowStepPlan* f = nullptr;
     for (const FlowStepPlan& s : P.flow) if (s.layer == which - 1) f = &s;
-    if (!f) return QVC_ERR_BAD_ARG;
-    c.cond_table(g);
-    c.wn(f->wn, c.wsp<float>(W.bb) + f->cond_row0, P.cond_rows);
-  }
-  if (c.status != QVC_OK) return c.status;
-  if (hipMemcpyAsync(out_fm, c.wsp<float>(W.oacc), bytes, hipMemcpyDeviceToDevice, be.stream) != hipSuccess) return QVC_ERR_LAUNCH;
-  return QVC_OK;
+    if (which > cfg->n_flows || (which > 0 && !f)) { c.status = QVC_ERR_BAD_ARG; return; }
+    const size_t bytes = (size_t)batch * frames * cfg->hidden_channels * 4;
+    if (hipMemcpyAsync(c.wsp<float>(c.W.xw), x_fm, bytes, hipMemcpyDeviceToDevice, be.stream) != hipSuccess) { c.status = QVC_ERR_LAUNCH; return; }
+    if (which == 0) {
+      c.wn(P.enc_wn, reinterpret_cast<const float*>(c.blob + P.enc_wn.inbias_off), 0);
+    } else {
+      c.cond_table(g);
+      c.wn(f->wn, c.wsp<float>(c.W.bb) + f->cond_row0, P.cond_rows);
+    }
+    if (c.status == QVC_OK && hipMemcpyAsync(out_fm, c.wsp<float>(c.W.oacc), bytes, hipMemcpyDeviceToDevice, be.stream) != hipSuccess) c.status = QVC_ERR_LAUNCH;
+  });
 }
 
 int qvc_flow_reverse(const qvc_config* cfg, const void* blob_dev, float* z_fm, const float* g, int32_t batch,
                      int32_t frames, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!z_fm || !g) return QVC_ERR_BAD_ARG;
-  Plan P; Workspace W;
-  int st = check_common(cfg, blob_dev, batch, frames, workspace, workspace_bytes, P, W);
-  if (st != QVC_OK) return st;
-  HipBackend be; be.stream = be.stream0 = static_cast<hipStream_t>(stream);
-  Ctx c{P, static_cast<const char*>(blob_dev), static_cast<char*>(workspace), W, batch, frames, be};
-  c.cond_table(g);
-  c.flow(z_fm);
-  return c.status;
+  HipBackend be(stream);
+  return run_path(be, false, z_fm && g, cfg, blob_dev, batch, frames, workspace, workspace_bytes,
+                  [&](Ctx& c) { c.cond_table(g); c.flow(z_fm); });
 }
 
 int qvc_flow_forward(const qvc_config* cfg, const void* blob_dev, float* z_fm, const float* g, int32_t batch,
                      int32_t frames, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!z_fm || !g) return QVC_ERR_BAD_ARG;
-  Plan P; Workspace W;
-  int st = check_common(cfg, blob_dev, batch, frames, workspace, workspace_bytes, P, W);
-  if (st != QVC_OK) return st;
-  HipBackend be; be.stream = be.stream0 = static_cast<hipStream_t>(stream);
-  Ctx c{P, static_cast<const char*>(blob_dev), static_cast<char*>(workspace), W, batch, frames, be};
-  window_from_switch(c);
-  c.cond_table(g);
-  c.flow(z_fm, /*forward=*/true);
-  record_steps(c);
-  return c.status;
+  HipBackend be(stream);
+  return run_path(be, true, z_fm && g, cfg, blob_dev, batch, frames, workspace, workspace_bytes,
+                  [&](Ctx& c) { c.cond_table(g); c.flow(z_fm, /*forward=*/true); });
 }
 
 int qvc_enc_q(const qvc_config* cfg, const void* encq_blob_dev, const float* spec, const float* g, const float* noise,
               float* z_fm, int32_t batch, int32_t frames, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!spec || !g || !noise || !z_fm) return QVC_ERR_BAD_ARG;
-  Plan P; Workspace W;
-  int st = check_common(cfg, encq_blob_dev, batch, frames, workspace, workspace_bytes, P, W);
-  if (st != QVC_OK) return st;
-  const EncQPlan Q = build_encq_plan(*cfg);
-  if (Q.status != QVC_OK) return Q.status;
-  HipBackend be; be.stream = be.stream0 = static_cast<hipStream_t>(stream);
-  Ctx c{P, static_cast<const char*>(encq_blob_dev), static_cast<char*>(workspace), W, batch, frames, be};
-  window_from_switch(c);
-  c.enc_q(Q, static_cast<const char*>(encq_blob_dev), spec, g, noise, z_fm);
-  record_steps(c);
-  return c.status;
+  HipBackend be(stream);
+  return run_path(be, true, spec && g && noise && z_fm, cfg, encq_blob_dev, batch, frames, workspace, workspace_bytes, [&](Ctx& c) {
+    const EncQPlan Q = build_encq_plan(*cfg);
+    if (Q.status != QVC_OK) c.status = Q.status;
+    else c.enc_q(Q, c.blob, spec, g, noise, z_fm);
+  });
 }
 
 int qvc_dec_trunk(const qvc_config* cfg, const void* blob_dev, const float* z_fm, const float* g, float* post_fm,
                   int32_t batch, int32_t frames, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!z_fm || !g || !post_fm) return QVC_ERR_BAD_ARG;
-  Plan P; Workspace W;
-  int st = check_common(cfg, blob_dev, batch, frames, workspace, workspace_bytes, P, W);
-  if (st != QVC_OK) return st;
-  HipBackend be; be.stream = be.stream0 = static_cast<hipStream_t>(stream);
-  Ctx c{P, static_cast<const char*>(blob_dev), static_cast<char*>(workspace), W, batch, frames, be};
-  c.cond_table(g);
-  c.dec_trunk(z_fm, post_fm);
-  return c.status;
+  HipBackend be(stream);
+  return run_path(be, false, z_fm && g && post_fm, cfg, blob_dev, batch, frames, workspace, workspace_bytes,
+                  [&](Ctx& c) { c.cond_table(g); c.dec_trunk(z_fm, post_fm); });
 }
 
 int qvc_istft_synth(const qvc_config* cfg, const void* blob_dev, const float* post_fm, float* out, float* y_mb,

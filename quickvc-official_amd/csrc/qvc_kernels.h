@@ -82,6 +82,12 @@ struct ConvArgs {
   int32_t lp = 0;          // ConvDesc::lp (lane-packed rows): EPI_STD with only a y16 output (the polyphase up-samplers)
   Ragged rg;               // per-utterance INPUT length (in T_in units); see Ragged
 };
+// The geometry fields of a conv launch, from its descriptor (the one place that copies them).
+inline void conv_geometry(ConvArgs& a, const ConvDesc& d) {
+  a.Cin = d.Cin; a.CinP = d.CinP; a.taps = d.taps; a.dil = d.dil; a.left = d.left;
+  a.KS = d.KS(); a.nIt = d.nIt(); a.nchunk = d.nchunk; a.M = d.M;
+  a.up_s = d.up_s; a.up_p = d.up_p; a.Cout = d.Cout; a.lp = d.lp; a.ksize = d.ksize;
+}
 
 // Arguments of one fused ResBlock1 pair (modules.py:148-153):  y = x + conv2(lrelu(conv1(lrelu(x)))).
 // x / y are frame-major tensors in the operand type (the MRF mean of the three ResBlocks, models.py:378-384,
@@ -245,6 +251,26 @@ inline int post_tail_bands(const ConvDesc& d) {
 }
 inline bool post_tail_supported(const ConvDesc& d) { return post_tail_bands(d) != 0; }
 
+// Layout decisions of the plan for `cfg` (qvc_plan_info, include/qvc.h; the emulation exports the same as a test hook):
+// out[0] enc_p.proj rows paired [mu | log sigma] (sampling in the epilogue), out[1] its fragments per wave,
+// out[2..3] up-samplers 0 / 1 lane-packed, out[4] conv_post + tail can run as one launch,
+// out[5..6] waves per workgroup of the stage 0 / 1 ResBlock pairs, out[7] all pairs fusable
+inline int plan_flags(const qvc_config* cfg, int32_t out[8]) {
+  if (!cfg || !out) return QVC_ERR_BAD_ARG;
+  const Plan P = build_plan(*cfg);
+  if (P.status != QVC_OK) return P.status;
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  out[0] = P.enc_proj.gau; out[1] = P.enc_proj.MF;
+  for (size_t i = 0; i < P.stages.size() && i < 2; ++i) {
+    out[2 + i] = P.stages[i].up.lp;
+    out[5 + i] = block_waves(P.stages[i].c1[0]);
+  }
+  out[4] = post_tail_supported(P.conv_post) ? 1 : 0;
+  out[7] = 1;
+  for (const StagePlan& st : P.stages) out[7] = out[7] && pairs_fusable(P.cfg, st);
+  return QVC_OK;
+}
+
 // One LSTM layer's recurrence over all partials (models.py:510,516): gates = xp[t] + W_hh h[t-1], PyTorch gate
 // order i,f,g,o.  The input projection xp (with b_ih + b_hh) comes from a conv launch.
 struct LstmArgs {
@@ -295,7 +321,6 @@ inline std::atomic<int32_t>& debug_launch_steps() {
 
 // Launchers return a QVC_* status.  `stream` is a hipStream_t.
 int launch_conv(const ConvDesc& d, ConvArgs a, int batch, int epi, int dtype, void* stream, int* nf_out = nullptr);
-int launch_pair(const ConvDesc& d1, const ConvDesc& d2, PairArgs a, int batch, int dtype, void* stream, int* nf_out = nullptr);
 // n pairs (1..3) of equal shape class in one launch; d1[i] / d2[i] are chain i's convs
 int launch_pair3(const ConvDesc* d1, const ConvDesc* d2, const PairArgs3& a, int batch, int dtype, void* stream, int* nf_out = nullptr);
 // the n pairs of one ResBlock chained in one launch (chain_supported() says when); d1[q] / d2[q] are pair q's convs

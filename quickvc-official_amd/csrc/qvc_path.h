@@ -7,36 +7,37 @@
 // emulation.
 //
 // A backend provides:  int conv(const ConvDesc&, const ConvArgs&, int batch, int epi, int dtype);
-//                      int pair(const ConvDesc&, const ConvDesc&, const PairArgs&, int batch, int dtype);
 //                      int pair3(const ConvDesc* d1, const ConvDesc* d2, const PairArgs3&, int batch, int dtype);
+//                      bool chain_ok(const ConvDesc* d1, const ConvDesc* d2, int n);
+//                      int chain(const ConvDesc* d1, const ConvDesc* d2, const ChainArgs&, int batch, int dtype);
 //                      int wn(const ConvDesc& in, const ConvDesc& rs, const WnArgs&, int batch, int dtype);
-//                      int gemv(const GemvArgs&); int sample(const SampleArgs&);
-//                      int tail(const TailArgs&); int zero(void* ptr, size_t bytes);
-//                      optional, the single-band decoder (QVC_DEC_ISTFT):  int tail1(const TailArgs&);
-//                      int post_tail1(const ConvDesc&, const PostTailArgs&, int batch, int dtype) -- a backend without
-//                      them (has_single_band_tail) returns QVC_ERR_BAD_CONFIG for that decoder
-//                      void fork(int n); void branch(int j); void branch_done(int j);
-//                      void wait_branch_done(int j); void join(int n);   (stream fork/join; no-ops on one stream)
+//                      int wn_stack_chunk(int layers);   (layers per whole-stack launch, 0 = one launch per layer)
+//                      int wn_stack(const ConvDesc& in, const ConvDesc& rs, const ConvDesc& rs_last, const WnStackArgs&,
+//                                   int batch, int dtype, const ConvDesc* pre, const ConvDesc* post);
+//                      int gemv(const GemvArgs&); int sample(const SampleArgs&); int zero(void* ptr, size_t bytes);
+//                      int tail(const TailArgs&); bool post_tail_ok(const ConvDesc&);
+//                      int post_tail(const ConvDesc&, const PostTailArgs&, int batch, int dtype);
+//                      optional:  static constexpr bool kSingleBandTail = true -- tail (TailArgs::bands == 1) and
+//                      post_tail (post_tail_bands(d) == 1) run the single-band decoder (QVC_DEC_ISTFT).  A backend that
+//                      does not say so gets QVC_ERR_BAD_CONFIG from the path for that decoder
+//                      void fork(int n); void branch(int j); void branch_done(int j); void join(int n);
+//                      (stream fork/join; no-ops on one stream)
 #pragma once
 #include <algorithm>
 #include <climits>
 #include <cstdlib>
 #include <type_traits>
-#include <utility>
 #include "qvc_kernels.h"
 
 namespace qvc {
 
-// Does a backend run the single-band tail (tail1 / post_tail1)?  Detected at compile time, so that a backend written
-// before the single-band decoder existed keeps building and refuses that decoder instead of running the four-band tail.
-template <class B, class = void> struct has_single_band_tail : std::false_type {};
-template <class B>
-struct has_single_band_tail<B, std::void_t<decltype(std::declval<B&>().tail1(std::declval<const TailArgs&>())),
-                                           decltype(std::declval<B&>().post_tail1(std::declval<const ConvDesc&>(),
-                                                                                  std::declval<const PostTailArgs&>(), 0, 0))>>
-    : std::true_type {};
+// Backend::kSingleBandTail, false for a backend that does not state it (one written before the single-band decoder
+// existed keeps building and refuses that decoder instead of running the four-band tail).
+template <class B, class = void> constexpr bool single_band_tail = false;
+template <class B> constexpr bool single_band_tail<B, std::void_t<decltype(B::kSingleBandTail)>> = B::kSingleBandTail;
 
 // Kinds of the steps a Path issues (one per backend call that enqueues device work), in the order they are counted.
+// (A single-band launch is counted as STEP_POST_TAIL1 / STEP_TAIL1: the same backend calls, told apart for the tests.)
 enum StepKind : int32_t {
   STEP_CONV = 0, STEP_ZERO, STEP_GEMV, STEP_SAMPLE, STEP_WN, STEP_WN_STACK, STEP_CHAIN, STEP_PAIR3, STEP_POST_TAIL,
   STEP_POST_TAIL1, STEP_TAIL, STEP_TAIL1, STEP_KINDS
@@ -87,9 +88,7 @@ struct Path {
     if (!wb) wb = blob;
     a.w = wb + d.w_off;
     a.bias = d.b_off >= 0 ? reinterpret_cast<const float*>(wb + d.b_off) : nullptr;
-    a.Cin = d.Cin; a.CinP = d.CinP; a.taps = d.taps; a.dil = d.dil; a.left = d.left;
-    a.KS = d.KS(); a.nIt = d.nIt(); a.nchunk = d.nchunk; a.M = d.M;
-    a.up_s = d.up_s; a.up_p = d.up_p; a.Cout = d.Cout;
+    conv_geometry(a, d);
     return a;
   }
   void conv(const ConvDesc& d, const ConvArgs& a, int dt, int epi = EPI_STD) {
@@ -103,12 +102,22 @@ struct Path {
     if (step(STEP_ZERO)) status = be.zero(ws + off, (size_t)bytes);
   }
 
-  // ---- conditioning table: bb[b][row] for every cond row (flow WN layers + dec.cond)
-  void cond_table(const float* g) {
+  // ---- conditioning table: bb[b][row] for every cond row (flow WN layers + dec.cond; enc_q: its WN layers, own blob)
+  void cond_table(const float* g) { cond_table(blob, P.cond_w_off, P.cond_b_off, P.cond_rows, g); }
+  void cond_table(const char* wb, int64_t w_off, int64_t b_off, int rows, const float* g) {
     if (status != QVC_OK) return;
-    GemvArgs ga{reinterpret_cast<const float*>(blob + P.cond_w_off), reinterpret_cast<const float*>(blob + P.cond_b_off),
-                g, wsp<float>(W.bb), P.cond_rows, P.cfg.gin_channels, B};
+    GemvArgs ga{reinterpret_cast<const float*>(wb + w_off), reinterpret_cast<const float*>(wb + b_off),
+                g, wsp<float>(W.bb), rows, P.cfg.gin_channels, B};
     if (step(STEP_GEMV)) status = be.gemv(ga);
+  }
+
+  // ---- the whole conversion path: unit frames, speaker embedding, noise -> waveform (every backend's whole-path
+  // entry points call this, so they issue the same steps)
+  void infer(const float* unit, const float* g, const float* noise, float* out) {
+    cond_table(g);
+    enc_p(unit, noise, wsp<float>(W.z));
+    flow(wsp<float>(W.z));
+    dec_trunk_wave(wsp<float>(W.z), wsp<float>(W.post), out);
   }
 
   // ---- WN stack over xw (in place) accumulating into oacc (modules.py:69-114)
@@ -120,7 +129,7 @@ struct Path {
     // Whole-stack kernel, in launches of `chunk` layers: fewer layers per launch = less halo to recompute
     // (4 layers: 48-frame window for 32 output frames; 16 layers: 96), more launches = more x round trips.
     const int chunk = be.wn_stack_chunk(wn.layers);
-    if (chunk > 0 && wn.layers % chunk == 0 && wn_stack_ok(wn.in_conv[0], chunk) && be.use_wn_stack(B, T)) {
+    if (chunk > 0 && wn.layers % chunk == 0 && wn_stack_ok(wn.in_conv[0], chunk)) {
       for (int l0 = 0; l0 < wn.layers; l0 += chunk) {
         const int part = l0 / chunk;
         WnStackArgs a;
@@ -158,30 +167,40 @@ struct Path {
     }
   }
 
-  // ---- enc_p (models.py:75-95)
-  void enc_p(const float* unit, const float* noise, float* z_out) {
-    const qvc_config& c = P.cfg;
-    const int H = c.hidden_channels, C = c.inter_channels;
+  // ---- enc_p (models.py:75-95) and enc_q (the same with cond = g, :582,617; own plan and blob): x, noise -> z.
+  // x: Cx channels, frame- or channel-major; wb: the blob the three descriptors point into; bb / bb_bs: see wn
+  void enc(const ConvDesc& pre, const WNPlan& w, const ConvDesc& proj, const char* wb, const float* x, int Cx, bool x_fm,
+           const float* bb, int64_t bb_bs, const float* noise, float* z_out) {
+    const int H = P.cfg.hidden_channels, C = P.cfg.inter_channels;
     {
-      ConvArgs a = args(P.enc_pre);
-      a.x = unit; a.x_bs = (int64_t)c.unit_channels * T; a.T_in = T;
-      if (unit_fm) { a.x_kind = XK_F32_FM; a.x_ts = c.unit_channels; } else { a.x_kind = XK_F32_CM; a.x_ts = T; }
+      ConvArgs a = args(pre, wb);
+      a.x = x; a.x_bs = (int64_t)Cx * T; a.T_in = T;
+      if (x_fm) { a.x_kind = XK_F32_FM; a.x_ts = Cx; } else { a.x_kind = XK_F32_CM; a.x_ts = T; }
       a.Nq = T; a.T_out = T; a.rg = rg(1);
       a.y32 = wsp<float>(W.xw); a.y32_bs = (int64_t)T * H; a.y32_ts = H;
-      conv(P.enc_pre, a, dtype_wn());
+      conv(pre, a, dtype_wn());
     }
-    wn(P.enc_wn, reinterpret_cast<const float*>(blob + P.enc_wn.inbias_off), 0);
+    wn(w, bb, bb_bs, wb);
     {
-      ConvArgs a = args(P.enc_proj);
+      ConvArgs a = args(proj, wb);
       a.x = wsp<float>(W.oacc); a.x_kind = XK_F32_FM; a.x_bs = (int64_t)T * H; a.x_ts = H; a.T_in = T;
       a.Nq = T; a.T_out = T; a.rg = rg(1);
-      if (proj_and_sample(P.enc_proj, a, noise, z_out)) return;
+      if (proj_and_sample(proj, a, noise, z_out)) return;
       a.y32 = wsp<float>(W.stats); a.y32_bs = (int64_t)T * 2 * C; a.y32_ts = 2 * C;
-      conv(P.enc_proj, a, dtype_wn());
+      conv(proj, a, dtype_wn());
     }
     if (status != QVC_OK) return;
     SampleArgs sa{wsp<float>(W.stats), noise, z_out, B, T, C};
     if (step(STEP_SAMPLE)) status = be.sample(sa);
+  }
+  void enc_p(const float* unit, const float* noise, float* z_out) {
+    enc(P.enc_pre, P.enc_wn, P.enc_proj, blob, unit, P.cfg.unit_channels, unit_fm,
+        reinterpret_cast<const float*>(blob + P.enc_wn.inbias_off), 0, noise, z_out);
+  }
+  // the conditioning GEMV (cond_layer on g + in_layer biases: enc_q's own table) comes first
+  void enc_q(const EncQPlan& Q, const char* qblob, const float* spec, const float* g, const float* noise, float* z_out) {
+    cond_table(qblob, Q.cond_w_off, Q.cond_b_off, Q.cond_rows, g);
+    enc(Q.pre, Q.wn, Q.proj, qblob, spec, Q.spec_channels, false, wsp<float>(W.bb), Q.cond_rows, noise, z_out);
   }
   // proj packed with paired [mu | log sigma] rows (make_proj): z = mu + noise * exp(log sigma) in the conv epilogue
   bool proj_and_sample(const ConvDesc& d, ConvArgs& a, const float* noise, float* z_out) {
@@ -191,35 +210,6 @@ struct Path {
     a.y32 = z_out; a.y32_bs = (int64_t)T * C; a.y32_ts = C;
     conv(d, a, dtype_wn(), EPI_SAMPLE);
     return true;
-  }
-
-  // ---- enc_q (models.py:75-95 with cond = g, :582,617): spec, g, noise -> z
-  void enc_q(const EncQPlan& Q, const char* qblob, const float* spec, const float* g, const float* noise, float* z_out) {
-    const qvc_config& c = P.cfg;
-    const int H = c.hidden_channels, C = c.inter_channels;
-    if (status != QVC_OK) return;
-    GemvArgs ga{reinterpret_cast<const float*>(qblob + Q.cond_w_off), reinterpret_cast<const float*>(qblob + Q.cond_b_off),
-                g, wsp<float>(W.bb), Q.cond_rows, c.gin_channels, B};
-    if (step(STEP_GEMV)) status = be.gemv(ga);
-    {
-      ConvArgs a = args(Q.pre, qblob);
-      a.x = spec; a.x_kind = XK_F32_CM; a.x_bs = (int64_t)Q.spec_channels * T; a.x_ts = T; a.T_in = T;
-      a.Nq = T; a.T_out = T; a.rg = rg(1);
-      a.y32 = wsp<float>(W.xw); a.y32_bs = (int64_t)T * H; a.y32_ts = H;
-      conv(Q.pre, a, dtype_wn());
-    }
-    wn(Q.wn, wsp<float>(W.bb), Q.cond_rows, qblob);
-    {
-      ConvArgs a = args(Q.proj, qblob);
-      a.x = wsp<float>(W.oacc); a.x_kind = XK_F32_FM; a.x_bs = (int64_t)T * H; a.x_ts = H; a.T_in = T;
-      a.Nq = T; a.T_out = T; a.rg = rg(1);
-      if (proj_and_sample(Q.proj, a, noise, z_out)) return;
-      a.y32 = wsp<float>(W.stats); a.y32_bs = (int64_t)T * 2 * C; a.y32_ts = 2 * C;
-      conv(Q.proj, a, dtype_wn());
-    }
-    if (status != QVC_OK) return;
-    SampleArgs sa{wsp<float>(W.stats), noise, z_out, B, T, C};
-    if (step(STEP_SAMPLE)) status = be.sample(sa);
   }
 
   // ---- flow (models.py:39-51, modules.py:199-224); z updated in place.  reverse (the conversion path): the plan's
@@ -237,7 +227,7 @@ struct Path {
     const float* bb = wsp<float>(W.bb);
     {
       const ConvDesc& din = f.wn.in_conv[0];
-      if (f.wn.layers == be.wn_stack_chunk(f.wn.layers) && wn_fuse_ok(din, f.pre, f.post, f.wn.layers) && be.use_wn_stack(B, T)) {
+      if (f.wn.layers == be.wn_stack_chunk(f.wn.layers) && wn_fuse_ok(din, f.pre, f.post, f.wn.layers)) {
         // the whole coupling layer in ONE launch: pre 1x1 -> 4 WaveNet layers -> post 1x1 -> x1 -= m
         WnStackArgs a;
         a.bs = (int64_t)T * H; a.T = T; a.H = H; a.HP = din.CinP;
@@ -300,7 +290,7 @@ struct Path {
   bool single_band() const { return P.cfg.decoder == QVC_DEC_ISTFT; }
   void dec_part(const float* z, float* post_out, int stage_lo, int stage_hi, bool with_pre, bool with_post, float* wave = nullptr) {
     const qvc_config& c = P.cfg;
-    if (wave && single_band() && !has_single_band_tail<Backend>::value) status = QVC_ERR_BAD_CONFIG;
+    if (wave && single_band() && !single_band_tail<Backend>) status = QVC_ERR_BAD_CONFIG;
     const int C = c.inter_channels, C0 = c.upsample_initial_channel;
     if (with_pre) {   // conv_pre(k7) + cond(g), then the first stage's leaky ReLU fused into the store
       ConvArgs a = args(P.conv_pre);
@@ -349,13 +339,7 @@ struct Path {
         pa.y = dst;
         return pa;
       };
-      bool fused = NB <= 3;
-      for (int j = 0; j < NB && fused; ++j)
-        for (int q = 0; q < 3; ++q) {
-          const ConvDesc& d1 = st.c1[(size_t)j * 3 + q];
-          const ConvDesc& d2 = st.c2[(size_t)j * 3 + q];
-          fused = fused && pair_supported(d1, d2) && d1.lp && d2.lp && d1.MF == st.c1[0].MF && d1.WM == st.c1[0].WM;
-        }
+      const bool fused = pairs_fusable(c, st);
       // One launch for the three chains, chain-major grid (blockIdx.z = chain, longest kernel first): the dispatcher
       // hands out all workgroups of the k 11 chain first and the shorter chains backfill the CUs as they free up --
       // longest-processing-time-first, so the launch ends on short workgroups.  Interleaving the chains on the CUs
@@ -462,8 +446,7 @@ struct Path {
         PostTailArgs pt;
         pt.c = a; pt.fir = single_band() ? nullptr : reinterpret_cast<const float*>(blob + P.fir_off); pt.out = wave; pt.F = t_in + 1;
         pt.rg = rg(P.total_up, 1);
-        if (!single_band()) { if (step(STEP_POST_TAIL)) status = be.post_tail(P.conv_post, pt, B, dtype_dec()); }
-        else if constexpr (has_single_band_tail<Backend>::value) { if (step(STEP_POST_TAIL1)) status = be.post_tail1(P.conv_post, pt, B, dtype_dec()); }
+        if (step(single_band() ? STEP_POST_TAIL1 : STEP_POST_TAIL)) status = be.post_tail(P.conv_post, pt, B, dtype_dec());
         return;
       }
       a.y32 = post_out; a.y32_bs = (int64_t)(t_in + 1) * P.post_channels; a.y32_ts = P.post_channels;
@@ -473,13 +456,12 @@ struct Path {
   }
 
   void tail(const float* post, float* out, float* y_mb, int F) {
+    if (status == QVC_OK && single_band() && !single_band_tail<Backend>) status = QVC_ERR_BAD_CONFIG;
     if (status != QVC_OK) return;
     TailArgs ta{post, reinterpret_cast<const float*>(blob + P.fir_off), out, y_mb, B, F};
     ta.rg = rg(P.total_up, 1);
-    if (!single_band()) { if (step(STEP_TAIL)) status = be.tail(ta); return; }
-    ta.fir = nullptr; ta.bands = 1;
-    if constexpr (has_single_band_tail<Backend>::value) { if (step(STEP_TAIL1)) status = be.tail1(ta); }
-    else status = QVC_ERR_BAD_CONFIG;
+    if (single_band()) { ta.fir = nullptr; ta.bands = 1; }
+    if (step(single_band() ? STEP_TAIL1 : STEP_TAIL)) status = be.tail(ta);
   }
 };
 
@@ -494,8 +476,7 @@ int spk_path(const SpkPlan& S, int dtype, const char* blob, char* ws, const SpkW
     const ConvDesc& d = S.ih[l];
     ConvArgs ca;
     ca.w = blob + d.w_off; ca.bias = reinterpret_cast<const float*>(blob + d.b_off);
-    ca.Cin = d.Cin; ca.CinP = d.CinP; ca.taps = 1; ca.dil = 1; ca.left = 0;
-    ca.KS = d.KS(); ca.nIt = d.nIt(); ca.nchunk = d.nchunk; ca.M = d.M; ca.up_s = 1; ca.up_p = 0; ca.Cout = d.Cout;
+    conv_geometry(ca, d);     // a 1x1 conv (make_conv(4H, Cin, 1, 1))
     int batch;
     if (l == 0) {     // mel (U, n_mel, F) as handed to infer() (convert.py:77); the transpose of models.py:635 is the staging
       ca.x = mel; ca.x_kind = XK_F32_CM; ca.x_bs = (int64_t)S.n_mel * F; ca.x_ts = F; ca.T_in = F;

@@ -188,6 +188,13 @@ struct StagePlan {
   int32_t ch = 0;                 // channels of this stage
   int32_t rate = 1;
 };
+// Can every ResBlock pair of the stage run fused, the chains sharing launches?  (else: one launch per conv)
+inline bool pairs_fusable(const qvc_config& c, const StagePlan& st) {
+  bool ok = c.n_resblocks <= 3;
+  for (size_t j = 0; j < st.c1.size() && ok; ++j)
+    ok = pair_supported(st.c1[j], st.c2[j]) && st.c1[j].lp && st.c2[j].lp && st.c1[j].MF == st.c1[0].MF && st.c1[j].WM == st.c1[0].WM;
+  return ok;
+}
 
 struct Plan {
   qvc_config cfg{};

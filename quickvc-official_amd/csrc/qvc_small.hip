@@ -351,9 +351,7 @@ int launch_copy_batch(const CopyDesc* d, int n, void* stream) {
 
 // ------------------------------------------------------------------ conv dispatcher
 int launch_conv(const ConvDesc& d, ConvArgs a, int batch, int epi, int dtype, void* stream, int* nf_out) {
-  a.Cin = d.Cin; a.CinP = d.CinP; a.taps = d.taps; a.dil = d.dil; a.left = d.left;
-  a.KS = d.KS(); a.nIt = d.nIt(); a.nchunk = d.nchunk; a.M = d.M;
-  a.up_s = d.up_s; a.up_p = d.up_p; a.Cout = d.Cout; a.lp = d.lp; a.ksize = d.ksize;
+  conv_geometry(a, d);
   if (d.lp && (epi != EPI_STD || !a.y16 || a.y32 || a.y32b || a.res || a.res16 || d.MF % 2)) return QVC_ERR_BAD_CONFIG;
   if (dtype == QVC_F16) return launch_conv_typed<_Float16>(d, a, batch, epi, stream, nf_out);
   if (dtype == QVC_BF16) return launch_conv_typed<__bf16>(d, a, batch, epi, stream, nf_out);
@@ -361,9 +359,7 @@ int launch_conv(const ConvDesc& d, ConvArgs a, int batch, int epi, int dtype, vo
 }
 
 int launch_post_tail(const ConvDesc& d, PostTailArgs a, int batch, int dtype, void* stream) {
-  a.c.Cin = d.Cin; a.c.CinP = d.CinP; a.c.taps = d.taps; a.c.dil = d.dil; a.c.left = d.left;
-  a.c.KS = d.KS(); a.c.nIt = d.nIt(); a.c.nchunk = d.nchunk; a.c.M = d.M;
-  a.c.up_s = d.up_s; a.c.up_p = d.up_p; a.c.Cout = d.Cout;
+  conv_geometry(a.c, d);
   if (dtype == QVC_F16) return launch_post_tail_typed<_Float16>(d, a, batch, stream);
   if (dtype == QVC_BF16) return launch_post_tail_typed<__bf16>(d, a, batch, stream);
   return QVC_ERR_BAD_ARG;
@@ -426,11 +422,6 @@ int launch_chain(const ConvDesc* d1, const ConvDesc* d2, const ChainArgs& a, int
   if (dtype == QVC_BF16) return launch_chain_typed<__bf16, __bf16>(d1, d2, a, batch, stream, nf_out);
   if (dtype == QVC_BF16X) return launch_chain_typed<__bf16, _Float16>(d1, d2, a, batch, stream, nf_out);
   return QVC_ERR_BAD_ARG;
-}
-
-int launch_pair(const ConvDesc& d1, const ConvDesc& d2, PairArgs a, int batch, int dtype, void* stream, int* nf_out) {
-  PairArgs3 a3; a3.p[0] = a; a3.n = 1;
-  return launch_pair3(&d1, &d2, a3, batch, dtype, stream, nf_out);
 }
 
 }  // namespace qvc

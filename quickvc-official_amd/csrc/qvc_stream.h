@@ -61,6 +61,14 @@ inline StreamGeom stream_geom(const Plan& P, int hop) {
   return G;
 }
 
+// What every streaming entry point starts from: the plan and the stream geometry for (cfg, hop), or why not.
+inline int stream_plan(const qvc_config* cfg, int hop, Plan& P, StreamGeom& G) {
+  if (!cfg || hop <= 0) return QVC_ERR_BAD_ARG;
+  P = build_plan(*cfg);
+  G = stream_geom(P, hop);
+  return G.status;
+}
+
 struct StreamState {     // byte offsets into the caller-owned state buffer
   int64_t unit = 0;      // fp32 (B, unit_channels, 2*He + hop), the reference's (B, C, T) layout
   int64_t zf[16] = {};   // fp32 [B][2*Hf + hop][C]: z in front of coupling layer k

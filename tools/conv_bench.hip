@@ -256,10 +256,11 @@ int main(int argc, char** argv) {
         a.k = ks[c]; a.dil = dils[q]; a.KS = d1.KS(); a.nIt = d1.nIt(); a.y = (char*)y16 + c * slice * 2;
         d1s[c] = d1; d2s[c] = d2; a3.p[c] = a;
         int nf = 0;
-        for (int i = 0; i < 3; ++i) if (launch_pair(d1, d2, a, B, QVC_F16, st, &nf) != QVC_OK) { printf("%s: launch failed\n", sg.name); break; }
+        PairArgs3 a1; a1.p[0] = a;                     // the chain alone: a launch of one pair
+        for (int i = 0; i < 3; ++i) if (launch_pair3(&d1, &d2, a1, B, QVC_F16, st, &nf) != QVC_OK) { printf("%s: launch failed\n", sg.name); break; }
         CK(hipStreamSynchronize(st));
         CK(hipEventRecord(e0, st));
-        for (int i = 0; i < reps; ++i) launch_pair(d1, d2, a, B, QVC_F16, st, &nf);
+        for (int i = 0; i < reps; ++i) launch_pair3(&d1, &d2, a1, B, QVC_F16, st, &nf);
         CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));
         const double us = ms * 1e3 / reps;
