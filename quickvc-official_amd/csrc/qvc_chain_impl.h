@@ -49,45 +49,14 @@ __global__ __launch_bounds__(NWV * 64) void rbchain_kernel(const ChainArgs A) {
     for (int i = tid; i < 2 * mrg * cpr; i += NTHR) {
       const int r = i / cpr, c8 = i - r * cpr;
       const int row = r < mrg ? r : ROWS + r;
-      *reinterpret_cast<uint4*>(act + row * rowbytes + ((rotc(c8, sm) ^ swz(row, sm)) << 4)) = make_uint4(0u, 0u, 0u, 0u);
+      *reinterpret_cast<uint4*>(tile_at(act, row, c8, rowbytes, sm)) = make_uint4(0u, 0u, 0u, 0u);
     }
-    const int total = ROWS * cpr;
-    constexpr int kU = 16;
-    const int rstep = NTHR / cpr, cstep = NTHR - rstep * cpr;
-    for (int base = tid; base < total; base += NTHR * kU) {
-      uint4 v[kU];
-      const int r_0 = base / cpr, c_0 = base - r_0 * cpr;
-      int r = r_0, c8 = c_0;
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        const int idx = base + u * NTHR;
-        const int ti = F0 + r;
-        v[u] = make_uint4(0u, 0u, 0u, 0u);
-        if (idx < total && ti >= Tlo && ti < Tb && c8 * 8 < C) v[u] = *reinterpret_cast<const uint4*>(xb + (size_t)ti * C + c8 * 8);
-        c8 += cstep; r += rstep;
-        if (c8 >= cpr) { c8 -= cpr; ++r; }
-      }
-      r = r_0; c8 = c_0;
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        const int idx = base + u * NTHR;
-        if (idx < total) {
-          frag o;
-          if constexpr (std::is_same<T, TS>::value) {
-            frag h; __builtin_memcpy(&h, &v[u], 16);
-            o = lrelu8<T>(h, a0.slope);
-          } else {
-            sfrag h; __builtin_memcpy(&h, &v[u], 16);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = O::cvt(lrelu((float)h[e], a0.slope));
-          }
-          *reinterpret_cast<uint4*>(raw + r * rowbytes + ((rotc(c8, sm) ^ swz(r, sm)) << 4)) = v[u];
-          *reinterpret_cast<frag*>(act + (mrg + r) * rowbytes + ((rotc(c8, sm) ^ swz(mrg + r, sm)) << 4)) = o;
-        }
-        c8 += cstep; r += rstep;
-        if (c8 >= cpr) { c8 -= cpr; ++r; }
-      }
-    }
+    stage_stream_tile<T, TS, NTHR>(xb, C, cpr, ROWS * cpr, F0, Tlo, Tb, a0.slope, tid,
+        [&](int r, int c8, const uint4& x, frag o) {
+          *reinterpret_cast<uint4*>(tile_at(raw, r, c8, rowbytes, sm)) = x;
+          *reinterpret_cast<frag*>(tile_at(act, mrg + r, c8, rowbytes, sm)) = o;
+        },
+        [](bool) {});
   }
   __syncthreads();
 
@@ -99,12 +68,9 @@ __global__ __launch_bounds__(NWV * 64) void rbchain_kernel(const ChainArgs A) {
     const bool last = q == A.n - 1;
     f32x4 acc[MF][NF];
     {   // ---- GEMM1 (dilation d_q) over the whole tile, bias + lrelu -> the operand tile, in place
-#pragma unroll
-      for (int m = 0; m < MF; ++m)
-#pragma unroll
-        for (int n = 0; n < NF; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+      QVC_ZERO_ACC(acc);
       const frag* ap = static_cast<const frag*>(a.w1) + ((size_t)wm * a.nIt * MF) * 64 + lane;
-      gemm_loop<T, MF, NF, QVC_PF_CONV>(acc, ap, a.nIt, a.KS, a.dil, act, rowbytes, sm, mrg - h1 + lrow, lq, 0);
+      gemm_loop<T, MF, NF, QVC_PF_CONV>(acc, ap, a.nIt, a.KS, a.dil, act, rowbytes, sm, mrg - h1 + lrow, lq);
       float4 bias[MF];
 #pragma unroll
       for (int m = 0; m < MF; ++m) bias[m] = *reinterpret_cast<const float4*>(a.b1 + cb + m * 4);
@@ -114,34 +80,26 @@ __global__ __launch_bounds__(NWV * 64) void rbchain_kernel(const ChainArgs A) {
         const int r = n * 16 + lrow;
         const int f = F0 + r;
         const bool inside = f >= Tlo && f < Tb;                  // conv2 zero-pads outside the utterance
-        char* rowp = act + (mrg + r) * rowbytes;
-        const int sw = swz(mrg + r, sm);
 #pragma unroll
         for (int m = 0; m < MF; m += 2) {
           const int v = cb + m * 4;
           if (v >= CP) continue;
           frag h;
           if (inside && v < C) {
-            h[0] = O::cvt(lrelu(acc[m][n][0] + bias[m].x, a.slope)); h[1] = O::cvt(lrelu(acc[m][n][1] + bias[m].y, a.slope));
-            h[2] = O::cvt(lrelu(acc[m][n][2] + bias[m].z, a.slope)); h[3] = O::cvt(lrelu(acc[m][n][3] + bias[m].w, a.slope));
-            h[4] = O::cvt(lrelu(acc[m + 1][n][0] + bias[m + 1].x, a.slope)); h[5] = O::cvt(lrelu(acc[m + 1][n][1] + bias[m + 1].y, a.slope));
-            h[6] = O::cvt(lrelu(acc[m + 1][n][2] + bias[m + 1].z, a.slope)); h[7] = O::cvt(lrelu(acc[m + 1][n][3] + bias[m + 1].w, a.slope));
+            h = pack8_lrelu<T>(acc[m][n], bias[m], acc[m + 1][n], bias[m + 1], a.slope);
           } else {
 #pragma unroll
             for (int e = 0; e < 8; ++e) h[e] = (T)0.f;
           }
-          *reinterpret_cast<frag*>(rowp + ((rotc(v >> 3, sm) ^ sw) << 4)) = h;
+          *reinterpret_cast<frag*>(tile_at(act, mrg + r, v >> 3, rowbytes, sm)) = h;
         }
       }
     }
     __syncthreads();
     {   // ---- GEMM2 (dilation 1) + bias + residual (raw tile) -> the stream: back into both tiles, or out to memory
-#pragma unroll
-      for (int m = 0; m < MF; ++m)
-#pragma unroll
-        for (int n = 0; n < NF; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+      QVC_ZERO_ACC(acc);
       const frag* ap = static_cast<const frag*>(a.w2) + ((size_t)wm * a.nIt * MF) * 64 + lane;
-      gemm_loop<T, MF, NF, QVC_PF_CONV>(acc, ap, a.nIt, a.KS, 1, act, rowbytes, sm, mrg - h2 + lrow, lq, 0);
+      gemm_loop<T, MF, NF, QVC_PF_CONV>(acc, ap, a.nIt, a.KS, 1, act, rowbytes, sm, mrg - h2 + lrow, lq);
       float4 bias[MF];
 #pragma unroll
       for (int m = 0; m < MF; ++m) bias[m] = *reinterpret_cast<const float4*>(a.b2 + cb + m * 4);
@@ -152,18 +110,12 @@ __global__ __launch_bounds__(NWV * 64) void rbchain_kernel(const ChainArgs A) {
         const int r = n * 16 + lrow;
         const int f = F0 + r;
         const bool inside = f >= Tlo && f < Tb;
-        const int swr = swz(r, sm), swa = swz(mrg + r, sm);
 #pragma unroll
         for (int m = 0; m < MF; m += 2) {
           const int v = cb + m * 4;
           if (v >= C) continue;
-          char* rp = raw + r * rowbytes + ((rotc(v >> 3, sm) ^ swr) << 4);
-          sfrag r8 = *reinterpret_cast<const sfrag*>(rp);
-          sfrag h;
-          h[0] = OS::cvt(acc[m][n][0] + bias[m].x + (float)r8[0]); h[1] = OS::cvt(acc[m][n][1] + bias[m].y + (float)r8[1]);
-          h[2] = OS::cvt(acc[m][n][2] + bias[m].z + (float)r8[2]); h[3] = OS::cvt(acc[m][n][3] + bias[m].w + (float)r8[3]);
-          h[4] = OS::cvt(acc[m + 1][n][0] + bias[m + 1].x + (float)r8[4]); h[5] = OS::cvt(acc[m + 1][n][1] + bias[m + 1].y + (float)r8[5]);
-          h[6] = OS::cvt(acc[m + 1][n][2] + bias[m + 1].z + (float)r8[6]); h[7] = OS::cvt(acc[m + 1][n][3] + bias[m + 1].w + (float)r8[7]);
+          char* rp = tile_at(raw, r, v >> 3, rowbytes, sm);
+          sfrag h = pack8_res<TS>(acc[m][n], bias[m], acc[m + 1][n], bias[m + 1], *reinterpret_cast<const sfrag*>(rp));
           if (last) {
             if (r >= A.halo && r < A.halo + A.NT && f < Tb) *reinterpret_cast<sfrag*>(yb + (size_t)f * C + v) = h;
           } else {
@@ -172,14 +124,7 @@ __global__ __launch_bounds__(NWV * 64) void rbchain_kernel(const ChainArgs A) {
               for (int e = 0; e < 8; ++e) h[e] = (TS)0.f;        // the next pair's convs zero-pad outside the utterance
             }
             *reinterpret_cast<sfrag*>(rp) = h;
-            frag o;
-            if constexpr (std::is_same<T, TS>::value) {
-              o = lrelu8<T>(h, a.slope);
-            } else {
-#pragma unroll
-              for (int e = 0; e < 8; ++e) o[e] = O::cvt(lrelu((float)h[e], a.slope));
-            }
-            *reinterpret_cast<frag*>(act + (mrg + r) * rowbytes + ((rotc(v >> 3, sm) ^ swa) << 4)) = o;
+            *reinterpret_cast<frag*>(tile_at(act, mrg + r, v >> 3, rowbytes, sm)) = act8<T, TS>(h, a.slope);
           }
         }
       }
@@ -190,12 +135,8 @@ __global__ __launch_bounds__(NWV * 64) void rbchain_kernel(const ChainArgs A) {
 
 template <typename T, int MF, int NF, int NWV, typename TS>
 inline int launch_chain_one(const ChainArgs& a, int batch, size_t lds, hipStream_t stream) {
-  auto kern = rbchain_kernel<T, MF, NF, NWV, TS>;
-  static std::atomic<uint32_t> lds_ok{0};                  // > 64 KiB dynamic LDS: opt in once per device
-  if (!allow_big_lds(lds_ok, reinterpret_cast<const void*>(kern))) return QVC_ERR_LAUNCH;
   const dim3 grid((unsigned)ceil_div(a.p[0].T, a.NT), (unsigned)batch);
-  hipLaunchKernelGGL(kern, grid, dim3(NWV * 64), lds, stream, a);
-  return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
+  return launch_big_lds<rbchain_kernel<T, MF, NF, NWV, TS>>(grid, dim3(NWV * 64), lds, stream, a);
 }
 
 template <typename T, int MF, int NWV, typename TS>

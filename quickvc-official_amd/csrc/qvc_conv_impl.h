@@ -98,6 +98,25 @@ __device__ __forceinline__ int swz(int row, Swz m) { return (row >> m.sh) & m.ma
 __device__ __forceinline__ int rotc(int chunk, Swz m) {
   return m.rot ? ((chunk & ~15) | ((chunk & 1) << 3) | ((chunk >> 1) & 7)) : chunk;
 }
+// 16-byte chunk `chunk` of row `row` of the tile at `base` (rows of `rowbytes` bytes); base 0: its byte offset
+template <typename B>
+__device__ __forceinline__ B tile_at(B base, int row, int chunk, int rowbytes, Swz m) {
+  return base + row * rowbytes + ((rotc(chunk, m) ^ swz(row, m)) << 4);
+}
+
+// Zeroes an accumulator array f32x4 acc[M][N].  A macro on purpose: as a function taking the array by reference it
+// cost the 4-wave conv, WaveNet-layer and WaveNet-stack kernels 16-32 more vector registers and a wave of occupancy.
+#define QVC_ZERO_ACC(acc) \
+  _Pragma("unroll") for (auto& row_ : acc) { _Pragma("unroll") for (auto& e_ : row_) e_ = f32x4{0.f, 0.f, 0.f, 0.f}; }
+
+// The frame `src` that tile row `ti` reads, and whether it reads one at all: an utterance's frames are [Tlo, Tin),
+// everything outside is the conv's zero padding.  reflect: `ti` counts in the sequence with one reflected frame in
+// front (row Tlo reads frame Tlo + 1, row ti > Tlo reads frame ti - 1).
+__device__ __forceinline__ bool in_row(int ti, int Tlo, int Tin, int reflect, int& src) {
+  if (reflect) { src = ti == Tlo ? Tlo + 1 : ti - 1; return ti >= Tlo && ti <= Tin; }
+  src = ti;
+  return ti >= Tlo && ti < Tin;
+}
 
 // leaky ReLU on 8 packed operand values (slope <= 1): max(x, slope*x), in operand arithmetic
 template <typename T>
@@ -121,18 +140,83 @@ __device__ __forceinline__ f16x8 lrelu8<_Float16>(f16x8 v, float slope) {
   return __builtin_elementwise_max(v, s);
 }
 
+// leaky ReLU of eight values of a stream of type TS, as the operand type T
+template <typename T, typename TS>
+__device__ __forceinline__ typename Op<T>::frag act8(typename Op<TS>::frag h, float slope) {
+  if constexpr (std::is_same<T, TS>::value) {
+    return lrelu8<T>(h, slope);
+  } else {                                       // stream type -> fp32 -> activation -> operand type
+    typename Op<T>::frag o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = Op<T>::cvt(lrelu((float)h[e], slope));
+    return o;
+  }
+}
+
+// fp32 -> operand type, eight consecutive channels (two float4) at a time; cvt8_lrelu: with the activation on the way
+template <typename T>
+__device__ __forceinline__ typename Op<T>::frag cvt8(float4 v0, float4 v1) {
+  using O = Op<T>;
+  typename O::frag h;
+  h[0] = O::cvt(v0.x); h[1] = O::cvt(v0.y); h[2] = O::cvt(v0.z); h[3] = O::cvt(v0.w);
+  h[4] = O::cvt(v1.x); h[5] = O::cvt(v1.y); h[6] = O::cvt(v1.z); h[7] = O::cvt(v1.w);
+  return h;
+}
+template <typename T>
+__device__ __forceinline__ typename Op<T>::frag cvt8_lrelu(float4 v0, float4 v1, float slope) {
+  return cvt8<T>(make_float4(lrelu(v0.x, slope), lrelu(v0.y, slope), lrelu(v0.z, slope), lrelu(v0.w, slope)),
+                 make_float4(lrelu(v1.x, slope), lrelu(v1.y, slope), lrelu(v1.z, slope), lrelu(v1.w, slope)));
+}
+
+// Epilogue packing of a lane's accumulator quads (four consecutive channels each) to type T:
+//   pack4_lrelu / pack8_lrelu: lrelu(acc + bias);  pack4_res / pack8_res: acc + bias + residual (r: T's quad / frag).
+// The 8-wide forms take the two quads of eight consecutive channels = one 16-byte piece.
+template <typename T>
+__device__ __forceinline__ typename Op<T>::quad pack4_lrelu(f32x4 a, float4 b, float slope) {
+  using O = Op<T>;
+  typename O::quad h;
+  h[0] = O::cvt(lrelu(a[0] + b.x, slope)); h[1] = O::cvt(lrelu(a[1] + b.y, slope));
+  h[2] = O::cvt(lrelu(a[2] + b.z, slope)); h[3] = O::cvt(lrelu(a[3] + b.w, slope));
+  return h;
+}
+template <typename T>
+__device__ __forceinline__ typename Op<T>::quad pack4_res(f32x4 a, float4 b, typename Op<T>::quad r) {
+  using O = Op<T>;
+  typename O::quad h;
+  h[0] = O::cvt(a[0] + b.x + (float)r[0]); h[1] = O::cvt(a[1] + b.y + (float)r[1]);
+  h[2] = O::cvt(a[2] + b.z + (float)r[2]); h[3] = O::cvt(a[3] + b.w + (float)r[3]);
+  return h;
+}
+template <typename T>
+__device__ __forceinline__ typename Op<T>::frag pack8_lrelu(f32x4 a0, float4 b0, f32x4 a1, float4 b1, float slope) {
+  const typename Op<T>::quad lo = pack4_lrelu<T>(a0, b0, slope), hi = pack4_lrelu<T>(a1, b1, slope);
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+template <typename T>
+__device__ __forceinline__ typename Op<T>::frag pack8_res(f32x4 a0, float4 b0, f32x4 a1, float4 b1, typename Op<T>::frag r) {
+  using quad = typename Op<T>::quad;
+  const quad lo = pack4_res<T>(a0, b0, __builtin_shufflevector(r, r, 0, 1, 2, 3));
+  const quad hi = pack4_res<T>(a1, b1, __builtin_shufflevector(r, r, 4, 5, 6, 7));
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// the WaveNet gate tanh(t + bt) * sigmoid(s + bs) of a lane's four channels, in the operand type
+template <typename T>
+__device__ __forceinline__ typename Op<T>::quad gate4(f32x4 t, f32x4 s, float4 bt, float4 bs) {
+  using O = Op<T>;
+  typename O::quad o;
+  o[0] = O::cvt(fast_tanh(t[0] + bt.x) * fast_sigmoid(s[0] + bs.x));
+  o[1] = O::cvt(fast_tanh(t[1] + bt.y) * fast_sigmoid(s[1] + bs.y));
+  o[2] = O::cvt(fast_tanh(t[2] + bt.z) * fast_sigmoid(s[2] + bs.z));
+  o[3] = O::cvt(fast_tanh(t[3] + bt.w) * fast_sigmoid(s[3] + bs.w));
+  return o;
+}
+
 // A fragments are prefetched PF k-steps ahead through a register ring of PF+1 slots.  Bytes in flight per
 // wave = PF * MF KiB: the weight stream of a layer is cold (touched once per step), so small-tile kernels
 // (WaveNet layer) need a deep ring to cover the L2/MALL round trip; big-tile kernels are MFMA-paced.
 #ifndef QVC_PF_CONV
 #define QVC_PF_CONV 3
-#endif
-// k-step rotation of a workgroup (see gemm_loop); QVC_NO_ROT=1 disables it for A/B measurements
-// (measured: no effect on gfx950 -- the L2 is not the limiter -- so it is off; QVC_ROTATE=1 enables it)
-#ifdef QVC_ROTATE
-#define QVC_ROT(n) ((int)((blockIdx.x * 5u + blockIdx.y * 3u + blockIdx.z) % (unsigned)(n)))
-#else
-#define QVC_ROT(n) 0
 #endif
 // developer ablation switches for tools/conv_bench (never defined in the product build)
 #ifdef QVC_ABLATE
@@ -190,6 +274,7 @@ __device__ __forceinline__ void gemm_loop_primed(f32x4 (&acc)[MF][NF], typename 
   int tap = 0, ks = 0;                                          // k-step whose B fragments are read next
   auto read_b = [&](frag (&dst)[NF]) {
     const int row0 = tap * dil + colrow;
+    // tile_at(), open-coded: through the helper the chunk is evaluated first, which reorders wn_stack2_kernel's code
     const char* bp = tile + row0 * rowbytes + ((rotc(ks * 4 + lq, sm) ^ swz(row0, sm)) << 4);
 #pragma unroll
     for (int n = 0; n < NF; ++n) dst[n] = *reinterpret_cast<const frag*>(bp + n * nstride);
@@ -225,10 +310,49 @@ __device__ __forceinline__ void gemm_loop_primed(f32x4 (&acc)[MF][NF], typename 
 // the compiler copied not-yet-landed asm outputs in one instantiation (wrong results).
 template <typename T, int MF, int NF, int kPF, int AS = MF>
 __device__ __forceinline__ void gemm_loop(f32x4 (&acc)[MF][NF], const typename Op<T>::frag* ap, int nIt, int KS, int dil,
-                                          const char* tile, int rowbytes, Swz sm, int colrow, int lq, int /*rot*/) {
+                                          const char* tile, int rowbytes, Swz sm, int colrow, int lq) {
   typename Op<T>::frag ar[kPF + 1][MF];
   gemm_prime<T, MF, kPF, AS>(ar, ap, nIt);
   gemm_loop_primed<T, MF, NF, kPF, AS>(acc, ar, ap, nIt, KS, dil, tile, rowbytes, sm, colrow, lq);
+}
+
+// Staging of a tile of an utterance's residual stream (type TS, frame-major, C channels; 16-byte chunk c8 of row r is
+// frame t_base + r, zeros outside [Tlo, Tb) and past C) by NTHR threads: put(r, c8, raw, act) gets the chunk as it is
+// in memory and as lrelu(x) in the operand type T.  Every load of the tile (up to 16 per thread) is in flight before the
+// first conversion -- no accumulator is live yet, so the registers are free: one memory round trip per tile instead of
+// two.  A thread walks rows / chunks by a fixed step instead of dividing per load.  loads_issued(first) runs between
+// the loads and the conversions of a batch (the phase stamps of tools/conv_bench).
+template <typename T, typename TS, int NTHR, typename Put, typename Mid>
+__device__ __forceinline__ void stage_stream_tile(const TS* xb, int C, int cpr, int total, int t_base, int Tlo, int Tb, float slope,
+                                                  int tid, Put&& put, Mid&& loads_issued) {
+  constexpr int kU = 16;
+  const int rstep = NTHR / cpr, cstep = NTHR - rstep * cpr;
+  for (int base = tid; base < total; base += NTHR * kU) {
+    uint4 v[kU];
+    const int r_0 = base / cpr, c_0 = base - r_0 * cpr;
+    int r = r_0, c8 = c_0;
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int idx = base + u * NTHR;
+      const int ti = t_base + r;
+      v[u] = make_uint4(0u, 0u, 0u, 0u);
+      if (idx < total && ti >= Tlo && ti < Tb && c8 * 8 < C) v[u] = *reinterpret_cast<const uint4*>(xb + (size_t)ti * C + c8 * 8);
+      c8 += cstep; r += rstep;
+      if (c8 >= cpr) { c8 -= cpr; ++r; }
+    }
+    r = r_0; c8 = c_0;
+    loads_issued(base == tid);
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int idx = base + u * NTHR;
+      if (idx < total) {
+        typename Op<TS>::frag h; __builtin_memcpy(&h, &v[u], 16);
+        put(r, c8, v[u], act8<T, TS>(h, slope));
+      }
+      c8 += cstep; r += rstep;
+      if (c8 >= cpr) { c8 -= cpr; ++r; }
+    }
+  }
 }
 
 // WM waves along M, WN = 4/WM along the frames; block tile = [WM*MF*16 rows] x [WN*NF*16 frames].
@@ -273,26 +397,19 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
         const int idx = base + u * 256;
         const int r = idx / cpr, c8 = idx - r * cpr;
         const int ti = t_base + r;
-        bool ok; int src;
-        if (a.reflect) { ok = ti >= Tlo && ti <= Tin; src = ti == Tlo ? Tlo + 1 : ti - 1; }
-        else { ok = ti >= Tlo && ti < Tin; src = ti; }
-        ok = ok && idx < total && (c8 * 8 < a.Cin);
+        int src;
+        const bool ok = in_row(ti, Tlo, Tin, a.reflect, src) && idx < total && (c8 * 8 < a.Cin);
         v0[u] = make_float4(0.f, 0.f, 0.f, 0.f); v1[u] = v0[u];
         if (ok) {
           const float4* p = reinterpret_cast<const float4*>(xb + (size_t)src * a.x_ts + c8 * 8);
           v0[u] = p[0]; v1[u] = p[1];
         }
-        dst[u] = idx < total ? r * rowbytes + ((rotc(c8, sm) ^ swz(r, sm)) << 4) : -1;
+        dst[u] = idx < total ? tile_at(0, r, c8, rowbytes, sm) : -1;
       }
 #pragma unroll
       for (int u = 0; u < kU; ++u) {
         if (dst[u] < 0) continue;
-        frag h;
-        h[0] = O::cvt(lrelu(v0[u].x, slope)); h[1] = O::cvt(lrelu(v0[u].y, slope));
-        h[2] = O::cvt(lrelu(v0[u].z, slope)); h[3] = O::cvt(lrelu(v0[u].w, slope));
-        h[4] = O::cvt(lrelu(v1[u].x, slope)); h[5] = O::cvt(lrelu(v1[u].y, slope));
-        h[6] = O::cvt(lrelu(v1[u].z, slope)); h[7] = O::cvt(lrelu(v1[u].w, slope));
-        *reinterpret_cast<frag*>(smem + dst[u]) = h;
+        *reinterpret_cast<frag*>(smem + dst[u]) = cvt8_lrelu<T>(v0[u], v1[u], slope);
       }
     }
   } else if (a.x_kind == XK_OP_FM && a.x2) {
@@ -311,10 +428,8 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
         const int idx = base + u * 256;
         const int r = idx / cpr, c8 = idx - r * cpr;
         const int ti = t_base + r;
-        bool ok; int src;
-        if (a.reflect) { ok = ti >= Tlo && ti <= Tin; src = ti == Tlo ? Tlo + 1 : ti - 1; }
-        else { ok = ti >= Tlo && ti < Tin; src = ti; }
-        ok = ok && idx < total && (c8 * 8 < a.Cin);
+        int src;
+        const bool ok = in_row(ti, Tlo, Tin, a.reflect, src) && idx < total && (c8 * 8 < a.Cin);
         v1[u] = make_uint4(0u, 0u, 0u, 0u); v2[u] = v1[u]; v3[u] = v1[u];
         if (ok) {
           const size_t o = (size_t)src * a.x_ts + c8 * 8;
@@ -322,7 +437,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
           v2[u] = *reinterpret_cast<const uint4*>(xb2 + o);
           v3[u] = *reinterpret_cast<const uint4*>(xb3 + o);
         }
-        dst[u] = idx < total ? r * rowbytes + ((rotc(c8, sm) ^ swz(r, sm)) << 4) : -1;
+        dst[u] = idx < total ? tile_at(0, r, c8, rowbytes, sm) : -1;
       }
 #pragma unroll
       for (int u = 0; u < kU; ++u) {
@@ -346,10 +461,11 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
         const int idx = base + u * 256;
         const int r = idx / cpr, c8 = idx - r * cpr;
         const int ti = t_base + r;
-        const bool ok = idx < total && ti >= Tlo && ti < Tin && (c8 * 8 < a.Cin);
+        int src;                                                  // (this input kind is never reflect-padded)
+        const bool ok = idx < total && in_row(ti, Tlo, Tin, 0, src) && (c8 * 8 < a.Cin);
         v[u] = make_uint4(0u, 0u, 0u, 0u);
-        if (ok) v[u] = *reinterpret_cast<const uint4*>(xb + (size_t)ti * a.x_ts + c8 * 8);
-        dst[u] = idx < total ? r * rowbytes + ((rotc(c8, sm) ^ swz(r, sm)) << 4) : -1;
+        if (ok) v[u] = *reinterpret_cast<const uint4*>(xb + (size_t)src * a.x_ts + c8 * 8);
+        dst[u] = idx < total ? tile_at(0, r, c8, rowbytes, sm) : -1;
       }
 #pragma unroll
       for (int u = 0; u < kU * 2; ++u)
@@ -380,7 +496,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
         const int ti = t_base + r;
         v[u] = 0.f;
         if (idx < total && c < a.Cin && ti >= Tlo && ti < Tin) v[u] = xb[(size_t)c * a.x_ts + ti];
-        dst[u] = idx < total ? r * rowbytes + ((rotc(c >> 3, sm) ^ swz(r, sm)) << 4) + (c & 7) * 2 : -1;
+        dst[u] = idx < total ? tile_at(0, r, c >> 3, rowbytes, sm) + (c & 7) * 2 : -1;
       }
 #pragma unroll
       for (int u = 0; u < kCM; ++u)
@@ -394,10 +510,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
   const int chunk_lo = CL ? 0 : (int)blockIdx.z, chunk_hi = CL ? a.nchunk : chunk_lo + 1;
   for (int chunk = chunk_lo; chunk < chunk_hi; ++chunk) {
   f32x4 acc[MF][NF];
-#pragma unroll
-  for (int m = 0; m < MF; ++m)
-#pragma unroll
-    for (int n = 0; n < NF; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+  QVC_ZERO_ACC(acc);
 
   const frag* ap = static_cast<const frag*>(a.w) + ((size_t)(chunk * WM + wm) * a.nIt * MF) * 64 + lane;
   // Polyphase rows: phase ph of a transposed conv (kernel k, stride s) has ceil((k - ph) / s) real taps; the packed
@@ -412,7 +525,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
     it0 = tap0 * a.KS;
   }
   gemm_loop<T, MF, NF, QVC_PF_CONV>(acc, ap + (size_t)it0 * MF * 64, a.nIt - it0, a.KS, a.dil, smem, rowbytes, sm,
-                                    wn * (NF * 16) + lrow + (it0 / a.KS) * a.dil, lq, QVC_ROT(a.nIt));
+                                    wn * (NF * 16) + lrow + (it0 / a.KS) * a.dil, lq);
 
   // ------------------------------------------------------------------ epilogue
   const int qw = q0 + wn * (NF * 16);                           // first frame of this wave's columns
@@ -433,13 +546,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
       for (int n = 0; n < NF; ++n) {
         const int q = qw + n * 16 + lrow;
         if (q < a.Nq) {
-          const f32x4 t = acc[f][n], s = acc[HF + f][n];
-          typename O::quad o;
-          o[0] = O::cvt(fast_tanh(t[0] + bt.x) * fast_sigmoid(s[0] + bs.x));
-          o[1] = O::cvt(fast_tanh(t[1] + bt.y) * fast_sigmoid(s[1] + bs.y));
-          o[2] = O::cvt(fast_tanh(t[2] + bt.z) * fast_sigmoid(s[2] + bs.z));
-          o[3] = O::cvt(fast_tanh(t[3] + bt.w) * fast_sigmoid(s[3] + bs.w));
-          *reinterpret_cast<typename O::quad*>(yb + (size_t)q * a.y16_ts) = o;
+          *reinterpret_cast<typename O::quad*>(yb + (size_t)q * a.y16_ts) = gate4<T>(acc[f][n], acc[HF + f][n], bt, bs);
         }
       }
     }
@@ -496,12 +603,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
         if (q >= a.Nq || o < 0 || o >= a.T_out) continue;
         frag h[MF / 2];
 #pragma unroll
-        for (int m = 0; m < MF; ++m) {
-          h[m >> 1][(m & 1) * 4 + 0] = O::cvt(lrelu(acc[m][n][0] + bias[m].x, a.slope_out));
-          h[m >> 1][(m & 1) * 4 + 1] = O::cvt(lrelu(acc[m][n][1] + bias[m].y, a.slope_out));
-          h[m >> 1][(m & 1) * 4 + 2] = O::cvt(lrelu(acc[m][n][2] + bias[m].z, a.slope_out));
-          h[m >> 1][(m & 1) * 4 + 3] = O::cvt(lrelu(acc[m][n][3] + bias[m].w, a.slope_out));
-        }
+        for (int m = 0; m < MF; m += 2) h[m >> 1] = pack8_lrelu<T>(acc[m][n], bias[m], acc[m + 1][n], bias[m + 1], a.slope_out);
 #pragma unroll
         for (int k2 = 0; k2 < MF / 2; ++k2) *reinterpret_cast<frag*>(yb + (size_t)o * a.y16_ts + k2 * 8) = h[k2];
       }
@@ -633,52 +735,18 @@ __global__ __launch_bounds__(NWV * 64) void rbpair_kernel(const PairArgs3 A) {
   if (st_ && lane == 0) st_[11] = __builtin_amdgcn_s_memrealtime();      // 100 MHz: with slots 0 / 6 the clock the chip holds
 #endif
 
-  if (!QVC_ABL(0)) {   // ---- stage lrelu(x): every load of the tile is in flight before the first conversion
-    // (no accumulator is live yet, so the registers are free: one memory round trip per tile instead of two)
-    const int t_base = q0 - h2 - h1;
-    const int total = Rx * cpr;
-    constexpr int kU = 16;
-    const int rstep = NTHR / cpr, cstep = NTHR - rstep * cpr;
-    for (int base = tid; base < total; base += NTHR * kU) {
-      uint4 v[kU];
-      const int r_0 = base / cpr, c_0 = base - r_0 * cpr;
-      int r = r_0, c8 = c_0;
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        const int idx = base + u * NTHR;
-        const int ti = t_base + r;
-        v[u] = make_uint4(0u, 0u, 0u, 0u);
-        if (idx < total && ti >= Tlo && ti < Tb && c8 * 8 < a.C) v[u] = *reinterpret_cast<const uint4*>(xb + (size_t)ti * a.C + c8 * 8);
-        c8 += cstep; r += rstep;
-        if (c8 >= cpr) { c8 -= cpr; ++r; }
-      }
-      r = r_0; c8 = c_0;
+  if (!QVC_ABL(0)) {   // ---- stage lrelu(x)
+    stage_stream_tile<T, TS, NTHR>(xb, a.C, cpr, Rx * cpr, q0 - h2 - h1, Tlo, Tb, a.slope, tid,
+        [&](int r, int c8, const uint4&, frag o) { *reinterpret_cast<frag*>(tile_at(smem, r, c8, rowbytes, sm)) = o; },
+        [&](bool first) {
 #ifdef QVC_STAMP
-      if (base == tid) {
-        QVC_ST(8);
-        asm volatile("s_waitcnt vmcnt(15)" ::: "memory");      // the first of the 16 loads is back
-        QVC_ST(9);
-      }
-#endif
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        const int idx = base + u * NTHR;
-        if (idx < total) {
-          frag o;
-          if constexpr (std::is_same<T, TS>::value) {
-            frag h; __builtin_memcpy(&h, &v[u], 16);
-            o = lrelu8<T>(h, a.slope);
-          } else {                                   // stream type -> fp32 -> activation -> operand type
-            sfrag h; __builtin_memcpy(&h, &v[u], 16);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = O::cvt(lrelu((float)h[e], a.slope));
+          if (first) {
+            QVC_ST(8);
+            asm volatile("s_waitcnt vmcnt(15)" ::: "memory");      // the first of the 16 loads is back
+            QVC_ST(9);
           }
-          *reinterpret_cast<frag*>(smem + r * rowbytes + ((rotc(c8, sm) ^ swz(r, sm)) << 4)) = o;
-        }
-        c8 += cstep; r += rstep;
-        if (c8 >= cpr) { c8 -= cpr; ++r; }
-      }
-    }
+#endif
+        });
   }
   QVC_ST(10);
   __syncthreads();
@@ -686,12 +754,9 @@ __global__ __launch_bounds__(NWV * 64) void rbpair_kernel(const PairArgs3 A) {
 
   {   // ---- GEMM1 over N1P frames, then bias + lrelu -> intermediate tile (in place of the input tile)
     f32x4 acc[MF][NF1];
-#pragma unroll
-    for (int m = 0; m < MF; ++m)
-#pragma unroll
-      for (int n = 0; n < NF1; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    QVC_ZERO_ACC(acc);
     const frag* ap = static_cast<const frag*>(a.w1) + ((size_t)wm * a.nIt * MF) * 64 + lane;
-    if (!QVC_ABL(1)) gemm_loop<T, MF, NF1, QVC_PF_CONV>(acc, ap, a.nIt, a.KS, a.dil, smem, rowbytes, sm, wn * (NF1 * 16) + lrow, lq, QVC_ROT(a.nIt));
+    if (!QVC_ABL(1)) gemm_loop<T, MF, NF1, QVC_PF_CONV>(acc, ap, a.nIt, a.KS, a.dil, smem, rowbytes, sm, wn * (NF1 * 16) + lrow, lq);
     QVC_ST(2);
     float4 bias[MF];                     // the bias array is padded to WM*MF*16 entries (zeros past C)
 #pragma unroll
@@ -703,8 +768,6 @@ __global__ __launch_bounds__(NWV * 64) void rbpair_kernel(const PairArgs3 A) {
       const int jr = wn * (NF1 * 16) + n * 16 + lrow;            // intermediate row <-> frame q0 - h2 + jr
       const int f = q0 - h2 + jr;
       const bool inside = f >= Tlo && f < Tb;                      // conv2 zero-pads outside [0, T)
-      char* rowp = smem + jr * rowbytes;
-      const int sw = swz(jr, sm);
       if constexpr (kWide) {
 #pragma unroll
         for (int m = 0; m < MF; m += 2) {
@@ -712,15 +775,12 @@ __global__ __launch_bounds__(NWV * 64) void rbpair_kernel(const PairArgs3 A) {
           if (v >= a.CP) continue;
           frag h;
           if (inside && v < a.C) {
-            h[0] = O::cvt(lrelu(acc[m][n][0] + bias[m].x, a.slope)); h[1] = O::cvt(lrelu(acc[m][n][1] + bias[m].y, a.slope));
-            h[2] = O::cvt(lrelu(acc[m][n][2] + bias[m].z, a.slope)); h[3] = O::cvt(lrelu(acc[m][n][3] + bias[m].w, a.slope));
-            h[4] = O::cvt(lrelu(acc[m + 1][n][0] + bias[m + 1].x, a.slope)); h[5] = O::cvt(lrelu(acc[m + 1][n][1] + bias[m + 1].y, a.slope));
-            h[6] = O::cvt(lrelu(acc[m + 1][n][2] + bias[m + 1].z, a.slope)); h[7] = O::cvt(lrelu(acc[m + 1][n][3] + bias[m + 1].w, a.slope));
+            h = pack8_lrelu<T>(acc[m][n], bias[m], acc[m + 1][n], bias[m + 1], a.slope);
           } else {
 #pragma unroll
             for (int e = 0; e < 8; ++e) h[e] = (T)0.f;
           }
-          *reinterpret_cast<frag*>(rowp + ((rotc(v >> 3, sm) ^ sw) << 4)) = h;
+          *reinterpret_cast<frag*>(tile_at(smem, jr, v >> 3, rowbytes, sm)) = h;
         }
       } else {
 #pragma unroll
@@ -729,12 +789,11 @@ __global__ __launch_bounds__(NWV * 64) void rbpair_kernel(const PairArgs3 A) {
           if (v >= a.CP) continue;
           quad h;
           if (inside && v < a.C) {
-            h[0] = O::cvt(lrelu(acc[m][n][0] + bias[m].x, a.slope)); h[1] = O::cvt(lrelu(acc[m][n][1] + bias[m].y, a.slope));
-            h[2] = O::cvt(lrelu(acc[m][n][2] + bias[m].z, a.slope)); h[3] = O::cvt(lrelu(acc[m][n][3] + bias[m].w, a.slope));
+            h = pack4_lrelu<T>(acc[m][n], bias[m], a.slope);
           } else {
             h[0] = h[1] = h[2] = h[3] = (T)0.f;
           }
-          *reinterpret_cast<quad*>(rowp + ((rotc(v >> 3, sm) ^ sw) << 4) + (v & 7) * 2) = h;
+          *reinterpret_cast<quad*>(tile_at(smem, jr, v >> 3, rowbytes, sm) + (v & 7) * 2) = h;
         }
       }
     }
@@ -744,12 +803,9 @@ __global__ __launch_bounds__(NWV * 64) void rbpair_kernel(const PairArgs3 A) {
 
   {   // ---- GEMM2 over NT frames (dilation 1) + bias + residual
     f32x4 acc[MF][NF];
-#pragma unroll
-    for (int m = 0; m < MF; ++m)
-#pragma unroll
-      for (int n = 0; n < NF; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    QVC_ZERO_ACC(acc);
     const frag* ap = static_cast<const frag*>(a.w2) + ((size_t)wm * a.nIt * MF) * 64 + lane;
-    if (!QVC_ABL(2)) gemm_loop<T, MF, NF, QVC_PF_CONV>(acc, ap, a.nIt, a.KS, 1, smem, rowbytes, sm, wn * (NF * 16) + lrow, lq, QVC_ROT(a.nIt));
+    if (!QVC_ABL(2)) gemm_loop<T, MF, NF, QVC_PF_CONV>(acc, ap, a.nIt, a.KS, 1, smem, rowbytes, sm, wn * (NF * 16) + lrow, lq);
     QVC_ST(5);
     float4 bias[MF];
 #pragma unroll
@@ -781,12 +837,7 @@ __global__ __launch_bounds__(NWV * 64) void rbpair_kernel(const PairArgs3 A) {
           const int q = qw + n * 16;
           if (q >= Tb) continue;
           sfrag r8; __builtin_memcpy(&r8, &rr[m / 2][n], 16);
-          sfrag h;
-          h[0] = OS::cvt(acc[m][n][0] + bias[m].x + (float)r8[0]); h[1] = OS::cvt(acc[m][n][1] + bias[m].y + (float)r8[1]);
-          h[2] = OS::cvt(acc[m][n][2] + bias[m].z + (float)r8[2]); h[3] = OS::cvt(acc[m][n][3] + bias[m].w + (float)r8[3]);
-          h[4] = OS::cvt(acc[m + 1][n][0] + bias[m + 1].x + (float)r8[4]); h[5] = OS::cvt(acc[m + 1][n][1] + bias[m + 1].y + (float)r8[5]);
-          h[6] = OS::cvt(acc[m + 1][n][2] + bias[m + 1].z + (float)r8[6]); h[7] = OS::cvt(acc[m + 1][n][3] + bias[m + 1].w + (float)r8[7]);
-          *reinterpret_cast<sfrag*>(yb + (size_t)q * a.C + v) = h;
+          *reinterpret_cast<sfrag*>(yb + (size_t)q * a.C + v) = pack8_res<TS>(acc[m][n], bias[m], acc[m + 1][n], bias[m + 1], r8);
         }
       }
     } else {
@@ -809,11 +860,7 @@ __global__ __launch_bounds__(NWV * 64) void rbpair_kernel(const PairArgs3 A) {
         for (int n = 0; n < NF; ++n) {
           const int q = qw + n * 16;
           if (q >= Tb) continue;
-          const squad r4 = rr[m][n];
-          squad h;
-          h[0] = OS::cvt(acc[m][n][0] + bias[m].x + (float)r4[0]); h[1] = OS::cvt(acc[m][n][1] + bias[m].y + (float)r4[1]);
-          h[2] = OS::cvt(acc[m][n][2] + bias[m].z + (float)r4[2]); h[3] = OS::cvt(acc[m][n][3] + bias[m].w + (float)r4[3]);
-          *reinterpret_cast<squad*>(yb + (size_t)q * a.C + v) = h;
+          *reinterpret_cast<squad*>(yb + (size_t)q * a.C + v) = pack4_res<TS>(acc[m][n], bias[m], rr[m][n]);
         }
       }
     }
@@ -875,15 +922,12 @@ __global__ __launch_bounds__(WV * 64) void wn_layer_kernel(const WnArgs a) {
           const float4* p = reinterpret_cast<const float4*>(xb + (size_t)ti * a.H + c8 * 8);
           v0[u] = p[0]; v1[u] = p[1];
         }
-        dst[u] = idx < total ? r * rowbytes + ((rotc(c8, sm) ^ swz(r, sm)) << 4) : -1;
+        dst[u] = idx < total ? tile_at(0, r, c8, rowbytes, sm) : -1;
       }
 #pragma unroll
       for (int u = 0; u < kU; ++u) {
         if (dst[u] < 0) continue;
-        frag h;
-        h[0] = O::cvt(v0[u].x); h[1] = O::cvt(v0[u].y); h[2] = O::cvt(v0[u].z); h[3] = O::cvt(v0[u].w);
-        h[4] = O::cvt(v1[u].x); h[5] = O::cvt(v1[u].y); h[6] = O::cvt(v1[u].z); h[7] = O::cvt(v1[u].w);
-        *reinterpret_cast<frag*>(smem + dst[u]) = h;
+        *reinterpret_cast<frag*>(smem + dst[u]) = cvt8<T>(v0[u], v1[u]);
       }
     }
   }
@@ -891,12 +935,9 @@ __global__ __launch_bounds__(WV * 64) void wn_layer_kernel(const WnArgs a) {
 
   {   // ---- GEMM1 (k taps) + conditioning + gate -> acts tile
     f32x4 acc[MF1][NF];
-#pragma unroll
-    for (int m = 0; m < MF1; ++m)
-#pragma unroll
-      for (int n = 0; n < NF; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    QVC_ZERO_ACC(acc);
     const frag* ap = static_cast<const frag*>(a.w_in) + ((size_t)wm * a.nIt1 * MF1) * 64 + lane;
-    if (!QVC_ABL(1)) gemm_loop<T, MF1, NF, QVC_PF_WN>(acc, ap, a.nIt1, a.KS, 1, smem, rowbytes, sm, lrow, lq, QVC_ROT(a.nIt1));
+    if (!QVC_ABL(1)) gemm_loop<T, MF1, NF, QVC_PF_WN>(acc, ap, a.nIt1, a.KS, 1, smem, rowbytes, sm, lrow, lq);
     const float* bb = a.bbias + (size_t)b * a.bbias_bs;
 #pragma unroll
     for (int f = 0; f < FW; ++f) {
@@ -907,17 +948,13 @@ __global__ __launch_bounds__(WV * 64) void wn_layer_kernel(const WnArgs a) {
 #pragma unroll
       for (int n = 0; n < NF; ++n) {
         const int j = n * 16 + lrow;
-        const f32x4 t = acc[f][n], sg = acc[FW + f][n];
         quad o;
         if (ch0 < a.H) {
-          o[0] = O::cvt(fast_tanh(t[0] + bt.x) * fast_sigmoid(sg[0] + bs.x));
-          o[1] = O::cvt(fast_tanh(t[1] + bt.y) * fast_sigmoid(sg[1] + bs.y));
-          o[2] = O::cvt(fast_tanh(t[2] + bt.z) * fast_sigmoid(sg[2] + bs.z));
-          o[3] = O::cvt(fast_tanh(t[3] + bt.w) * fast_sigmoid(sg[3] + bs.w));
+          o = gate4<T>(acc[f][n], acc[FW + f][n], bt, bs);
         } else {
           o[0] = o[1] = o[2] = o[3] = (T)0.f;                    // K padding of the 1x1 must be finite
         }
-        *reinterpret_cast<quad*>(acts + j * rowbytes + ((rotc(ch0 >> 3, sm) ^ swz(j, sm)) << 4) + (ch0 & 7) * 2) = o;
+        *reinterpret_cast<quad*>(tile_at(acts, j, ch0 >> 3, rowbytes, sm) + (ch0 & 7) * 2) = o;
       }
     }
   }
@@ -925,12 +962,9 @@ __global__ __launch_bounds__(WV * 64) void wn_layer_kernel(const WnArgs a) {
 
   {   // ---- GEMM2 (1x1) + residual / skip updates
     f32x4 acc[MF2][NF];
-#pragma unroll
-    for (int m = 0; m < MF2; ++m)
-#pragma unroll
-      for (int n = 0; n < NF; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    QVC_ZERO_ACC(acc);
     const frag* ap = static_cast<const frag*>(a.w_rs) + ((size_t)wm * a.KS * MF2) * 64 + lane;
-    if (!QVC_ABL(2)) gemm_loop<T, MF2, NF, QVC_PF_WN>(acc, ap, a.KS, a.KS, 1, acts, rowbytes, sm, lrow, lq, QVC_ROT(a.KS));
+    if (!QVC_ABL(2)) gemm_loop<T, MF2, NF, QVC_PF_WN>(acc, ap, a.KS, a.KS, 1, acts, rowbytes, sm, lrow, lq);
     // all loads of the epilogue are issued before the first dependent store (they are independent
     // L2 round trips; issued one by one they cost ~5 us per layer)
     float4 xin[FW][NF], oin[FW][NF];
@@ -1035,21 +1069,14 @@ __global__ __launch_bounds__(WV * 64) void wn_stack_kernel(const WnStackArgs a) 
       const int q = w0 + r;
       if (q >= Tlo && q < Tb && c8 * 8 < a.pre_cin) {
         const float4* p = reinterpret_cast<const float4*>(zb + (size_t)q * a.z_ts + c8 * 8);
-        const float4 v0 = p[0], v1 = p[1];
-        frag h;
-        h[0] = O::cvt(v0.x); h[1] = O::cvt(v0.y); h[2] = O::cvt(v0.z); h[3] = O::cvt(v0.w);
-        h[4] = O::cvt(v1.x); h[5] = O::cvt(v1.y); h[6] = O::cvt(v1.z); h[7] = O::cvt(v1.w);
-        *reinterpret_cast<frag*>(acts + r * rowbytes + ((rotc(c8, sm) ^ swz(r, sm)) << 4)) = h;
+        *reinterpret_cast<frag*>(tile_at(acts, r, c8, rowbytes, sm)) = cvt8<T>(p[0], p[1]);
       }
     }
     __syncthreads();
     f32x4 pacc[FW][NF];
-#pragma unroll
-    for (int f = 0; f < FW; ++f)
-#pragma unroll
-      for (int n = 0; n < NF; ++n) pacc[f][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    QVC_ZERO_ACC(pacc);
     const frag* app = static_cast<const frag*>(a.w_pre) + ((size_t)wm * a.pre_KS * FW) * 64 + lane;
-    gemm_loop<T, FW, NF, QVC_PF_STACK>(pacc, app, a.pre_KS, a.pre_KS, 1, acts, rowbytes, sm, lrow, lq, 0);
+    gemm_loop<T, FW, NF, QVC_PF_STACK>(pacc, app, a.pre_KS, a.pre_KS, 1, acts, rowbytes, sm, lrow, lq);
 #pragma unroll
     for (int f = 0; f < FW; ++f) {
       const int ch0 = (wm * FW + f) * 16 + lq * 4;
@@ -1094,7 +1121,7 @@ __global__ __launch_bounds__(WV * 64) void wn_stack_kernel(const WnStackArgs a) 
         const int r = n * 16 + lrow + left;
         quad h;
         h[0] = O::cvt(xr[f][n][0]); h[1] = O::cvt(xr[f][n][1]); h[2] = O::cvt(xr[f][n][2]); h[3] = O::cvt(xr[f][n][3]);
-        *reinterpret_cast<quad*>(smem + r * rowbytes + ((rotc(ch0 >> 3, sm) ^ swz(r, sm)) << 4) + (ch0 & 7) * 2) = h;
+        *reinterpret_cast<quad*>(tile_at(smem, r, ch0 >> 3, rowbytes, sm) + (ch0 & 7) * 2) = h;
       }
     }
   };
@@ -1106,12 +1133,9 @@ __global__ __launch_bounds__(WV * 64) void wn_stack_kernel(const WnStackArgs a) 
     const bool last = a.final_layer && l == a.layers - 1;      // the network's last layer has no residual half
     {   // ---- GEMM1 (k taps) + conditioning + gate -> acts tile
       f32x4 acc[MF][NF];
-#pragma unroll
-      for (int m = 0; m < MF; ++m)
-#pragma unroll
-        for (int n = 0; n < NF; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+      QVC_ZERO_ACC(acc);
       const frag* ap = static_cast<const frag*>(a.w_in[l]) + ((size_t)wm * a.nIt1 * MF) * 64 + lane;
-      if (!QVC_ABL(1)) gemm_loop<T, MF, NF, QVC_PF_STACK>(acc, ap, a.nIt1, a.KS, 1, smem, rowbytes, sm, lrow, lq, 0);
+      if (!QVC_ABL(1)) gemm_loop<T, MF, NF, QVC_PF_STACK>(acc, ap, a.nIt1, a.KS, 1, smem, rowbytes, sm, lrow, lq);
 #ifdef QVC_STAMP
       if (l < 4) QVC_ST(2 + 6 * l);
 #endif
@@ -1130,14 +1154,11 @@ __global__ __launch_bounds__(WV * 64) void wn_stack_kernel(const WnStackArgs a) 
           if (ch0 < a.H && QVC_ABL(4)) {
             o[0] = O::cvt(t[0] + bt.x); o[1] = O::cvt(t[1] + bt.y); o[2] = O::cvt(sg[2] + bs.z); o[3] = O::cvt(sg[3] + bs.w);
           } else if (ch0 < a.H) {
-            o[0] = O::cvt(fast_tanh(t[0] + bt.x) * fast_sigmoid(sg[0] + bs.x));
-            o[1] = O::cvt(fast_tanh(t[1] + bt.y) * fast_sigmoid(sg[1] + bs.y));
-            o[2] = O::cvt(fast_tanh(t[2] + bt.z) * fast_sigmoid(sg[2] + bs.z));
-            o[3] = O::cvt(fast_tanh(t[3] + bt.w) * fast_sigmoid(sg[3] + bs.w));
+            o = gate4<T>(t, sg, bt, bs);
           } else {
             o[0] = o[1] = o[2] = o[3] = (T)0.f;
           }
-          *reinterpret_cast<quad*>(acts + j * rowbytes + ((rotc(ch0 >> 3, sm) ^ swz(j, sm)) << 4) + (ch0 & 7) * 2) = o;
+          *reinterpret_cast<quad*>(tile_at(acts, j, ch0 >> 3, rowbytes, sm) + (ch0 & 7) * 2) = o;
         }
       }
     }
@@ -1150,14 +1171,11 @@ __global__ __launch_bounds__(WV * 64) void wn_stack_kernel(const WnStackArgs a) 
 #endif
     {   // ---- GEMM2 (1x1): x += res, out += skip   (modules.py:104-112)
       f32x4 acc[MF][NF];
-#pragma unroll
-      for (int m = 0; m < MF; ++m)
-#pragma unroll
-        for (int n = 0; n < NF; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+      QVC_ZERO_ACC(acc);
       const float* brs = a.b_rs[l];
       if (!last) {
         const frag* ap = static_cast<const frag*>(a.w_rs[l]) + ((size_t)wm * a.KS * MF) * 64 + lane;
-        if (!QVC_ABL(2)) gemm_loop<T, MF, NF, QVC_PF_STACK>(acc, ap, a.KS, a.KS, 1, acts, rowbytes, sm, lrow, lq, 0);
+        if (!QVC_ABL(2)) gemm_loop<T, MF, NF, QVC_PF_STACK>(acc, ap, a.KS, a.KS, 1, acts, rowbytes, sm, lrow, lq);
 #ifdef QVC_STAMP
         if (l < 4) QVC_ST(5 + 6 * l);
 #endif
@@ -1185,7 +1203,7 @@ __global__ __launch_bounds__(WV * 64) void wn_stack_kernel(const WnStackArgs a) 
       } else {
         f32x4 (&acl)[FW][NF] = reinterpret_cast<f32x4 (&)[FW][NF]>(acc);
         const frag* ap = static_cast<const frag*>(a.w_rs[l]) + ((size_t)wm * a.KS * FW) * 64 + lane;
-        gemm_loop<T, FW, NF, QVC_PF_STACK>(acl, ap, a.KS, a.KS, 1, acts, rowbytes, sm, lrow, lq, 0);
+        gemm_loop<T, FW, NF, QVC_PF_STACK>(acl, ap, a.KS, a.KS, 1, acts, rowbytes, sm, lrow, lq);
 #pragma unroll
         for (int f = 0; f < FW; ++f) {
           const int ch0 = (wm * FW + f) * 16 + lq * 4;
@@ -1228,17 +1246,14 @@ __global__ __launch_bounds__(WV * 64) void wn_stack_kernel(const WnStackArgs a) 
           } else {
             h[0] = h[1] = h[2] = h[3] = (T)0.f;
           }
-          *reinterpret_cast<quad*>(acts + j * rowbytes + ((rotc(ch0 >> 3, sm) ^ swz(j, sm)) << 4) + (ch0 & 7) * 2) = h;
+          *reinterpret_cast<quad*>(tile_at(acts, j, ch0 >> 3, rowbytes, sm) + (ch0 & 7) * 2) = h;
         }
       }
       __syncthreads();
       f32x4 qacc[PM][ON];
-#pragma unroll
-      for (int m = 0; m < PM; ++m)
-#pragma unroll
-        for (int n = 0; n < ON; ++n) qacc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+      QVC_ZERO_ACC(qacc);
       const frag* apq = static_cast<const frag*>(a.w_post) + ((size_t)wm * a.KS * PM) * 64 + lane;
-      gemm_loop<T, PM, ON, QVC_PF_STACK>(qacc, apq, a.KS, a.KS, 1, acts, rowbytes, sm, OLO * 16 + lrow, lq, 0);
+      gemm_loop<T, PM, ON, QVC_PF_STACK>(qacc, apq, a.KS, a.KS, 1, acts, rowbytes, sm, OLO * 16 + lrow, lq);
 #pragma unroll
       for (int m = 0; m < PM; ++m) {
         const int v = (wm * PM + m) * 16 + lq * 4;
@@ -1334,13 +1349,9 @@ inline TileChoice choose_tile(const ConvDesc& d, int Nq, int batch, const int* n
 
 template <typename T, int MF, int NF, int WM, int EPI, bool CL = false>
 inline int launch_one_cl(const ConvArgs& a, int batch, size_t lds, hipStream_t stream) {
-  auto kern = conv_mfma_kernel<T, MF, NF, WM, EPI, CL>;
-  static std::atomic<uint32_t> lds_ok{0};                  // > 64 KiB dynamic LDS: opt in once per device
-  if (!allow_big_lds(lds_ok, reinterpret_cast<const void*>(kern))) return QVC_ERR_LAUNCH;
   constexpr int NT = (kWaves / WM) * NF * 16;
-  dim3 grid((unsigned)ceil_div(a.Nq, NT), (unsigned)batch, (unsigned)(CL ? 1 : a.nchunk));
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, a);
-  return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
+  const dim3 grid((unsigned)ceil_div(a.Nq, NT), (unsigned)batch, (unsigned)(CL ? 1 : a.nchunk));
+  return launch_big_lds<conv_mfma_kernel<T, MF, NF, WM, EPI, CL>>(grid, dim3(256), lds, stream, a);
 }
 template <typename T, int MF, int NF, int WM, int EPI>
 inline int launch_one(const ConvArgs& a, int batch, size_t lds, hipStream_t stream) {
@@ -1438,14 +1449,10 @@ inline TileChoice choose_pair_tile(const ConvDesc* ds, int n, int T, int batch) 
 
 template <typename T, int MF, int NF, int WM, int NWV, typename TS>
 inline int launch_pair_one(const PairArgs3& a, int batch, size_t lds, hipStream_t stream) {
-  auto kern = rbpair_kernel<T, MF, NF, WM, NWV, TS>;
-  static std::atomic<uint32_t> lds_ok{0};                  // > 64 KiB dynamic LDS: opt in once per device
-  if (!allow_big_lds(lds_ok, reinterpret_cast<const void*>(kern))) return QVC_ERR_LAUNCH;
   constexpr int NT = (NWV / WM) * NF * 16;
   const unsigned tiles = (unsigned)ceil_div(a.p[0].T, NT);
   const dim3 grid = a.chain_major ? dim3(tiles, (unsigned)batch, (unsigned)a.n) : dim3(tiles * (unsigned)a.n, (unsigned)batch, 1);
-  hipLaunchKernelGGL(kern, grid, dim3(NWV * 64), lds, stream, a);
-  return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
+  return launch_big_lds<rbpair_kernel<T, MF, NF, WM, NWV, TS>>(grid, dim3(NWV * 64), lds, stream, a);
 }
 
 template <typename T, int MF, int WM, int NWV, typename TS>
@@ -1489,18 +1496,9 @@ template <typename T, int NF, int WV>
 inline int launch_wn_one(const WnArgs& a, int waves, int batch, hipStream_t stream) {
   const size_t lds = (size_t)(NF * 16 + a.taps - 1 + NF * 16) * a.HP * 2;
   dim3 grid((unsigned)ceil_div(a.T, NF * 16), (unsigned)batch), block((unsigned)waves * 64);
-  // hidden = 256 with 64-frame tiles needs (64 + taps-1 + 64) * 512 B > 64 KiB of dynamic LDS: opt in per device
-  static std::atomic<uint32_t> lds_ok_last{0}, lds_ok_mid{0};
-  if (a.last) {
-    auto kern = wn_layer_kernel<T, NF, true, WV>;
-    if (lds > 64 * 1024 && !allow_big_lds(lds_ok_last, reinterpret_cast<const void*>(kern))) return QVC_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, grid, block, lds, stream, a);
-  } else {
-    auto kern = wn_layer_kernel<T, NF, false, WV>;
-    if (lds > 64 * 1024 && !allow_big_lds(lds_ok_mid, reinterpret_cast<const void*>(kern))) return QVC_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, grid, block, lds, stream, a);
-  }
-  return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
+  // hidden = 256 with 64-frame tiles needs (64 + taps-1 + 64) * 512 B > 64 KiB of dynamic LDS: only then the opt-in
+  return a.last ? launch_big_lds<wn_layer_kernel<T, NF, true, WV>>(grid, block, lds, stream, a, 64 * 1024)
+                : launch_big_lds<wn_layer_kernel<T, NF, false, WV>>(grid, block, lds, stream, a, 64 * 1024);
 }
 
 template <typename T, int NF>
@@ -1527,12 +1525,9 @@ int launch_wn_typed(const ConvDesc& din, const WnArgs& a, int batch, void* strea
 // ---- whole-stack WaveNet dispatch
 template <typename T, int NF, int PM, int WV>
 inline int launch_wn_stack_pm(const WnStackArgs& a, int waves, int batch, hipStream_t stream) {
-  auto kern = wn_stack_kernel<T, NF, PM, WV>;
   const size_t lds = (size_t)(NF * 16 + a.taps - 1 + NF * 16) * a.HP * 2;
-  static std::atomic<uint32_t> lds_ok{0};                  // > 64 KiB dynamic LDS: opt in once per device
-  if (!allow_big_lds(lds_ok, reinterpret_cast<const void*>(kern))) return QVC_ERR_LAUNCH;
-  hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(a.T, NF == 2 ? 16 : kWnOutFrames), (unsigned)batch), dim3((unsigned)waves * 64), lds, stream, a);
-  return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
+  const dim3 grid((unsigned)ceil_div(a.T, NF == 2 ? 16 : kWnOutFrames), (unsigned)batch);
+  return launch_big_lds<wn_stack_kernel<T, NF, PM, WV>>(grid, dim3((unsigned)waves * 64), lds, stream, a);
 }
 
 template <typename T, int NF, int PM>

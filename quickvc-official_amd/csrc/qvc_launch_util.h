@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <cstdint>
+#include "../../include/qvc.h"
 
 namespace qvc {
 
@@ -17,6 +18,17 @@ inline bool allow_big_lds(std::atomic<uint32_t>& done, const void* kernel) {
   if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
   done.fetch_or(bit, std::memory_order_release);
   return true;
+}
+
+// Launch `kern` with `lds` bytes of dynamic LDS: the opt-in above (its per-kernel mask lives here, one instance per
+// kernel pointer), the launch and the status check.  Kernels whose usual tile fits the default 64 KiB pass that as
+// `optin_above` and take the opt-in for the larger tiles only.
+template <auto kern, typename Args>
+inline int launch_big_lds(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Args& args, size_t optin_above = 0) {
+  static std::atomic<uint32_t> lds_ok{0};
+  if (lds > optin_above && !allow_big_lds(lds_ok, reinterpret_cast<const void*>(kern))) return QVC_ERR_LAUNCH;
+  hipLaunchKernelGGL(kern, grid, block, lds, stream, args);
+  return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
 }
 
 }  // namespace qvc

@@ -259,10 +259,8 @@ extern "C" int qvc_wave_to_mel(const void* table_dev, int32_t n_fft, int32_t hop
   const int piece = (kMelFrames - 1) * hop + n_fft;
   const size_t lds = (size_t)(piece + (piece / hop + 1) * kMelPadEvery) * 4;
   if (lds > 160 * 1024) return QVC_ERR_BAD_CONFIG;
-  static std::atomic<uint32_t> lds_ok{0};                  // > 64 KiB dynamic LDS: opt in once per device
-  if (!allow_big_lds(lds_ok, reinterpret_cast<const void*>(stft_mag_kernel))) return QVC_ERR_LAUNCH;
-  hipLaunchKernelGGL(stft_mag_kernel, dim3((unsigned)ceil_div(frames, kMelFrames), (unsigned)utterances, (unsigned)t.nchunk), dim3(256), lds, s, sa);
-  if (hipGetLastError() != hipSuccess) return QVC_ERR_LAUNCH;
+  const dim3 grid((unsigned)ceil_div(frames, kMelFrames), (unsigned)utterances, (unsigned)t.nchunk);
+  if (launch_big_lds<stft_mag_kernel>(grid, dim3(256), lds, s, sa) != QVC_OK) return QVC_ERR_LAUNCH;
   MelArgs ma;
   ma.spec = sa.spec; ma.basis = reinterpret_cast<const float*>(tb + t.basis_off);
   ma.range = reinterpret_cast<const int32_t*>(tb + t.range_off); ma.mel = mel;

@@ -114,10 +114,8 @@ void post_tail_kernel(const PostTailArgs A) {
         const int idx = base + u * 256;
         if (!regular) { r = idx / cpr; c8 = idx - r * cpr; }
         const int ti = t_base + r;
-        bool ok; int src;
-        if (A.c.reflect) { ok = ti >= Tlo && ti <= Tin; src = ti == Tlo ? Tlo + 1 : ti - 1; }
-        else { ok = ti >= Tlo && ti < Tin; src = ti; }
-        ok = ok && idx < total && (c8 * 8 < A.c.Cin);
+        int src;
+        const bool ok = in_row(ti, Tlo, Tin, A.c.reflect, src) && idx < total && (c8 * 8 < A.c.Cin);
         v1[u] = make_uint4(0u, 0u, 0u, 0u); v2[u] = v1[u]; v3[u] = v1[u];
         if (ok) {
           const size_t o = (size_t)src * A.c.x_ts + c8 * 8;
@@ -125,7 +123,7 @@ void post_tail_kernel(const PostTailArgs A) {
           v2[u] = *reinterpret_cast<const uint4*>(xb2 + o);
           v3[u] = *reinterpret_cast<const uint4*>(xb3 + o);
         }
-        dst[u] = idx < total ? r * rowbytes + ((rotc(c8, sm) ^ swz(r, sm)) << 4) : -1;
+        dst[u] = idx < total ? tile_at(0, r, c8, rowbytes, sm) : -1;
         r += rstep;
       }
 #pragma unroll
@@ -144,17 +142,14 @@ void post_tail_kernel(const PostTailArgs A) {
 
   // ------------------------------------------------------------------ GEMM (A from global through the ring, B from the tile)
   f32x4 acc[MF][NF];
-#pragma unroll
-  for (int m = 0; m < MF; ++m)
-#pragma unroll
-    for (int n = 0; n < NF; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+  QVC_ZERO_ACC(acc);
   const frag* ap = static_cast<const frag*>(A.c.w) + ((size_t)wm * A.c.nIt * MF) * 64 + lane;
   if (NB == 4 && wm == 0) {
-    gemm_loop<T, MF, NF, QVC_PF_CONV>(acc, ap, A.c.nIt, A.c.KS, 1, smem, rowbytes, sm, wn * (NF * 16) + lrow, lq, 0);
+    gemm_loop<T, MF, NF, QVC_PF_CONV>(acc, ap, A.c.nIt, A.c.KS, 1, smem, rowbytes, sm, wn * (NF * 16) + lrow, lq);
   } else {        // four bands, rows 48..95: the third fragment (80..95) is all padding -- 72 channels -- and is neither
                   // loaded nor multiplied; one band: rows 0..31 (18 channels), the packing's waves 1..3 are never read
     f32x4 (&acc2)[2][NF] = reinterpret_cast<f32x4 (&)[2][NF]>(acc);
-    gemm_loop<T, 2, NF, QVC_PF_CONV, MF>(acc2, ap, A.c.nIt, A.c.KS, 1, smem, rowbytes, sm, wn * (NF * 16) + lrow, lq, 0);
+    gemm_loop<T, 2, NF, QVC_PF_CONV, MF>(acc2, ap, A.c.nIt, A.c.KS, 1, smem, rowbytes, sm, wn * (NF * 16) + lrow, lq);
   }
   __syncthreads();                              // every wave is done with the input tile
 
@@ -225,14 +220,11 @@ void post_tail_kernel(const PostTailArgs A) {
 
 template <typename T, int NF, int NB>
 inline int launch_post_tail_nf(const ConvDesc& d, const PostTailArgs& a, int batch, hipStream_t stream) {
-  auto kern = post_tail_kernel<T, NF, NB>;
   const size_t lds = post_tail_lds<NF, NB>(d.taps, d.CinP);
   if (lds > 160 * 1024) return QVC_ERR_BAD_CONFIG;
-  static std::atomic<uint32_t> lds_ok{0};
-  if (!allow_big_lds(lds_ok, reinterpret_cast<const void*>(kern))) return QVC_ERR_LAUNCH;
   const int n_out = NB * 4 * (a.F - 1);
-  hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n_out, PostTailGeom<NF, NB>::OT), (unsigned)batch), dim3(256), lds, stream, a);
-  return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
+  const dim3 grid((unsigned)ceil_div(n_out, PostTailGeom<NF, NB>::OT), (unsigned)batch);
+  return launch_big_lds<post_tail_kernel<T, NF, NB>>(grid, dim3(256), lds, stream, a);
 }
 
 template <typename T>

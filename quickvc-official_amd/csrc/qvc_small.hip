@@ -101,11 +101,7 @@ int launch_gemv(const GemvArgs& a, void* stream) {
   if (a.rows <= 0) return QVC_OK;
   const size_t lds = ((size_t)gemv_g_floats(a.gin) + (size_t)kGR * a.gin) * 4;
   if (a.gin % 4 || a.gin > 512 || lds > 160 * 1024) return QVC_ERR_BAD_CONFIG;
-  static std::atomic<uint32_t> lds_ok{0};                  // > 64 KiB dynamic LDS: opt in once per device
-  if (!allow_big_lds(lds_ok, reinterpret_cast<const void*>(cond_gemv_kernel))) return QVC_ERR_LAUNCH;
-  hipLaunchKernelGGL(cond_gemv_kernel, dim3((unsigned)ceil_div(a.rows, kGR)), dim3(kGT), lds,
-                     static_cast<hipStream_t>(stream), a);
-  return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
+  return launch_big_lds<cond_gemv_kernel>(dim3((unsigned)ceil_div(a.rows, kGR)), dim3(kGT), lds, static_cast<hipStream_t>(stream), a);
 }
 
 // ------------------------------------------------------------------ sampling

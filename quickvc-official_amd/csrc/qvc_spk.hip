@@ -222,11 +222,7 @@ template <typename T, int KS, int KREG, int KLDS, int RING, bool LAST>
 static int launch_lstm_last(const LstmArgs& a, hipStream_t stream) {
   constexpr int HPs = KS * 32 + 8;
   const size_t lds = (size_t)2 * kSpkCols * HPs * sizeof(T) + (size_t)KS * KLDS * 8 * 1024;
-  auto kern = lstm_layer_kernel<T, KS, KREG, KLDS, RING, LAST>;
-  static std::atomic<uint32_t> lds_ok{0};                  // > 64 KiB dynamic LDS: opt in once per device
-  if (!allow_big_lds(lds_ok, reinterpret_cast<const void*>(kern))) return QVC_ERR_LAUNCH;
-  hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(a.P, kSpkCols)), dim3((unsigned)KS * 64), lds, stream, a);
-  return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
+  return launch_big_lds<lstm_layer_kernel<T, KS, KREG, KLDS, RING, LAST>>(dim3((unsigned)ceil_div(a.P, kSpkCols)), dim3((unsigned)KS * 64), lds, stream, a);
 }
 
 template <typename T, int KS, int KREG, int KLDS, int RING>

@@ -148,7 +148,7 @@ __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArg
         frag h;
         h[0] = O::cvt(v0.x); h[1] = O::cvt(v0.y); h[2] = O::cvt(v0.z); h[3] = O::cvt(v0.w);
         h[4] = O::cvt(v1.x); h[5] = O::cvt(v1.y); h[6] = O::cvt(v1.z); h[7] = O::cvt(v1.w);
-        *reinterpret_cast<frag*>(acts + r * RB + ((rotc(c8, sm) ^ swz(r, sm)) << 4)) = h;
+        *reinterpret_cast<frag*>(tile_at(acts, r, c8, RB, sm)) = h;
       }
     }
     __syncthreads();
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArg
 #pragma unroll
     for (int n = 0; n < NF; ++n) pacc[0][n] = f32x4{0.f, 0.f, 0.f, 0.f};
     const frag* app = static_cast<const frag*>(a.w_pre) + ((size_t)wm * a.pre_KS) * 64 + lane;
-    gemm_loop<T, 1, NF, QVC_PF_STACK>(pacc, app, a.pre_KS, a.pre_KS, 1, acts, RB, sm, lrow, lq, 0);
+    gemm_loop<T, 1, NF, QVC_PF_STACK>(pacc, app, a.pre_KS, a.pre_KS, 1, acts, RB, sm, lrow, lq);
     float4 bp = make_float4(0.f, 0.f, 0.f, 0.f);
     if (ch0 < a.H) bp = *reinterpret_cast<const float4*>(a.b_pre + ch0);
 #pragma unroll
@@ -282,7 +282,7 @@ __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArg
       };
       auto put_acts = [&](int n, const quad& o) {
         const int j = n * 16 + lrow;
-        *reinterpret_cast<quad*>(acts + j * RB + ((rotc(ch0 >> 3, sm) ^ swz(j, sm)) << 4) + (ch0 & 7) * 2) = o;
+        *reinterpret_cast<quad*>(tile_at(acts, j, ch0 >> 3, RB, sm) + (ch0 & 7) * 2) = o;
       };
       if constexpr (!ALIAS) {
 #pragma unroll
@@ -418,7 +418,7 @@ __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArg
         } else {
           h[0] = h[1] = h[2] = h[3] = (T)0.f;
         }
-        *reinterpret_cast<quad*>(acts + j * RB + ((rotc(ch0 >> 3, sm) ^ swz(j, sm)) << 4) + (ch0 & 7) * 2) = h;
+        *reinterpret_cast<quad*>(tile_at(acts, j, ch0 >> 3, RB, sm) + (ch0 & 7) * 2) = h;
       }
       __syncthreads();
       f32x4 qacc[PM][ON];
@@ -427,7 +427,7 @@ __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArg
 #pragma unroll
         for (int n = 0; n < ON; ++n) qacc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
       const frag* apq = static_cast<const frag*>(a.w_post) + ((size_t)wm * KS * PM) * 64 + lane;
-      gemm_loop<T, PM, ON, QVC_PF_STACK>(qacc, apq, KS, KS, 1, acts, RB, sm, lrow_e, lq, 0);
+      gemm_loop<T, PM, ON, QVC_PF_STACK>(qacc, apq, KS, KS, 1, acts, RB, sm, lrow_e, lq);
 #pragma unroll
       for (int m = 0; m < PM; ++m) {
         const int v = (wm * PM + m) * 16 + lq * 4;
@@ -480,18 +480,8 @@ int launch_wn_stack2_nf(const WnStackArgs& a, int batch, hipStream_t stream) {
   constexpr size_t lds = wn2_lds_bytes<KS, TAPS, NF>();
   static_assert(lds <= 160 * 1024, "one workgroup per CU");
   const dim3 grid((unsigned)ceil_div(a.T, NF * 16 - 16), (unsigned)batch), block(KS * 2 * 64);
-  if (a.w_post) {
-    auto kern = wn_stack2_kernel<T, KS, TAPS, 1, NF, RING>;
-    static std::atomic<uint32_t> lds_ok{0};                  // > 64 KiB dynamic LDS: opt in once per device
-    if (!allow_big_lds(lds_ok, reinterpret_cast<const void*>(kern))) return QVC_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, grid, block, lds, stream, a);
-  } else {
-    auto kern = wn_stack2_kernel<T, KS, TAPS, 0, NF, RING>;
-    static std::atomic<uint32_t> lds_ok{0};
-    if (!allow_big_lds(lds_ok, reinterpret_cast<const void*>(kern))) return QVC_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, grid, block, lds, stream, a);
-  }
-  return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
+  return a.w_post ? launch_big_lds<wn_stack2_kernel<T, KS, TAPS, 1, NF, RING>>(grid, block, lds, stream, a)
+                  : launch_big_lds<wn_stack2_kernel<T, KS, TAPS, 0, NF, RING>>(grid, block, lds, stream, a);
 }
 
 // wide: the 64-frame tile (NF = 5), else the 32-frame one
