@@ -313,6 +313,19 @@ int64_t qvc_spk_workspace_bytes(const qvc_config* cfg, int32_t utterances, int32
 int qvc_speaker_embed(const qvc_config* cfg, const void* spk_blob_dev, const float* mel, float* g,
                       int32_t utterances, int32_t mel_frames,
                       void* workspace, int64_t workspace_bytes, void* stream);
+/* The same for a RAGGED batch -- target recordings never have one length:
+ *   mel (U, n_mel, max_frames) fp32 padded, frames_dev[U] int32 ON THE DEVICE: valid frames per row
+ *   (clamped to [0, max_frames] on the device; the padding is never read, it may hold anything).
+ * Row u of g is bit-identical to qvc_speaker_embed on that row alone (utterances = 1, mel_frames =
+ * frames_dev[u]); a row of 0 frames gives a zero row.  One small launch builds a partial map on the
+ * device ({row, first frame, steps} per partial, exclusive scan of the rows' partial counts); the
+ * launches after it are sized from the cap utterances * partials(max_frames), and recurrence columns
+ * whose own steps are over keep their state -- no length is read on the host, so the call can be
+ * captured in a graph and replayed with other lengths.  Workspace: qvc_spk_ragged_workspace_bytes. */
+int64_t qvc_spk_ragged_workspace_bytes(const qvc_config* cfg, int32_t utterances, int32_t max_frames);
+int qvc_speaker_embed_ragged(const qvc_config* cfg, const void* spk_blob_dev, const float* mel,
+                             const int32_t* frames_dev, float* g, int32_t utterances, int32_t max_frames,
+                             void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- mel front-end: replaces mel_processing.wave_to_mel (mel_processing.py:15-98) ---------
  * The step in front of the speaker encoder on the target side (convert.py:75-77):
@@ -331,6 +344,30 @@ int qvc_mel_pack_tables(int32_t n_fft, int32_t hop, int32_t n_mels, const float*
 int64_t qvc_mel_workspace_bytes(int32_t n_fft, int32_t hop, int32_t utterances, int32_t samples);
 int qvc_wave_to_mel(const void* table_dev, int32_t n_fft, int32_t hop, int32_t n_mels,
                     const float* wave, float* mel, int32_t utterances, int32_t samples,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+/* The same for a RAGGED batch: wave (U, max_samples) fp32 padded; row u is the samples_dev[u] samples
+ * from start_dev[u] on (device int32 arrays, clamped to the row on the device; start_dev may be null
+ * = 0), reflect-padded at ITS two ends.  mel (U, n_mels, max_frames) with max_frames = the frame
+ * count of max_samples; frames_dev[U] receives each row's own count, frames at or past it are
+ * written as 0.0, a row no longer than the reflect pad (n_fft-hop)/2 gets 0 frames.  A valid frame
+ * is bit-identical to qvc_wave_to_mel on that row alone. */
+int64_t qvc_mel_ragged_workspace_bytes(int32_t n_fft, int32_t hop, int32_t utterances, int32_t max_samples);
+int qvc_wave_to_mel_ragged(const void* table_dev, int32_t n_fft, int32_t hop, int32_t n_mels,
+                           const float* wave, const int32_t* start_dev, const int32_t* samples_dev,
+                           float* mel, int32_t* frames_dev, int32_t utterances, int32_t max_samples,
+                           void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- silence trim in front of the mel (librosa.effects.trim in the reference, convert.py:65) ----
+ * For every row of wave (U, max_samples) with samples_dev[u] samples (clamped on the device): frames
+ * of frame_length samples at hop_length over the row zero-padded by frame_length/2 on both sides;
+ * a frame is kept when its RMS is less than top_db below the row's loudest frame;
+ *   start = first kept * hop_length, end = min(samples, (last kept + 1) * hop_length),
+ * written to start_dev[u] / len_dev[u] (= end - start).  A row shorter than frame_length is left
+ * whole.  Needs frame_length % (2 * hop_length) == 0 (QVC_ERR_BAD_CONFIG otherwise) and top_db > 0.
+ * The outputs feed qvc_wave_to_mel_ragged as they are. */
+int64_t qvc_trim_workspace_bytes(int32_t utterances, int32_t max_samples, int32_t frame_length, int32_t hop_length);
+int qvc_trim_bounds(const float* wave, const int32_t* samples_dev, int32_t* start_dev, int32_t* len_dev,
+                    int32_t utterances, int32_t max_samples, float top_db, int32_t frame_length, int32_t hop_length,
                     void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- posterior direction: enc_q and the forward flow (models.py:617-618) -------

@@ -34,7 +34,7 @@ import torch
 from .checkpoint import load_checkpoint
 from .dist import env_world, shard_indices
 from .config import get_hparams_from_file
-from .frontend import MelFrontend, load_wav, trim
+from .frontend import MelFrontend, load_wav
 from .model import SynthesizerTrn
 
 
@@ -60,6 +60,34 @@ def _load_units(src: str) -> torch.Tensor:
     if u.ndim != 2 or u.shape[1] != 256:
         raise ValueError(f"{_unit_path(src)}: expected (frames, 256), got {u.shape}")
     return torch.from_numpy(u).t().unsqueeze(0)               # (1, 256, frames), data_utils_new_new.py:121-122
+
+
+def wav_samples(path: str, sr: int) -> int:
+    """Sample count ``load_wav(path, sr)`` will return, from the wav HEADER only (memory-mapped: no payload is read)."""
+    from scipy.io import wavfile
+    try:
+        rate, data = wavfile.read(path, mmap=True)
+        n = int(data.shape[0])
+    except ValueError:                                                    # a sample format that cannot be mapped (24-bit)
+        return len(load_wav(path, sr))
+    if rate != sr:
+        from math import gcd
+        g = gcd(int(rate), int(sr))
+        n = -(-n * (sr // g) // (rate // g))                              # resample_poly: ceil(n * up / down)
+    return n
+
+
+def target_chunks(counts, rows: int = 64, max_bytes: int = 64 << 20):
+    """Chunks [lo, hi) of a list of sample counts sorted ascending: at most ``rows`` targets each, fewer where the padded
+    fp32 batch (rows x longest) would exceed ``max_bytes`` of upload."""
+    chunks, lo = [], 0
+    for i in range(len(counts)):
+        if i > lo and (i - lo >= rows or (i - lo + 1) * int(counts[i]) * 4 > max_bytes):
+            chunks.append((lo, i))
+            lo = i
+    if lo < len(counts):
+        chunks.append((lo, len(counts)))
+    return chunks
 
 
 def plan_batches(lengths, batch: int, max_pad: float = 0.25):
@@ -339,14 +367,42 @@ def convert_items(net_g, d, items, outdir: str, rank: int = 0, world: int = 1, b
             # mel front-end on the GPU (qvc_wave_to_mel; raises for configs it does not cover -- there is no CPU path);
             # speaker embeddings once per distinct target of this shard (the reference recomputes them per line, convert.py:64-77)
             front = MelFrontend(d.filter_length, d.n_mel_channels, d.sampling_rate, d.hop_length, d.win_length, d.mel_fmin, d.mel_fmax)
-            tgt_row, rows = {}, []
+            tgt_row, tgts = {}, []
             for i in mine:
                 tgt = items[i][2]
                 if tgt not in tgt_row:
-                    wav = torch.from_numpy(trim(load_wav(tgt, d.sampling_rate), top_db=20)).unsqueeze(0).cuda()
-                    tgt_row[tgt] = len(rows)
-                    rows.append(net_g.speaker_embed(front(wav)))          # (1, 80, F') -> (1, gin), HIP mel + HIP LSTM
-            table = torch.cat(rows, 0)
+                    tgt_row[tgt] = len(tgts)
+                    tgts.append(tgt)
+            # Ragged batches of targets (SynthesizerTrn.speaker_embed_waves: trim, mel and LSTM per batch on device
+            # lengths): the speaker encoder is latency-bound, a batch costs about what one target costs.  Sorted by
+            # sample count (wav headers only) so that a chunk pads little; the next chunk's files are read on a helper
+            # thread while this one is embedded.
+            counts = [wav_samples(t, d.sampling_rate) for t in tgts]
+            order = sorted(range(len(tgts)), key=lambda r: (counts[r], r))
+            chunks = target_chunks([counts[r] for r in order])
+            table = torch.empty(len(tgts), net_g.model_config["gin_channels"], device="cuda")
+            loaded = queue.Queue(maxsize=1)
+
+            def reader():
+                try:
+                    for lo, hi in chunks:
+                        loaded.put([load_wav(tgts[r], d.sampling_rate) for r in order[lo:hi]])
+                except Exception as exc:                                  # noqa: BLE001 -- re-raised by the consumer
+                    loaded.put(exc)
+
+            rt = threading.Thread(target=reader, daemon=True)
+            rt.start()
+            for lo, hi in chunks:
+                waves = loaded.get()
+                if isinstance(waves, Exception):
+                    raise waves
+                try:
+                    g = net_g.speaker_embed_waves(waves, front, trim_top_db=20)
+                except ValueError as exc:
+                    raise ValueError(f"{exc} (targets {[tgts[r] for r in order[lo:hi]]})") from exc
+                table[torch.as_tensor(order[lo:hi], device=table.device)] = g
+            rt.join()
+            rows = tgts
             g_rows = torch.zeros(len(items), table.shape[1], device=table.device)
             g_rows[torch.as_tensor(mine, device=table.device)] = table[torch.as_tensor([tgt_row[items[i][2]] for i in mine], device=table.device)]
             n_targets[0] = len(rows)

@@ -280,11 +280,28 @@ struct LstmArgs {
   const void* w_hh;     // [wave][k-step][8 fragments][64 lanes][8], see spk_hh_row
   void* hseq;           // [P16][S][HP] operand type (P, H padded to 16 / 32): input of the next layer (null on the last)
   float* hfin;          // [P][H] fp32: h after the last step (last layer only)
+  // Ragged batches (all null = the uniform layout above): partial p reads row prow[p] from frame pstart[p] for
+  // psteps[p] steps (see SpkMapArgs).  P and S are then the host-known caps -- they size the grid and stride the
+  // buffers --, phdr[0] is the number of partials and phdr[1] the step bound of the launch.
+  const int32_t* prow = nullptr; const int32_t* pstart = nullptr; const int32_t* psteps = nullptr;
+  const int32_t* phdr = nullptr;
 };
 
 struct SpkEmbedArgs {   // relu(linear(h)) / ||.||, mean over an utterance's partials (models.py:514-518,539)
   const float* hfin; const float* lw; const float* lb; float* g;
   int32_t utterances, n_part, H;
+  const int32_t* poff = nullptr;   // ragged batches: row u owns partials [poff[u], poff[u+1]); none = a zero row
+};
+
+// The partial map of a ragged batch, built on the device by one small launch: row u of frames[u] mel frames (clamped
+// to [0, F]) has spk_partials(frames[u]) partials (none at 0 frames); poff is the exclusive scan of those counts, every
+// partial gets one {row, first frame, steps} entry, entries past the count up to the cap P = U * spk_partials(F) get
+// 0 steps, hdr = {count, longest partial}.
+struct SpkMapArgs {
+  const int32_t* frames = nullptr;
+  int32_t U = 0, F = 0, P = 0;
+  int32_t* flen = nullptr; int32_t* poff = nullptr; int32_t* prow = nullptr; int32_t* pstart = nullptr;
+  int32_t* psteps = nullptr; int32_t* phdr = nullptr;
 };
 
 // Developer / test switches.  Process-wide integers that start at their production value and change ONLY through

@@ -10,6 +10,11 @@
 // magnitude is lane-local in the epilogue; no complex tensor, no FFT plan, nothing but the spectrogram is written.
 // The mel stage exploits the filters' sparsity (each triangle spans a few dozen bins): one thread per
 // (utterance, frame, filter) walks its own bin range.
+//
+// Ragged batches (qvc_wave_to_mel_ragged): every row brings its own (start, samples) from device arrays; the reflect
+// padding is applied at the row's own two ends and tiles still start at the row's frame 0, so a valid frame is the
+// same fmaf chain as in a call on that row alone.  Frames past a row's own count are written as 0.
+// qvc_trim_bounds (the silence trim in front of it, convert.py:65) is at the end of this file.
 #include <hip/hip_runtime.h>
 #include "qvc_launch_util.h"
 #include <cmath>
@@ -52,6 +57,9 @@ inline MelTable mel_table(int n_fft, int hop, int n_mels) {
   return t;
 }
 
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
 inline int mel_frames(int n_fft, int hop, int samples) {
   const int pad = (n_fft - hop) / 2;
   const int total = samples + 2 * pad;
@@ -61,7 +69,22 @@ inline int mel_frames(int n_fft, int hop, int samples) {
 struct StftArgs {
   const float* wave; int32_t samples, frames, n_fft, hop, pad, bins, binsP, ksteps;
   const float* dft; float* spec;     // spec: [U][frames][binsP]
+  // ragged batches (samples_dev set): rows are `samples` apart, row u is wave[start_dev[u] ..][0 .. samples_dev[u]) (both
+  // clamped to the row), `frames` is the count of the longest possible row and frames_dev[u] receives the row's own
+  const int32_t* start_dev = nullptr; const int32_t* samples_dev = nullptr; int32_t* frames_dev = nullptr;
 };
+
+// Row u of a ragged batch: first sample, length and frame count -- clamped on the device, never trusted.  A row no
+// longer than the reflect pad has no frame (the reflection needs pad < samples).
+struct MelRow { int start, samples, frames; };
+__device__ __forceinline__ MelRow mel_row(const int32_t* start_dev, const int32_t* samples_dev, int u, int stride, int n_fft, int hop,
+                                          int max_frames) {
+  MelRow r;
+  r.start = start_dev ? min(max(start_dev[u], 0), stride) : 0;
+  r.samples = min(max(samples_dev[u], 0), stride - r.start);
+  r.frames = r.samples > (n_fft - hop) / 2 ? min(mel_frames(n_fft, hop, r.samples), max_frames) : 0;
+  return r;
+}
 
 // LDS index of padded-waveform sample i of the staged piece (4 floats of padding per hop)
 __device__ __forceinline__ int mel_lds_idx(int i, int hop) { return i + (i / hop) * kMelPadEvery; }
@@ -75,6 +98,13 @@ __global__ __launch_bounds__(256) void stft_mag_kernel(const StftArgs a) {
   // stage padded samples [f0*hop, f0*hop + (kMelFrames-1)*hop + n_fft), reflect padding as F.pad(mode='reflect')
   const int piece = (kMelFrames - 1) * a.hop + a.n_fft;
   const float* wv = a.wave + (size_t)u * a.samples;
+  int samples = a.samples, frames = a.frames;
+  if (a.samples_dev) {
+    const MelRow r = mel_row(a.start_dev, a.samples_dev, u, a.samples, a.n_fft, a.hop, a.frames);
+    wv += r.start; samples = r.samples; frames = r.frames;
+    if (blockIdx.x == 0 && chunk == 0 && tid == 0) a.frames_dev[u] = frames;
+    if (f0 >= frames) return;                         // tile past the row's end (uniform, before the barrier)
+  }
   constexpr int kStageU = 8;                          // loads in flight per thread (one per loop trip = serialised round trips)
   for (int base = tid; base < piece; base += 256 * kStageU) {
     float v[kStageU];
@@ -83,9 +113,9 @@ __global__ __launch_bounds__(256) void stft_mag_kernel(const StftArgs a) {
       const int i = base + j * 256;
       int s = f0 * a.hop + i - a.pad;                 // index into the unpadded waveform
       if (s < 0) s = -s;
-      if (s >= a.samples) s = 2 * (a.samples - 1) - s;
+      if (s >= samples) s = 2 * (samples - 1) - s;
       v[j] = 0.f;
-      if (i < piece && s >= 0 && s < a.samples) v[j] = wv[s];   // frames past the end of the utterance read zeros
+      if (i < piece && s >= 0 && s < samples) v[j] = wv[s];   // frames past the end of the utterance read zeros
     }
 #pragma unroll
     for (int j = 0; j < kStageU; ++j) {
@@ -145,7 +175,7 @@ __global__ __launch_bounds__(256) void stft_mag_kernel(const StftArgs a) {
 #pragma unroll
     for (int n = 0; n < kMelNF; ++n) {
       const int f = f0 + n * 16 + col;
-      if (f >= a.frames) continue;
+      if (f >= frames) continue;
       const mf32x4 re = acc[2 * half][n], im = acc[2 * half + 1][n];
       float4 o;
       o.x = sqrtf(re[0] * re[0] + im[0] * im[0] + 1e-6f); o.y = sqrtf(re[1] * re[1] + im[1] * im[1] + 1e-6f);
@@ -158,6 +188,8 @@ __global__ __launch_bounds__(256) void stft_mag_kernel(const StftArgs a) {
 struct MelArgs {
   const float* spec; const float* basis; const int32_t* range; float* mel;
   int32_t utterances, frames, bins, binsP, n_mels;
+  // ragged batches (see StftArgs): frames at or past the row's own count are written as 0
+  const int32_t* start_dev = nullptr; const int32_t* samples_dev = nullptr; int32_t stride = 0, n_fft = 0, hop = 0;
 };
 
 // mel[u][m][f] = log(max(sum_b basis[m][b] * spec[u][f][b], 1e-5))   (mel_processing.py:70-73, :8-9)
@@ -167,6 +199,7 @@ __global__ __launch_bounds__(256) void mel_log_kernel(const MelArgs a) {
     const int f = (int)(i % a.frames);
     const int m = (int)((i / a.frames) % a.n_mels);
     const int u = (int)(i / ((size_t)a.frames * a.n_mels));
+    if (a.samples_dev && f >= mel_row(a.start_dev, a.samples_dev, u, a.stride, a.n_fft, a.hop, a.frames).frames) { a.mel[i] = 0.f; continue; }
     const int lo = a.range[2 * m], hi = a.range[2 * m + 1];
     const float* sp = a.spec + ((size_t)u * a.frames + f) * a.binsP;
     const float* bs = a.basis + (size_t)m * a.bins;
@@ -238,9 +271,10 @@ extern "C" int64_t qvc_mel_workspace_bytes(int32_t n_fft, int32_t hop, int32_t u
   return align_up((int64_t)utterances * frames * binsP * 4, 256);
 }
 
-extern "C" int qvc_wave_to_mel(const void* table_dev, int32_t n_fft, int32_t hop, int32_t n_mels,
-                               const float* wave, float* mel, int32_t utterances, int32_t samples,
-                               void* workspace, int64_t workspace_bytes, void* stream) {
+// the two launches of both entry points; samples_dev == null: every row is `samples` long
+static int wave_to_mel(const void* table_dev, int32_t n_fft, int32_t hop, int32_t n_mels, const float* wave,
+                       const int32_t* start_dev, const int32_t* samples_dev, float* mel, int32_t* frames_dev,
+                       int32_t utterances, int32_t samples, void* workspace, int64_t workspace_bytes, void* stream) {
   if (!table_dev || !wave || !mel || !workspace) return QVC_ERR_BAD_ARG;
   int st = mel_validate(n_fft, hop, n_mels);
   if (st != QVC_OK) return st;
@@ -256,6 +290,7 @@ extern "C" int qvc_wave_to_mel(const void* table_dev, int32_t n_fft, int32_t hop
   sa.wave = wave; sa.samples = samples; sa.frames = frames; sa.n_fft = n_fft; sa.hop = hop; sa.pad = (n_fft - hop) / 2;
   sa.bins = t.bins; sa.binsP = (int)align_up(t.bins, 4); sa.ksteps = t.ksteps;
   sa.dft = reinterpret_cast<const float*>(tb + t.dft_off); sa.spec = static_cast<float*>(workspace);
+  sa.start_dev = start_dev; sa.samples_dev = samples_dev; sa.frames_dev = frames_dev;
   const int piece = (kMelFrames - 1) * hop + n_fft;
   const size_t lds = (size_t)(piece + (piece / hop + 1) * kMelPadEvery) * 4;
   if (lds > 160 * 1024) return QVC_ERR_BAD_CONFIG;
@@ -265,7 +300,126 @@ extern "C" int qvc_wave_to_mel(const void* table_dev, int32_t n_fft, int32_t hop
   ma.spec = sa.spec; ma.basis = reinterpret_cast<const float*>(tb + t.basis_off);
   ma.range = reinterpret_cast<const int32_t*>(tb + t.range_off); ma.mel = mel;
   ma.utterances = utterances; ma.frames = frames; ma.bins = t.bins; ma.binsP = sa.binsP; ma.n_mels = n_mels;
+  ma.start_dev = start_dev; ma.samples_dev = samples_dev; ma.stride = samples; ma.n_fft = n_fft; ma.hop = hop;
   const size_t total = (size_t)utterances * n_mels * frames;
   hipLaunchKernelGGL(mel_log_kernel, dim3((unsigned)std::min<size_t>(4096, (total + 255) / 256)), dim3(256), 0, s, ma);
+  return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
+}
+
+extern "C" int qvc_wave_to_mel(const void* table_dev, int32_t n_fft, int32_t hop, int32_t n_mels,
+                               const float* wave, float* mel, int32_t utterances, int32_t samples,
+                               void* workspace, int64_t workspace_bytes, void* stream) {
+  return wave_to_mel(table_dev, n_fft, hop, n_mels, wave, nullptr, nullptr, mel, nullptr, utterances, samples, workspace,
+                     workspace_bytes, stream);
+}
+
+extern "C" int64_t qvc_mel_ragged_workspace_bytes(int32_t n_fft, int32_t hop, int32_t utterances, int32_t max_samples) {
+  return qvc_mel_workspace_bytes(n_fft, hop, utterances, max_samples);     // the spectrogram of the longest possible rows
+}
+
+extern "C" int qvc_wave_to_mel_ragged(const void* table_dev, int32_t n_fft, int32_t hop, int32_t n_mels,
+                                      const float* wave, const int32_t* start_dev, const int32_t* samples_dev,
+                                      float* mel, int32_t* frames_dev, int32_t utterances, int32_t max_samples,
+                                      void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!samples_dev || !frames_dev) return QVC_ERR_BAD_ARG;
+  return wave_to_mel(table_dev, n_fft, hop, n_mels, wave, start_dev, samples_dev, mel, frames_dev, utterances, max_samples,
+                     workspace, workspace_bytes, stream);
+}
+
+// ---------------------------------------------------------------- silence trim (frontend.trim; convert.py:65)
+// Frame i of a row covers samples [i*hop - fl/2, i*hop + fl/2) of the zero-padded row.  With fl/2 a multiple of hop a
+// frame is fl/hop whole hop-sized blocks, so the squares are summed once per block (first launch) and a frame's mean
+// square is a sum of fl/hop block sums (second launch, one workgroup per row).
+namespace qvc {
+
+struct TrimArgs {
+  const float* wave; const int32_t* samples_dev; int32_t* start_dev; int32_t* len_dev; float* bsum;   // bsum: [U][nblk]
+  int32_t utterances, max_samples, nblk, frame_length, hop;
+  float ratio;      // 10^(-top_db / 10): the threshold on mean squares
+};
+
+__global__ __launch_bounds__(256) void trim_blocksum_kernel(const TrimArgs a) {
+  const int u = blockIdx.y, j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int n = min(max(a.samples_dev[u], 0), a.max_samples);
+  if (j >= a.nblk || (int64_t)j * a.hop >= n) return;           // blocks past the row's end are never read
+  const float* wv = a.wave + (size_t)u * a.max_samples;
+  const int s0 = j * a.hop, s1 = min(n, s0 + a.hop);
+  float s = 0.f;
+  for (int i = s0 + lane; i < s1; i += 64) { const float v = wv[i]; s = fmaf(v, v, s); }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if (lane == 0) a.bsum[(size_t)u * a.nblk + j] = s;
+}
+
+__global__ __launch_bounds__(256) void trim_bounds_kernel(const TrimArgs a) {
+  __shared__ float s_f[4];
+  __shared__ int s_lo[4], s_hi[4];
+  const int u = blockIdx.x, tid = threadIdx.x;
+  const int n = min(max(a.samples_dev[u], 0), a.max_samples);
+  if (n < a.frame_length) {                                     // frontend.trim: too short to frame, unchanged
+    if (tid == 0) { a.start_dev[u] = 0; a.len_dev[u] = n; }
+    return;
+  }
+  const int bpf = a.frame_length / a.hop, back = bpf / 2;       // blocks per frame, blocks of left padding
+  const int nblk = (n + a.hop - 1) / a.hop, nfr = 1 + n / a.hop;
+  const float* bs = a.bsum + (size_t)u * a.nblk;
+  const float inv = 1.f / (float)a.frame_length;
+  auto frame_ms = [&](int i) {
+    float s = 0.f;
+    for (int b = max(i - back, 0); b < min(i - back + bpf, nblk); ++b) s += bs[b];
+    return fmaxf(s * inv, 1e-20f);                              // rms floored at 1e-10
+  };
+  float mx = 0.f;
+  for (int i = tid; i < nfr; i += 256) mx = fmaxf(mx, frame_ms(i));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  if ((tid & 63) == 0) s_f[tid >> 6] = mx;
+  __syncthreads();
+  const float thr = fmaxf(fmaxf(s_f[0], s_f[1]), fmaxf(s_f[2], s_f[3])) * a.ratio;
+  int lo = nfr, hi = -1;
+  for (int i = tid; i < nfr; i += 256)
+    if (frame_ms(i) > thr) { lo = min(lo, i); hi = max(hi, i); }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { lo = min(lo, __shfl_xor(lo, o)); hi = max(hi, __shfl_xor(hi, o)); }
+  if ((tid & 63) == 0) { s_lo[tid >> 6] = lo; s_hi[tid >> 6] = hi; }
+  __syncthreads();
+  if (tid == 0) {
+    lo = min(min(s_lo[0], s_lo[1]), min(s_lo[2], s_lo[3]));
+    hi = max(max(s_hi[0], s_hi[1]), max(s_hi[2], s_hi[3]));
+    const int start = hi < 0 ? 0 : lo * a.hop;
+    const int end = hi < 0 ? 0 : (int)min((int64_t)n, ((int64_t)hi + 1) * a.hop);
+    a.start_dev[u] = start; a.len_dev[u] = end - start;
+  }
+}
+
+static int trim_validate(int frame_length, int hop) {
+  if (hop < 1 || frame_length < 2 * hop || frame_length % (2 * hop) || frame_length > (1 << 20)) return QVC_ERR_BAD_CONFIG;
+  return QVC_OK;
+}
+
+}  // namespace qvc
+
+extern "C" int64_t qvc_trim_workspace_bytes(int32_t utterances, int32_t max_samples, int32_t frame_length, int32_t hop_length) {
+  if (utterances <= 0 || max_samples <= 0) return QVC_ERR_BAD_ARG;
+  if (trim_validate(frame_length, hop_length) != QVC_OK) return QVC_ERR_BAD_CONFIG;
+  return align_up((int64_t)utterances * ceil_div(max_samples, hop_length) * 4, 256);
+}
+
+extern "C" int qvc_trim_bounds(const float* wave, const int32_t* samples_dev, int32_t* start_dev, int32_t* len_dev,
+                               int32_t utterances, int32_t max_samples, float top_db, int32_t frame_length, int32_t hop_length,
+                               void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!wave || !samples_dev || !start_dev || !len_dev || !workspace || !(top_db > 0.f)) return QVC_ERR_BAD_ARG;
+  const int64_t need = qvc_trim_workspace_bytes(utterances, max_samples, frame_length, hop_length);
+  if (need < 0) return (int)need;
+  if (workspace_bytes < need) return QVC_ERR_SMALL_BUFFER;
+  if (utterances > 65535) return QVC_ERR_BAD_ARG;
+  TrimArgs a;
+  a.wave = wave; a.samples_dev = samples_dev; a.start_dev = start_dev; a.len_dev = len_dev; a.bsum = static_cast<float*>(workspace);
+  a.utterances = utterances; a.max_samples = max_samples; a.nblk = ceil_div(max_samples, hop_length);
+  a.frame_length = frame_length; a.hop = hop_length; a.ratio = (float)std::pow(10.0, -(double)top_db / 10.0);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(trim_blocksum_kernel, dim3((unsigned)ceil_div(a.nblk, 4), (unsigned)utterances), dim3(256), 0, s, a);
+  if (hipGetLastError() != hipSuccess) return QVC_ERR_LAUNCH;
+  hipLaunchKernelGGL(trim_bounds_kernel, dim3((unsigned)utterances), dim3(256), 0, s, a);
   return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
 }

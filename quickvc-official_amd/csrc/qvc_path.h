@@ -506,4 +506,56 @@ int spk_path(const SpkPlan& S, int dtype, const char* blob, char* ws, const SpkW
   return be.spk_embed(ea);
 }
 
+// ---- the same for a ragged batch: mel (U, n_mel, F) padded, frames[u] valid frames per row, on the device.  One
+// small launch builds the partial map (SpkMapArgs); every launch after it is sized from the host-known cap
+// (U * spk_partials(F) partials of spk_steps(F) steps) and takes rows, starts and step counts from the map, so no
+// length is read on the host.  The input projections mask frames past a row's (a partial's) end through the convs'
+// own ragged staging: the padding is never read.  Backend adds:  int spk_map(const SpkMapArgs&);
+// W = carve_spk_ragged_workspace(S, U, F).
+template <class Backend>
+int spk_path_ragged(const SpkPlan& S, int dtype, const char* blob, char* ws, const SpkWorkspace& W, const float* mel,
+                    const int32_t* frames, float* g, int U, int F, Backend& be) {
+  const int H = S.H, n_part = spk_partials(F), St = spk_steps(F), P = U * n_part;
+  auto i32 = [&](int64_t off) { return reinterpret_cast<int32_t*>(ws + off); };
+  SpkMapArgs ma;
+  ma.frames = frames; ma.U = U; ma.F = F; ma.P = P;
+  ma.flen = i32(W.flen); ma.poff = i32(W.poff); ma.prow = i32(W.prow); ma.pstart = i32(W.pstart);
+  ma.psteps = i32(W.psteps); ma.phdr = i32(W.phdr);
+  int rc = be.spk_map(ma);
+  if (rc != QVC_OK) return rc;
+  for (int l = 0; l < kSpkLayers; ++l) {
+    const ConvDesc& d = S.ih[l];
+    ConvArgs ca;
+    ca.w = blob + d.w_off; ca.bias = reinterpret_cast<const float*>(blob + d.b_off);
+    conv_geometry(ca, d);
+    int batch;
+    if (l == 0) {     // once per mel frame per row, as in the uniform path
+      ca.x = mel; ca.x_kind = XK_F32_CM; ca.x_bs = (int64_t)S.n_mel * F; ca.x_ts = F; ca.T_in = F;
+      ca.Nq = F; ca.T_out = F; ca.rg.lens = ma.flen;
+      ca.y32 = reinterpret_cast<float*>(ws + W.xp0); ca.y32_bs = (int64_t)F * 4 * H; ca.y32_ts = 4 * H;
+      batch = U;
+    } else {
+      ca.x = ws + W.hseq; ca.x_kind = XK_OP_FM; ca.x_bs = (int64_t)St * S.HP; ca.x_ts = S.HP; ca.T_in = St;
+      ca.Nq = St; ca.T_out = St; ca.rg.lens = ma.psteps;
+      ca.y32 = reinterpret_cast<float*>(ws + W.xp); ca.y32_bs = (int64_t)St * 4 * H; ca.y32_ts = 4 * H;
+      batch = P;
+    }
+    rc = be.conv(d, ca, batch, EPI_STD, dtype);
+    if (rc != QVC_OK) return rc;
+    LstmArgs la;
+    la.xp = reinterpret_cast<const float*>(ws + (l == 0 ? W.xp0 : W.xp));
+    la.shared = l == 0 ? 1 : 0;
+    la.F = F; la.n_part = n_part; la.S = St; la.P = P; la.H = H;
+    la.w_hh = blob + S.hh_off[l];
+    la.hseq = l + 1 < kSpkLayers ? ws + W.hseq : nullptr;
+    la.hfin = l + 1 < kSpkLayers ? nullptr : reinterpret_cast<float*>(ws + W.hfin);
+    la.prow = ma.prow; la.pstart = ma.pstart; la.psteps = ma.psteps; la.phdr = ma.phdr;
+    rc = be.lstm(la, S.KS, dtype);
+    if (rc != QVC_OK) return rc;
+  }
+  SpkEmbedArgs ea{reinterpret_cast<const float*>(ws + W.hfin), reinterpret_cast<const float*>(blob + S.lin_w_off),
+                  reinterpret_cast<const float*>(blob + S.lin_b_off), g, U, n_part, H, ma.poff};
+  return be.spk_embed(ea);
+}
+
 }  // namespace qvc

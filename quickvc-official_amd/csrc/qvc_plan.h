@@ -540,6 +540,13 @@ struct SpkWorkspace {
   int64_t hseq = 0;   // op   [P16][S][HP]      hidden sequence of the previous layer (P, H padded: unconditional stores)
   int64_t hfin = 0;   // fp32 [P][H]            final hidden state of the last layer
   int64_t bytes = 0;
+  // ragged batches only (carve_spk_ragged_workspace; 0 in the uniform layout): the partial map, all int32
+  int64_t flen = 0;   // [U]      frame counts clamped to [0, F]
+  int64_t poff = 0;   // [U+1]    exclusive scan of the rows' partial counts
+  int64_t prow = 0;   // [Pcap]   source row of partial p
+  int64_t pstart = 0; // [Pcap]   its first mel frame
+  int64_t psteps = 0; // [Pcap]   its steps (0 past the device-side count)
+  int64_t phdr = 0;   // [2]      partial count, step bound (the longest partial)
 };
 
 inline SpkWorkspace carve_spk_workspace(const SpkPlan& S, int U, int F) {
@@ -551,6 +558,23 @@ inline SpkWorkspace carve_spk_workspace(const SpkPlan& S, int U, int F) {
   W.xp = take(P * St * 4 * S.H * 4);
   W.hseq = take(align_up(P, kSpkCols) * St * S.HP * 2);
   W.hfin = take(P * S.H * 4);
+  W.bytes = off;
+  return W;
+}
+
+// Ragged batch of U rows of at most F frames: the uniform layout at the cap (Pcap = U * spk_partials(F) partials of
+// spk_steps(F) steps) followed by the device-built partial map.  A row of 0 frames has no partial.
+inline SpkWorkspace carve_spk_ragged_workspace(const SpkPlan& S, int U, int F) {
+  SpkWorkspace W = carve_spk_workspace(S, U, F);
+  int64_t off = W.bytes;
+  auto take = [&](int64_t n) { int64_t o = off; off = align_up(off + n, 256); return o; };
+  const int64_t P = (int64_t)U * spk_partials(F);
+  W.flen = take((int64_t)U * 4);
+  W.poff = take(((int64_t)U + 1) * 4);
+  W.prow = take(P * 4);
+  W.pstart = take(P * 4);
+  W.psteps = take(P * 4);
+  W.phdr = take(2 * 4);
   W.bytes = off;
   return W;
 }

@@ -22,7 +22,9 @@
 
 namespace qvc {
 
-template <typename T, int KS, int KREG, int KLDS, int RING, bool LAST>
+// RAG: the ragged form (LstmArgs::prow ...).  Its own instantiation: the uniform one sits at the register limit at
+// KS = 8 and keeps its code as it was.
+template <typename T, int KS, int KREG, int KLDS, int RING, bool LAST, bool RAG>
 __global__ __launch_bounds__(512) void lstm_layer_kernel(const LstmArgs a) {
   using O = Op<T>;
   using frag = typename O::frag;
@@ -38,12 +40,21 @@ __global__ __launch_bounds__(512) void lstm_layer_kernel(const LstmArgs a) {
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int col = lane & 15, quad = lane >> 4;
+  // ragged: the partial count and the step bound come from the device; a workgroup past the count has nothing to do
+  // (uniform exit, before any barrier)
+  const int P = RAG ? min(a.phdr[0], a.P) : a.P;
+  const int S = RAG ? min(a.phdr[1], a.S) : a.S;
+  if (RAG && (int)blockIdx.x * kSpkCols >= P) return;
   const int p = blockIdx.x * kSpkCols + col;
-  const int pc = p < a.P ? p : a.P - 1;     // columns past the last partial replay it (their stores land in padding)
+  const int pc = p < P ? p : P - 1;         // columns past the last partial replay it (their stores land in padding)
   const int H = a.H, H4 = 4 * H;
+  // steps of THIS column: past them its c and h freeze, so a short row ends with the state of its last real step
+  const int steps = RAG ? a.psteps[pc] : S;
 
   const float* xb;
-  if (a.shared) {
+  if (RAG && a.shared) {
+    xb = a.xp + ((size_t)a.prow[pc] * a.F + a.pstart[pc]) * H4;
+  } else if (a.shared) {
     const int u = pc / a.n_part, i = pc - u * a.n_part;
     const int start = i + 1 < a.n_part ? i * kSpkHop : (a.F > kSpkPartial ? a.F - kSpkPartial : 0);
     xb = a.xp + ((size_t)u * a.F + start) * H4;
@@ -90,7 +101,7 @@ __global__ __launch_bounds__(512) void lstm_layer_kernel(const LstmArgs a) {
   T* hs = LAST ? nullptr : static_cast<T*>(a.hseq) + (size_t)p * a.S * HP + unit0;   // [P16][S][HP]
   __syncthreads();
 
-  for (int t = 0; t < a.S; ++t) {
+  for (int t = 0; t < S; ++t) {
     // the stream addresses repeat every step; keep hipcc from hoisting those loads out of the loop (it would
     // try to hold all of W_hh in registers and spill)
     // (an opaque OFFSET, not an opaque pointer: the latter loses the address space and turns the stream into
@@ -144,7 +155,7 @@ __global__ __launch_bounds__(512) void lstm_layer_kernel(const LstmArgs a) {
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int f = 0; f < 8; ++f) acc[f] += xv[f];
-      const float* xn = xb + (size_t)(t + 1 < a.S ? t + 1 : t) * H4;
+      const float* xn = xb + (size_t)(RAG ? (t + 1 < steps ? t + 1 : steps - 1) : (t + 1 < a.S ? t + 1 : t)) * H4;   // never past the column's own frames
 #pragma unroll
       for (int f = 0; f < 8; ++f) xv[f] = *reinterpret_cast<const f32x4*>(xn + ro[f]);
     }
@@ -156,8 +167,18 @@ __global__ __launch_bounds__(512) void lstm_layer_kernel(const LstmArgs a) {
       for (int j = 0; j < 4; ++j) {
         const float gi = fast_sigmoid(acc[0 + h][j]), gf = fast_sigmoid(acc[2 + h][j]);
         const float gg = fast_tanh(acc[4 + h][j]), go = fast_sigmoid(acc[6 + h][j]);
-        c[h][j] = gf * c[h][j] + gi * gg;
-        hf[h][j] = live[h] ? go * fast_tanh(c[h][j]) : 0.f;
+        if constexpr (RAG) {
+          // spelled out: the uniform instantiations contract their cell update to fma(gi, gg, gf * c) (one rounding of
+          // gf * c, then one of the sum); next to the selects below hipcc leaves "gf * c + gi * gg" unfused, and a row
+          // would differ from the uniform call on it in the last bit of c, growing over the steps
+          const float cn = __builtin_fmaf(gi, gg, gf * c[h][j]);
+          const float hn = live[h] ? go * fast_tanh(cn) : 0.f;
+          c[h][j] = t < steps ? cn : c[h][j];
+          hf[h][j] = t < steps ? hn : hf[h][j];
+        } else {
+          c[h][j] = gf * c[h][j] + gi * gg;
+          hf[h][j] = live[h] ? go * fast_tanh(c[h][j]) : 0.f;
+        }
         hq[j] = O::cvt(hf[h][j]);
       }
       *reinterpret_cast<typename O::quad*>(hnxt + unit0 + h * 16) = hq;
@@ -166,7 +187,7 @@ __global__ __launch_bounds__(512) void lstm_layer_kernel(const LstmArgs a) {
     __syncthreads();
   }
   if constexpr (LAST) {
-    if (p < a.P) {
+    if (p < P) {
 #pragma unroll
       for (int h = 0; h < 2; ++h)
         if (live[h]) *reinterpret_cast<float4*>(a.hfin + (size_t)p * H + unit0 + h * 16) = make_float4(hf[h][0], hf[h][1], hf[h][2], hf[h][3]);
@@ -178,14 +199,17 @@ __global__ __launch_bounds__(512) void lstm_layer_kernel(const LstmArgs a) {
 // (models.py:539), not re-normalised (:540).  One workgroup per utterance.
 __global__ __launch_bounds__(256) void spk_embed_kernel(const SpkEmbedArgs a) {
   const float* hfin = a.hfin; const float* lw = a.lw; const float* lb = a.lb; float* g = a.g;
-  const int n_part = a.n_part, H = a.H;
+  const int H = a.H;
   __shared__ float s_h[512];
   __shared__ float s_red[4];
   const int u = blockIdx.x, tid = threadIdx.x;
+  // ragged batches: the row's own partials, in the same order (uniform per workgroup: the loop holds barriers)
+  const int p0 = a.poff ? a.poff[u] : u * a.n_part;
+  const int n_part = a.poff ? a.poff[u + 1] - p0 : a.n_part;
   float mean[2] = {0.f, 0.f};
   for (int i = 0; i < n_part; ++i) {
     __syncthreads();
-    for (int k = tid; k < H; k += 256) s_h[k] = hfin[((size_t)u * n_part + i) * H + k];
+    for (int k = tid; k < H; k += 256) s_h[k] = hfin[((size_t)p0 + i) * H + k];
     __syncthreads();
     float e[2] = {0.f, 0.f};
     float ss = 0.f;
@@ -214,20 +238,62 @@ __global__ __launch_bounds__(256) void spk_embed_kernel(const SpkEmbedArgs a) {
 #pragma unroll
   for (int r = 0; r < 2; ++r) {
     const int row = tid + r * 256;
-    if (row < H) g[(size_t)u * H + row] = mean[r] / (float)n_part;
+    if (row < H) g[(size_t)u * H + row] = n_part > 0 ? mean[r] / (float)n_part : 0.f;   // a row of 0 frames: zeros
   }
+}
+
+// The partial map of a ragged batch (SpkMapArgs).  One workgroup: thread i owns a contiguous run of rows, the runs'
+// partial counts are scanned in LDS, then every thread writes the entries of its rows.
+__global__ __launch_bounds__(256) void spk_map_kernel(const SpkMapArgs a) {
+  __shared__ int s_cnt[256];
+  __shared__ int s_max[256];
+  const int tid = threadIdx.x;
+  const int per = (a.U + 255) / 256, u0 = tid * per, u1 = min(a.U, u0 + per);
+  auto parts = [](int f) { return f > kSpkPartial ? (f - kSpkPartial + kSpkHop - 1) / kSpkHop + 1 : (f > 0 ? 1 : 0); };
+  int cnt = 0, mx = 0;
+  for (int u = u0; u < u1; ++u) {
+    const int f = min(max(a.frames[u], 0), a.F);     // lengths are clamped, not trusted
+    a.flen[u] = f;
+    cnt += parts(f);
+    mx = max(mx, min(f, kSpkPartial));
+  }
+  s_cnt[tid] = cnt; s_max[tid] = mx;
+  __syncthreads();
+  int base = 0, total = 0, smax = 0;
+  for (int i = 0; i < 256; ++i) {                    // 256 LDS broadcasts: nothing next to the recurrence that follows
+    const int c = s_cnt[i];
+    base += i < tid ? c : 0;
+    total += c;
+    smax = max(smax, s_max[i]);
+  }
+  for (int u = u0; u < u1; ++u) {
+    const int f = min(max(a.frames[u], 0), a.F);
+    const int n = parts(f);
+    a.poff[u] = base;
+    for (int i = 0; i < n; ++i) {
+      a.prow[base + i] = u;
+      a.pstart[base + i] = i + 1 < n ? i * kSpkHop : (f > kSpkPartial ? f - kSpkPartial : 0);   // spk_start
+      a.psteps[base + i] = min(f, kSpkPartial);                                                 // spk_steps
+    }
+    base += n;
+  }
+  if (tid == 0) { a.poff[a.U] = total; a.phdr[0] = total; a.phdr[1] = smax; }
+  for (int p = total + tid; p < a.P; p += 256) { a.prow[p] = 0; a.pstart[p] = 0; a.psteps[p] = 0; }
 }
 
 template <typename T, int KS, int KREG, int KLDS, int RING, bool LAST>
 static int launch_lstm_last(const LstmArgs& a, hipStream_t stream) {
   constexpr int HPs = KS * 32 + 8;
   const size_t lds = (size_t)2 * kSpkCols * HPs * sizeof(T) + (size_t)KS * KLDS * 8 * 1024;
-  return launch_big_lds<lstm_layer_kernel<T, KS, KREG, KLDS, RING, LAST>>(dim3((unsigned)ceil_div(a.P, kSpkCols)), dim3((unsigned)KS * 64), lds, stream, a);
+  const dim3 grid((unsigned)ceil_div(a.P, kSpkCols)), block((unsigned)KS * 64);   // ragged: a.P is the cap
+  if (a.prow) return launch_big_lds<lstm_layer_kernel<T, KS, KREG, KLDS, RING, LAST, true>>(grid, block, lds, stream, a);
+  return launch_big_lds<lstm_layer_kernel<T, KS, KREG, KLDS, RING, LAST, false>>(grid, block, lds, stream, a);
 }
 
 template <typename T, int KS, int KREG, int KLDS, int RING>
 static int launch_lstm_variant(const LstmArgs& a, hipStream_t stream) {
   if ((a.hseq == nullptr) == (a.hfin == nullptr)) return QVC_ERR_BAD_ARG;
+  if (a.prow && (!a.pstart || !a.psteps || !a.phdr)) return QVC_ERR_BAD_ARG;
   return a.hseq ? launch_lstm_last<T, KS, KREG, KLDS, RING, false>(a, stream) : launch_lstm_last<T, KS, KREG, KLDS, RING, true>(a, stream);
 }
 
@@ -269,6 +335,10 @@ struct SpkHipBackend {
     hipLaunchKernelGGL(spk_embed_kernel, dim3((unsigned)a.utterances), dim3(256), 0, stream, a);
     return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
   }
+  int spk_map(const SpkMapArgs& a) {
+    hipLaunchKernelGGL(spk_map_kernel, dim3(1), dim3(256), 0, stream, a);
+    return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
+  }
 };
 
 }  // namespace qvc
@@ -295,6 +365,28 @@ extern "C" int qvc_speaker_embed(const qvc_config* cfg, const void* spk_blob_dev
   SpkHipBackend be{static_cast<hipStream_t>(stream)};
   return spk_path(S, dec_dtype(*cfg), static_cast<const char*>(spk_blob_dev), static_cast<char*>(workspace), W, mel, g,
                   U, F, be);
+}
+
+extern "C" int64_t qvc_spk_ragged_workspace_bytes(const qvc_config* cfg, int32_t utterances, int32_t max_frames) {
+  if (!cfg || utterances <= 0 || max_frames <= 0) return QVC_ERR_BAD_ARG;
+  SpkPlan S = build_spk_plan(*cfg);
+  if (S.status != QVC_OK) return S.status;
+  return carve_spk_ragged_workspace(S, utterances, max_frames).bytes;
+}
+
+extern "C" int qvc_speaker_embed_ragged(const qvc_config* cfg, const void* spk_blob_dev, const float* mel,
+                                        const int32_t* frames_dev, float* g, int32_t utterances, int32_t max_frames,
+                                        void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!cfg || !spk_blob_dev || !mel || !frames_dev || !g || !workspace || utterances <= 0 || max_frames <= 0) return QVC_ERR_BAD_ARG;
+  SpkPlan S = build_spk_plan(*cfg);
+  if (S.status != QVC_OK) return S.status;
+  const int U = utterances, F = max_frames;
+  const SpkWorkspace W = carve_spk_ragged_workspace(S, U, F);
+  if (workspace_bytes < W.bytes) return QVC_ERR_SMALL_BUFFER;
+  if ((int64_t)U * spk_partials(F) > (1 << 20)) return QVC_ERR_BAD_ARG;
+  SpkHipBackend be{static_cast<hipStream_t>(stream)};
+  return spk_path_ragged(S, dec_dtype(*cfg), static_cast<const char*>(spk_blob_dev), static_cast<char*>(workspace), W, mel,
+                         frames_dev, g, U, F, be);
 }
 #ifdef QVC_SATCOUNT
 namespace qvc { QVC_SAT_READER(sat_count_spk) }

@@ -202,17 +202,46 @@ class QvcEngine:
                                             torch.cuda.current_stream(self.device).cuda_stream)
         L.check(self.lib, st, "qvc_stream_reset_slot")
 
-    @_on_device
-    def speaker_embed(self, mel: torch.Tensor) -> torch.Tensor:
-        """SpeakerEncoder.embed_utterance for a batch (models.py:528-546): mel (U, n_mel, F) -> g (U, gin)."""
-        if mel.dim() != 3 or mel.shape[1] != int(self.cfg.n_mel_channels) or mel.shape[2] < 1:
-            raise ValueError(f"mel must be (U, {int(self.cfg.n_mel_channels)}, frames), got {tuple(mel.shape)}")
+    def _pack_spk(self) -> None:
         if self._spk_blob is None:
             if not self._spk_sd:
                 raise L.QvcError("the state dict holds no enc_spk.* weights")
             host = L.pack_weights(self.lib, self.cfg, self._spk_sd, which="spk")
             self._spk_blob = _aligned_empty(host.numel(), self.device)
             self._spk_blob.copy_(host)
+
+    @_on_device
+    def speaker_embed_ragged(self, mel: torch.Tensor, frames: torch.Tensor, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """embed_utterance for rows of DIFFERENT lengths: mel (U, n_mel, Fmax) padded (the padding's content is ignored),
+        frames (U,) int32 valid frames per row -- on the device it is never read on the host, so the call can sit in a
+        captured graph -- -> g (U, gin).  Row u equals ``speaker_embed(mel[u:u+1, :, :frames[u]])`` bit for bit; a row
+        of 0 frames gives zeros.  ``ws``: a caller-owned workspace (graph owners); default = the shared one."""
+        if mel.dim() != 3 or mel.shape[1] != int(self.cfg.n_mel_channels) or mel.shape[2] < 1 or tuple(frames.shape) != (mel.shape[0],):
+            raise ValueError(f"mel must be (U, {int(self.cfg.n_mel_channels)}, frames) and frames (U,), got {tuple(mel.shape)}, {tuple(frames.shape)}")
+        self._pack_spk()
+        mel = self._f32(mel, self.device)
+        frames = frames.to(device=self.device, dtype=torch.int32).contiguous()
+        U, _, F = mel.shape
+        n = int(self.lib.qvc_spk_ragged_workspace_bytes(ctypes.byref(self.cfg), U, F))
+        if n < 0:
+            L.check(self.lib, n, "qvc_spk_ragged_workspace_bytes")
+        if ws is None:
+            if self._spk_ws is None or self._spk_ws.numel() < n:
+                self._spk_ws = _aligned_empty(n, self.device)
+            ws = self._spk_ws
+        g = torch.empty(U, self.model_config["gin_channels"], dtype=torch.float32, device=self.device)
+        st = self.lib.qvc_speaker_embed_ragged(ctypes.byref(self.cfg), self._spk_blob.data_ptr(), mel.data_ptr(), frames.data_ptr(),
+                                               g.data_ptr(), U, F, ws.data_ptr(), ws.numel(),
+                                               torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib, st, "qvc_speaker_embed_ragged")
+        return g
+
+    @_on_device
+    def speaker_embed(self, mel: torch.Tensor) -> torch.Tensor:
+        """SpeakerEncoder.embed_utterance for a batch (models.py:528-546): mel (U, n_mel, F) -> g (U, gin)."""
+        if mel.dim() != 3 or mel.shape[1] != int(self.cfg.n_mel_channels) or mel.shape[2] < 1:
+            raise ValueError(f"mel must be (U, {int(self.cfg.n_mel_channels)}, frames), got {tuple(mel.shape)}")
+        self._pack_spk()
         mel = self._f32(mel, self.device)
         U, _, F = mel.shape
         n = int(self.lib.qvc_spk_workspace_bytes(ctypes.byref(self.cfg), U, F))

@@ -139,6 +139,18 @@ def declare(lib: ctypes.CDLL, prefix: str = "qvc") -> None:
         lib.qvc_mel_workspace_bytes.argtypes = [I, I, I, I]
         lib.qvc_wave_to_mel.restype = ctypes.c_int
         lib.qvc_wave_to_mel.argtypes = [V, I, I, I, V, V, I, I, V, L, V]
+        lib.qvc_spk_ragged_workspace_bytes.restype = L
+        lib.qvc_spk_ragged_workspace_bytes.argtypes = [cfgp, I, I]
+        lib.qvc_speaker_embed_ragged.restype = ctypes.c_int
+        lib.qvc_speaker_embed_ragged.argtypes = [cfgp, V, V, V, V, I, I, V, L, V]
+        lib.qvc_mel_ragged_workspace_bytes.restype = L
+        lib.qvc_mel_ragged_workspace_bytes.argtypes = [I, I, I, I]
+        lib.qvc_wave_to_mel_ragged.restype = ctypes.c_int
+        lib.qvc_wave_to_mel_ragged.argtypes = [V, I, I, I, V, V, V, V, V, I, I, V, L, V]
+        lib.qvc_trim_workspace_bytes.restype = L
+        lib.qvc_trim_workspace_bytes.argtypes = [I, I, I, I]
+        lib.qvc_trim_bounds.restype = ctypes.c_int
+        lib.qvc_trim_bounds.argtypes = [V, V, V, V, I, I, ctypes.c_float, I, I, V, L, V]
 
 
 _lib = None

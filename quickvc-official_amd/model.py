@@ -317,6 +317,39 @@ class SynthesizerTrn(nn.Module):
         return self.engine().speaker_embed(mel)
 
     @torch.no_grad()
+    def speaker_embed_waves(self, waves, front, trim_top_db: Optional[float] = 20.0) -> Tensor:
+        """The target side of convert.py:64-77 for a batch of recordings of ANY lengths: ``waves`` is a list of 1-D float
+        arrays / tensors at the model's sampling rate, ``front`` a ``MelFrontend`` -> g (U, gin).
+
+        The rows are padded into one upload, then silence trim (``trim_top_db=None`` skips it), mel and the speaker
+        encoder run back to back on the device lengths -- no host sync in between -- and each row equals
+        ``speaker_embed(front(trim(w)))`` of that recording alone.  The frame counts are read back once at the end: a
+        recording too short for one mel frame raises ``ValueError`` (as it does alone)."""
+        import numpy as np
+        from .frontend import trim_bounds
+        eng = self.engine()
+        rows = [torch.as_tensor(np.asarray(w, dtype=np.float32) if not torch.is_tensor(w) else w).reshape(-1) for w in waves]
+        if not rows:
+            raise ValueError("no waveform given")
+        lens = [int(r.numel()) for r in rows]
+        if max(lens) <= (front.n_fft - front.hop) // 2:                      # host-known: not even the longest row has a frame
+            raise ValueError(f"waveforms {list(range(len(rows)))} are too short for one mel frame")
+        host = torch.zeros(len(rows), max(max(lens), 1), dtype=torch.float32).pin_memory()
+        for u, r in enumerate(rows):
+            host[u, :lens[u]] = r.to(device="cpu", dtype=torch.float32)
+        wave = host.to(eng.device, non_blocking=True)
+        samples = torch.tensor(lens, dtype=torch.int32).pin_memory().to(eng.device, non_blocking=True)
+        start = None
+        if trim_top_db is not None:
+            start, samples = trim_bounds(wave, samples, top_db=trim_top_db)
+        mel, frames = front.ragged(wave, samples, start)
+        g = eng.speaker_embed_ragged(mel, frames)
+        empty = [u for u, f in enumerate(frames.tolist()) if f <= 0]          # the one read-back, after everything is enqueued
+        if empty:
+            raise ValueError(f"waveforms {empty} are too short for one mel frame after trimming")
+        return g
+
+    @torch.no_grad()
     def infer_batch(self, unit: Tensor, g: Tensor, noise: Optional[Tensor] = None) -> Tensor:
         """Batched path: unit (B,256,F), g (B,gin) or (B,gin,1), noise (B,inter,F) -> (B,1,320*F)."""
         eng = self.engine()
