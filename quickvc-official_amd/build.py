@@ -8,6 +8,7 @@ hipcc cross-compiles gfx950 without a GPU.  Translation units compile in paralle
 """
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 import sys
@@ -25,6 +26,9 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
 SOURCES = ["qvc_conv_f16.hip", "qvc_conv_bf16.hip", "qvc_wn2.hip", "qvc_chain.hip", "qvc_small.hip", "qvc_spk.hip", "qvc_mel.hip", "qvc_api.hip", "qvc_pack.cpp"]
+# translation units whose gfx950 assembly is kept next to the resource remarks (tests/test_pair_kloop_waits.py reads the
+# wait counts of the pair kernels' K loops from it)
+ASM_SOURCES = ["qvc_conv_f16.hip", "qvc_conv_bf16.hip"]
 HEADERS = ["qvc_plan.h", "qvc_kernels.h", "qvc_conv_impl.h", "qvc_wn2_impl.h", "qvc_chain_impl.h", "qvc_post_tail_impl.h", "qvc_tail_impl.h", "qvc_path.h", "qvc_stream.h", "qvc_pack_util.h", "qvc_launch_util.h"]
 
 
@@ -44,6 +48,15 @@ def _run(cmd):
     if "-c" in cmd and "-o" in cmd and cmd[cmd.index("-o") + 1].endswith(".o"):
         with open(cmd[cmd.index("-o") + 1][:-2] + ".remarks.txt", "w") as f:
             f.write(res.stdout)
+    # -save-temps=obj leaves every intermediate of the compile next to the object: the device assembly stays, as
+    # <name>.s; the preprocessed sources, bitcode and host assembly go
+    if "-save-temps=obj" in cmd:
+        base = cmd[cmd.index("-o") + 1][:-2]
+        for tmp in glob.glob(glob.escape(base) + "-hip-*") + glob.glob(glob.escape(base) + "-host-*") + glob.glob(glob.escape(base) + ".hip-hip-*"):
+            if tmp.endswith(f"-{ARCH}.s"):
+                os.replace(tmp, base + ".s")
+            else:
+                os.remove(tmp)
     return res.stdout
 
 
@@ -60,9 +73,10 @@ def build_hip(force: bool = False, verbose: bool = False, variant: str = "") -> 
         s = os.path.join(CSRC, src)
         o = os.path.join(obj_dir, os.path.splitext(src)[0] + ".o")
         objs.append(o)
-        if force or not _newer(o, [s] + hdrs):
+        keep_asm = src in ASM_SOURCES and not variant
+        if force or not _newer(o, [s] + hdrs) or (keep_asm and not os.path.exists(o[:-2] + ".s")):
             jobs.append([HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Rpass-analysis=kernel-resource-usage"] + extra +
-                        ["-c", s, "-o", o])
+                        (["-save-temps=obj"] if keep_asm else []) + ["-c", s, "-o", o])
     if jobs:
         with ThreadPoolExecutor(max_workers=min(len(jobs), 6)) as ex:
             for out in ex.map(_run, jobs):

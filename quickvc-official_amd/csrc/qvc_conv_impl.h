@@ -316,6 +316,73 @@ __device__ __forceinline__ void gemm_loop(f32x4 (&acc)[MF][NF], const typename O
   gemm_loop_primed<T, MF, NF, kPF, AS>(acc, ar, ap, nIt, KS, dil, tile, rowbytes, sm, colrow, lq);
 }
 
+// gemm_loop for the fused pair kernel: the same pipeline and the same K order (bit-identical sums), with no branch
+// around a load in whole groups of RING k-steps.  In gemm_loop_primed the A prefetch and the step itself sit behind
+// wave-uniform tests; hipcc's wait counts then assume the path without the loads and wait vmcnt(0) right behind the
+// first prefetch of every group, so the ring was empty once per group (seen in the ISA).  Here a group always issues
+// its MF A loads per step, from k-step min(it + kPF, nIt - 1): an address the loop reads anyway, into a slot that no
+// later MFMA reads; and its B reads, where the last step re-reads its own fragments.  The nIt % RING steps left over
+// (all of them when nIt < RING) run guarded as before; by then no A prefetch is due.
+template <typename T, int MF, int NF, int kPF>
+__device__ __forceinline__ void gemm_loop_free(f32x4 (&acc)[MF][NF], const typename Op<T>::frag* ap, int nIt, int KS, int dil,
+                                               const char* tile, int rowbytes, Swz sm, int colrow, int lq) {
+  using O = Op<T>;
+  using frag = typename O::frag;
+  constexpr int RING = kPF + 1;
+  static_assert(RING % 2 == 0, "the B double buffer needs an even ring");
+  if (nIt <= 0) return;
+  const int last = nIt - 1;
+  frag ar[RING][MF];
+#pragma unroll
+  for (int u = 0; u < kPF; ++u) {                               // gemm_prime without its guards: they too would cost the loop its counts
+    const int pu = u < last ? u : last;
+#pragma unroll
+    for (int m = 0; m < MF; ++m) ar[u][m] = ap[((size_t)pu * MF + m) * 64];
+  }
+  frag bf[2][NF];
+  const int nstride = 16 * rowbytes;
+  int tap = 0, ks = 0, bs = 0;                                  // k-step bs (tap, ks) is the one whose B fragments are read next
+  auto read_b = [&](frag (&dst)[NF]) {
+    const int row0 = tap * dil + colrow;
+    const char* bp = tile + row0 * rowbytes + ((rotc(ks * 4 + lq, sm) ^ swz(row0, sm)) << 4);
+#pragma unroll
+    for (int n = 0; n < NF; ++n) dst[n] = *reinterpret_cast<const frag*>(bp + n * nstride);
+    const int adv = bs < last ? 1 : 0;                          // selects, no branch: stays on the last k-step
+    bs += adv;
+    ks += adv;
+    const int wrap = ks == KS ? 1 : 0;
+    ks = wrap ? 0 : ks;
+    tap += wrap;
+  };
+  auto mfmas = [&](int u) {
+    __builtin_amdgcn_sched_barrier(0);                          // loads stay above this step's MFMAs
+#pragma unroll
+    for (int n = 0; n < NF; ++n)
+#pragma unroll
+      for (int m = 0; m < MF; ++m) acc[m][n] = O::mfma(ar[u][m], bf[u & 1][n], acc[m][n]);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  read_b(bf[0]);
+  const int nfree = nIt - nIt % RING;
+  for (int it0 = 0; it0 < nfree; it0 += RING) {
+#pragma unroll
+    for (int u = 0; u < RING; ++u) {
+      const int pf = it0 + u + kPF < last ? it0 + u + kPF : last;
+      if (!QVC_ABL(5))
+#pragma unroll
+        for (int m = 0; m < MF; ++m) ar[(u + kPF) % RING][m] = ap[((size_t)pf * MF + m) * 64];
+      if (!QVC_ABL(6)) read_b(bf[(u + 1) & 1]);
+      mfmas(u);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < RING - 1; ++u)
+    if (nfree + u < nIt) {                                      // wave-uniform
+      if (nfree + u + 1 < nIt) read_b(bf[(u + 1) & 1]);
+      mfmas(u);
+    }
+}
+
 // Staging of a tile of an utterance's residual stream (type TS, frame-major, C channels; 16-byte chunk c8 of row r is
 // frame t_base + r, zeros outside [Tlo, Tb) and past C) by NTHR threads: put(r, c8, raw, act) gets the chunk as it is
 // in memory and as lrelu(x) in the operand type T.  Every load of the tile (up to 16 per thread) is in flight before the
@@ -688,8 +755,16 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
 // TS = type of the residual STREAM in memory (x, y); T = MFMA operand type.  They differ in the mixed mode
 // (QVC_BF16X: bf16 operands, f16 stream): the identity path of 18 chained pairs then carries 11 mantissa bits --
 // rounding it to bf16 at every pair is what costs all-bf16 its waveform SNR (measured) -- at the same bytes.
+//
+// Waves per SIMD asked of the compiler: what the registers GEMM1 keeps live allow -- MF x (NF+1) accumulator quads, the
+// B double buffer, the A ring, and 16 for addresses and bias.  Left alone hipcc budgets a 4-wave workgroup for one wave
+// per SIMD, and with every ring slot in flight the shipped <2,10> layout then took 319 registers instead of 227.
+constexpr int pair_waves_per_simd(int MF, int NF) {
+  const int regs = 4 * (MF * (NF + 1) + 2 * (NF + 1) + (QVC_PF_CONV + 1) * MF) + 16;
+  return regs <= 168 ? 3 : regs <= 256 ? 2 : 1;      // (4 is never asked for: the staging phase, not the GEMMs, bounds the small layouts)
+}
 template <typename T, int MF, int NF, int WM, int NWV, typename TS = T>
-__global__ __launch_bounds__(NWV * 64) void rbpair_kernel(const PairArgs3 A) {
+__global__ __launch_bounds__(NWV * 64, pair_waves_per_simd(MF, NF)) void rbpair_kernel(const PairArgs3 A) {
   using O = Op<T>;
   using frag = typename O::frag;
   using quad = typename O::quad;
@@ -756,7 +831,7 @@ __global__ __launch_bounds__(NWV * 64) void rbpair_kernel(const PairArgs3 A) {
     f32x4 acc[MF][NF1];
     QVC_ZERO_ACC(acc);
     const frag* ap = static_cast<const frag*>(a.w1) + ((size_t)wm * a.nIt * MF) * 64 + lane;
-    if (!QVC_ABL(1)) gemm_loop<T, MF, NF1, QVC_PF_CONV>(acc, ap, a.nIt, a.KS, a.dil, smem, rowbytes, sm, wn * (NF1 * 16) + lrow, lq);
+    if (!QVC_ABL(1)) gemm_loop_free<T, MF, NF1, QVC_PF_CONV>(acc, ap, a.nIt, a.KS, a.dil, smem, rowbytes, sm, wn * (NF1 * 16) + lrow, lq);
     QVC_ST(2);
     float4 bias[MF];                     // the bias array is padded to WM*MF*16 entries (zeros past C)
 #pragma unroll
@@ -805,7 +880,7 @@ __global__ __launch_bounds__(NWV * 64) void rbpair_kernel(const PairArgs3 A) {
     f32x4 acc[MF][NF];
     QVC_ZERO_ACC(acc);
     const frag* ap = static_cast<const frag*>(a.w2) + ((size_t)wm * a.nIt * MF) * 64 + lane;
-    if (!QVC_ABL(2)) gemm_loop<T, MF, NF, QVC_PF_CONV>(acc, ap, a.nIt, a.KS, 1, smem, rowbytes, sm, wn * (NF * 16) + lrow, lq);
+    if (!QVC_ABL(2)) gemm_loop_free<T, MF, NF, QVC_PF_CONV>(acc, ap, a.nIt, a.KS, 1, smem, rowbytes, sm, wn * (NF * 16) + lrow, lq);
     QVC_ST(5);
     float4 bias[MF];
 #pragma unroll
