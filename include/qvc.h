@@ -121,7 +121,7 @@ int qvc_device_check(void);
  * tests flip them in-process).  The library never reads environment variables: a switch changes only through this
  * call.  Names: "post_tail", "post_tail_nf", "pair_wide_launch", "pair_cm4", "conv_cl", "wn_chunk", "pair_chain3",
  * "wn_kernel", "launch_stop" (-1 = off; n >= 0: the whole-path entry points -- qvc_infer_batch[_ex|_timed|_ragged[_fm]],
- * qvc_enc_q, qvc_flow_forward -- issue only their first n launches).  qvc_debug_get also reads "launch_steps" (read-only:
+ * qvc_infer_fanout_ragged[_fm], qvc_enc_q, qvc_flow_forward -- issue only their first n launches).  qvc_debug_get also reads "launch_steps" (read-only:
  * the launches the last such call would have issued without a stop).  Unknown name: QVC_ERR_BAD_ARG.  No reference
  * counterpart. */
 int qvc_debug_set(const char* name, int32_t value);
@@ -185,6 +185,35 @@ int qvc_infer_batch_ragged_fm(const qvc_config* cfg, const void* blob_dev,
                               const float* unit_fm, const float* g, const float* noise, float* out,
                               int32_t batch, int32_t max_frames, const int32_t* frames_dev,
                               void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- fan-out: R output rows from U <= R distinct sources (any-to-many conversion) -------------------------------
+ * The usual list for the reference's convert.py:58-86 names one source once per target speaker.  Nothing ahead of the
+ * draw z_p = mu + eps * exp(log sigma) (models.py:93-94) depends on the speaker -- in models.py:638-640 only the flow
+ * and the decoder see g -- so the sources are encoded ONCE each (enc_p at batch `sources`, as far as the projection's
+ * statistics), one small launch draws z_p for every row from its source's statistics with the row's own noise, and
+ * flow + decoder run at batch `rows`.
+ *   unit            (U, unit_channels, max_frames) fp32, padded (_fm: [U][max_frames][unit_channels], as on disk)
+ *   frames_dev      DEVICE int32 [U]: the sources' lengths (as qvc_infer_batch_ragged's; clamped on the device)
+ *   src_of_row_dev  DEVICE int32 [R]: the source of every output row; clamped to [0, U-1] on the device
+ *   g (R, gin), noise (R, inter_channels, max_frames), out (R, 320*max_frames): per output row
+ * Row r of `out` follows qvc_infer_batch_ragged's contract: its first 320*frames_dev[src[r]] samples are the waveform
+ * of source src[r] converted with g[r] and noise[r] -- what qvc_infer_batch_ragged gives for the expanded batch --, the
+ * rest are zeros.  1 <= sources <= rows (else QVC_ERR_BAD_ARG).  A source that no row refers to costs its share of
+ * enc_p time and nothing else.  Asynchronous, allocation-free and without a host read of any device array (map and
+ * lengths included), so a captured call can be replayed with other maps and lengths.  The workspace is
+ * qvc_workspace_bytes(cfg, rows, max_frames) plus the per-row length array: qvc_fanout_workspace_bytes (a negative
+ * QVC_ERR_* for bad arguments / configs, as the other size queries).  Offline only: no streaming form. */
+int64_t qvc_fanout_workspace_bytes(const qvc_config* cfg, int32_t sources, int32_t rows, int32_t max_frames);
+int qvc_infer_fanout_ragged(const qvc_config* cfg, const void* blob_dev,
+                            const float* unit, const int32_t* frames_dev, const int32_t* src_of_row_dev,
+                            const float* g, const float* noise, float* out,
+                            int32_t sources, int32_t rows, int32_t max_frames,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+int qvc_infer_fanout_ragged_fm(const qvc_config* cfg, const void* blob_dev,
+                               const float* unit_fm, const int32_t* frames_dev, const int32_t* src_of_row_dev,
+                               const float* g, const float* noise, float* out,
+                               int32_t sources, int32_t rows, int32_t max_frames,
+                               void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- streaming: one hop of new unit frames per call, state in a caller-owned buffer (BASELINE configs[4]) -----
  * The reference converts whole utterances; every op of the path is a bounded, symmetric

@@ -5,7 +5,8 @@ Differences forced by the offline environment: HuBERT-soft cannot 
 source side takes pre-extracted units -- ``src`` may be a ``.npy`` file of shape (frames, 256) fp32
 (the reference's own on-disk unit format, dataset/encode.py:38) or a ``.wav`` that has such a file
 next to it (``x.wav`` -> ``x.npy``).  New optional flags: ``--batch`` (utterances converted per
-launch), ``--seed`` (noise), ``--dtype``.
+launch), ``--seed`` (noise), ``--dtype``, ``--fanout`` (a source listed several times in a batch -- once per target
+speaker, the usual any-to-many list -- is read, uploaded and encoded once: ``qvc_infer_fanout_ragged``).
 
 Corpus scale (BASELINE.json configs[3]): the per-line loop of the reference (convert.py:58-86: load, infer, write, one
 utterance at a time) becomes a three-stage pipeline (``CorpusPipeline``): a loader thread reads the next batches' unit
@@ -139,12 +140,26 @@ def batch_noise(seed: int, key: int, n: int, inter: int, frames: int, device) ->
     return torch.randn((n, inter, frames), generator=gen, device=device, dtype=torch.float32)
 
 
+def fanout_rows(paths):
+    """The distinct sources of a batch and the source of every row: (unique_paths, src_of_row), first-occurrence order,
+    ``unique_paths[src_of_row[r]] == paths[r]``.  Pure host logic."""
+    row_of, unique, src_of_row = {}, [], []
+    for p in paths:
+        if p not in row_of:
+            row_of[p] = len(unique)
+            unique.append(p)
+        src_of_row.append(row_of[p])
+    return unique, src_of_row
+
+
 class CorpusPipeline:
     """Corpus-scale conversion of pre-planned ragged batches (BASELINE.json configs[3]; reference loop: convert.py:58-86).
 
     ``slots`` buffer sets rotate through three stages that run concurrently:
-      load   (loader thread + native I/O pool): unit files -> pinned (B, Tmax, 256) fp32, frame-major as on disk;
-      convert (caller's thread, side streams):  async upload, qvc_infer_batch_ragged_fm, async download into pinned memory;
+      load   (loader thread + native I/O pool): unit files -> pinned (B, Tmax, 256) fp32, frame-major as on disk -- only
+              the U DISTINCT files of a batch (``fanout_rows``), into rows 0 .. U-1;
+      convert (caller's thread, side streams):  async upload, qvc_infer_batch_ragged_fm -- qvc_infer_fanout_ragged_fm where
+              U < B: enc_p once per source --, async download into pinned memory;
       write  (writer thread + native I/O pool): float32 wav files, byte-identical to scipy.io.wavfile.write.
     ``lanes`` batches are converted at the same time, each on a compute stream and workspace of its own: the kernels of
     batch k+1 fill the launch tails and dependency gaps of batch k (about -6 % per batch at 32 x 5 s, bench.py
@@ -152,8 +167,9 @@ class CorpusPipeline:
     """
 
     def __init__(self, net_g, batch: int, max_frames: int, sampling_rate: int, slots: int = 4, io_threads: int = 8,
-                 seed: int = 0, lanes: int = 2):
+                 seed: int = 0, lanes: int = 2, fanout: bool = True):
         from .fileio import IoPool
+        self.fanout = bool(fanout)
         self.net_g, self.engine = net_g, net_g.engine()
         self.dev = self.engine.device
         self.batch, self.max_frames, self.rate, self.seed = int(batch), int(max_frames), int(sampling_rate), int(seed)
@@ -168,21 +184,24 @@ class CorpusPipeline:
             self.slots.append(dict(
                 unit_pin=torch.empty(B * Tm * self.uc, dtype=torch.float32).pin_memory(),
                 lens_pin=torch.empty(B, dtype=torch.int32).pin_memory(),
+                src_pin=torch.empty(B, dtype=torch.int32).pin_memory(),
                 out_pin=torch.empty(B * Tm * self.spf, dtype=torch.float32).pin_memory(),
                 unit_dev=torch.empty(B * Tm * self.uc, dtype=torch.float32, device=self.dev),
                 lens_dev=torch.empty(B, dtype=torch.int32, device=self.dev),
+                src_dev=torch.empty(B, dtype=torch.int32, device=self.dev),
                 out_dev=torch.empty(B * Tm * self.spf, dtype=torch.float32, device=self.dev),
                 done=torch.cuda.Event()))
         for s in self.slots:
             s["up"], s["comp"] = torch.cuda.Event(), torch.cuda.Event()
-        self.ws = [self.engine.alloc_workspace(B, Tm) for _ in range(self.lanes)]
+        self.ws = [self.engine.alloc_workspace(B, Tm, sources=1) for _ in range(self.lanes)]   # serves both entry points
         # uploads, kernels and downloads on streams of their own: batch k+1 travels to the GPU and batch k-1 back to
         # the host while batch k computes (one stream would serialise 1 GB of PCIe traffic with the kernels)
         self.streams = [torch.cuda.Stream(self.dev) for _ in range(self.lanes)]
         self.up_stream, self.down_stream = torch.cuda.Stream(self.dev), torch.cuda.Stream(self.dev)
         # where the threads spend their time (seconds): *_wait = blocked on the neighbouring stage
         self.stats = {"utterances": 0, "samples": 0, "batches": 0, "load_s": 0.0, "load_wait_s": 0.0, "enqueue_s": 0.0,
-                      "enqueue_wait_s": 0.0, "write_s": 0.0, "write_wait_s": 0.0, "gpu_wait_s": 0.0, "embed_s": 0.0}
+                      "enqueue_wait_s": 0.0, "write_s": 0.0, "write_wait_s": 0.0, "gpu_wait_s": 0.0, "embed_s": 0.0,
+                      "encodes_saved": 0}             # rows that shared another row's source: unit reads / uploads / enc_p runs not done
 
     def close(self) -> None:
         self.load_pool.close()
@@ -208,12 +227,17 @@ class CorpusPipeline:
                     n, tmax = len(idxs), max(int(lengths[i]) for i in idxs)
                     if n > self.batch or tmax > self.max_frames:
                         raise ValueError(f"batch of {n} x {tmax} frames exceeds the pipeline's buffers ({self.batch} x {self.max_frames})")
-                    dst = s["unit_pin"][:n * tmax * self.uc].view(n, tmax, self.uc)
-                    self.load_pool.load_units([src_paths[i] for i in idxs], dst, s["lens_pin"])
-                    if [int(v) for v in s["lens_pin"][:n]] != [int(lengths[i]) for i in idxs]:
+                    paths = [src_paths[i] for i in idxs]
+                    uniq, src_of_row = fanout_rows(paths) if self.fanout else (paths, list(range(n)))
+                    nu = len(uniq)
+                    dst = s["unit_pin"][:nu * tmax * self.uc].view(nu, tmax, self.uc)
+                    self.load_pool.load_units(uniq, dst, s["lens_pin"])
+                    first = {r: i for i, r in reversed(list(zip(idxs, src_of_row)))}     # a source's first line
+                    if [int(v) for v in s["lens_pin"][:nu]] != [int(lengths[first[u]]) for u in range(nu)]:
                         raise ValueError("a unit file changed its length since the run was planned")
+                    s["src_pin"][:n] = torch.tensor(src_of_row, dtype=torch.int32)
                     self.stats["load_s"] += time.perf_counter() - tl
-                    ready_q.put((s, idxs, n, tmax))
+                    ready_q.put((s, idxs, n, tmax, nu))
             except Exception as exc:                          # noqa: BLE001 -- reported by run()
                 errors.append(exc)
             finally:
@@ -226,7 +250,7 @@ class CorpusPipeline:
                     item = done_q.get()
                     if item is None:
                         return
-                    s, idxs, n, tmax = item
+                    s, idxs, n, tmax, _nu = item
                     tg = time.perf_counter()
                     s["done"].synchronize()
                     t0w = time.perf_counter()
@@ -270,12 +294,14 @@ class CorpusPipeline:
                     self.stats["enqueue_wait_s"] += te - tw
                     if item is None or errors:
                         break
-                    s, idxs, n, tmax = item
-                    unit = s["unit_dev"][:n * tmax * self.uc].view(n, tmax, self.uc)
-                    lens = s["lens_dev"][:n]
+                    s, idxs, n, tmax, nu = item
+                    unit = s["unit_dev"][:nu * tmax * self.uc].view(nu, tmax, self.uc)
+                    lens, src = s["lens_dev"][:nu], s["src_dev"][:n]
                     with torch.cuda.stream(self.up_stream):
-                        unit.copy_(s["unit_pin"][:n * tmax * self.uc].view(n, tmax, self.uc), non_blocking=True)
-                        lens.copy_(s["lens_pin"][:n], non_blocking=True)
+                        unit.copy_(s["unit_pin"][:nu * tmax * self.uc].view(nu, tmax, self.uc), non_blocking=True)
+                        lens.copy_(s["lens_pin"][:nu], non_blocking=True)
+                        if nu < n:
+                            src.copy_(s["src_pin"][:n], non_blocking=True)
                         s["up"].record(self.up_stream)
                     lane = bi % self.lanes                    # a stream's order keeps a lane's workspace to one batch at a time
                     stream = self.streams[lane]
@@ -284,7 +310,10 @@ class CorpusPipeline:
                         g = g_rows.index_select(0, idx_dev[offs[bi]:offs[bi] + n])
                         out = s["out_dev"][:n * tmax * self.spf].view(n, 1, tmax * self.spf)
                         stream.wait_event(s["up"])
-                        self.engine.infer_batch_ragged(unit, g, noise, lens, out=out, ws=self.ws[lane], unit_fm=True)
+                        if nu < n:                            # repeated sources: encode each once, draw every row from it
+                            self.engine.infer_fanout_ragged(unit, lens, src, g, noise, out=out, ws=self.ws[lane], unit_fm=True)
+                        else:
+                            self.engine.infer_batch_ragged(unit, g, noise, lens, out=out, ws=self.ws[lane], unit_fm=True)
                         s["comp"].record(stream)
                         # the caching allocator hands noise / g back to THIS stream's pool once they go out of scope
                     bi += 1
@@ -297,6 +326,7 @@ class CorpusPipeline:
                     self.stats["utterances"] += n
                     self.stats["samples"] += sum(int(lengths[i]) for i in idxs) * self.spf
                     self.stats["batches"] += 1
+                    self.stats["encodes_saved"] += n - nu
         finally:
             done_q.put(None)
             wt.join()
@@ -306,7 +336,7 @@ class CorpusPipeline:
             raise errors[0]
 
 
-def main(argv=None) -> None:
+def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--hpfile", type=str, default="logs/quickvc/config.json", help="path to json config file")
     p.add_argument("--ptfile", type=str, default="logs/quickvc/quickvc.pth", help="path to pth file")
@@ -319,6 +349,8 @@ def main(argv=None) -> None:
     p.add_argument("--device", type=int, default=None, help="GPU ordinal (default: LOCAL_RANK); rehearsals of several ranks on one GPU pass 0")
     p.add_argument("--io-threads", type=int, default=8, help="native I/O worker threads per direction")
     p.add_argument("--lanes", type=int, default=2, help="batches converted at the same time (compute streams); the output does not depend on it")
+    p.add_argument("--fanout", default="auto", choices=["auto", "off"],
+                   help="auto: a source listed several times in a batch is read, uploaded and encoded once; off: once per line")
     args = p.parse_args(argv)
 
     os.makedirs(args.outdir, exist_ok=True)
@@ -341,12 +373,12 @@ def main(argv=None) -> None:
     seed = args.seed if args.seed is not None else int.from_bytes(os.urandom(4), "little")
 
     print("Synthesizing...")
-    convert_items(net_g, hps.data, items, args.outdir, rank, world, args.batch, seed, args.use_timestamp, args.io_threads,
-                  lanes=args.lanes)
+    return convert_items(net_g, hps.data, items, args.outdir, rank, world, args.batch, seed, args.use_timestamp, args.io_threads,
+                         lanes=args.lanes, fanout=args.fanout != "off")      # the pipeline's stats, for callers in-process
 
 
 def convert_items(net_g, d, items, outdir: str, rank: int = 0, world: int = 1, batch: int = 32, seed: int = 0,
-                  use_timestamp: bool = False, io_threads: int = 8, timings: dict = None, lanes: int = 2):
+                  use_timestamp: bool = False, io_threads: int = 8, timings: dict = None, lanes: int = 2, fanout: bool = True):
     """Convert this rank's shard of ``items`` = [(title, src, tgt)] into ``outdir`` (the body of convert.py:58-86)."""
     from .fileio import IoPool
     t0 = time.perf_counter()
@@ -421,7 +453,7 @@ def convert_items(net_g, d, items, outdir: str, rank: int = 0, world: int = 1, b
             try:
                 with torch.cuda.device(dev_index):
                     box["pipe"] = CorpusPipeline(net_g, min(batch, max(len(b) for b in batches)), max(lengths[i] for i in mine),
-                                                 d.sampling_rate, io_threads=io_threads, seed=seed, lanes=lanes)
+                                                 d.sampling_rate, io_threads=io_threads, seed=seed, lanes=lanes, fanout=fanout)
             except Exception as exc:                                      # noqa: BLE001 -- re-raised below
                 box["error"] = exc
 

@@ -87,6 +87,8 @@ struct HipBackend {
   int wn_stack(const ConvDesc& din, const ConvDesc&, const ConvDesc&, const WnStackArgs& a, int batch, int dtype, const ConvDesc*, const ConvDesc*) { return launch_wn_stack(din, a, batch, dtype, stream); }
   int gemv(const GemvArgs& a) { return launch_gemv(a, stream); }
   int sample(const SampleArgs& a) { return launch_sample(a, stream); }
+  static constexpr bool kFanout = true;           // Path::infer_fanout: EPI_STATS in launch_conv + the row-sampling launch
+  int sample_rows(const SampleRowsArgs& a) { return launch_sample_rows(a, stream); }
   int tail(const TailArgs& a) { return launch_tail(a, stream); }
   bool post_tail_ok(const ConvDesc& d) const { return debug_get(DBG_POST_TAIL) != 0 && post_tail_supported(d); }
   int post_tail(const ConvDesc& d, const PostTailArgs& a, int batch, int dtype) { return launch_post_tail(d, a, batch, dtype, stream); }
@@ -253,6 +255,20 @@ int infer_ragged(const qvc_config* cfg, const void* blob_dev, const float* unit,
                   [&](Ctx& c) { c.lens = frames_dev; c.unit_fm = unit_fm; c.infer(unit, g, noise, out); });
 }
 
+// qvc_infer_fanout_ragged / _fm: `rows` output rows from `sources` encoded sources.  The per-row length array follows the
+// workspace of (rows, max_frames), which is carved as for every other entry point.
+inline int64_t fanout_tail_bytes(int32_t rows) { return align_up((int64_t)rows * 4, 256); }
+int infer_fanout(const qvc_config* cfg, const void* blob_dev, const float* unit, bool unit_fm, const int32_t* frames_dev,
+                 const int32_t* src_dev, const float* g, const float* noise, float* out, int32_t sources, int32_t rows,
+                 int32_t max_frames, void* workspace, int64_t workspace_bytes, void* stream) {
+  HipBackend be(stream);
+  const bool ok = unit && frames_dev && src_dev && g && noise && out && sources >= 1 && sources <= rows;
+  return run_path(be, true, ok, cfg, blob_dev, rows, max_frames, workspace, workspace_bytes - (ok ? fanout_tail_bytes(rows) : 0), [&](Ctx& c) {
+    c.unit_fm = unit_fm;
+    c.infer_fanout(unit, frames_dev, src_dev, sources, g, noise, out, c.wsp<int32_t>(c.W.bytes));
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -369,6 +385,26 @@ int qvc_infer_batch_ragged_fm(const qvc_config* cfg, const void* blob_dev, const
                               const float* noise, float* out, int32_t batch, int32_t max_frames, const int32_t* frames_dev,
                               void* workspace, int64_t workspace_bytes, void* stream) {
   return infer_ragged(cfg, blob_dev, unit_fm, true, g, noise, out, batch, max_frames, frames_dev, workspace, workspace_bytes, stream);
+}
+
+int64_t qvc_fanout_workspace_bytes(const qvc_config* cfg, int32_t sources, int32_t rows, int32_t max_frames) {
+  if (sources < 1 || sources > rows) return QVC_ERR_BAD_ARG;
+  const int64_t n = qvc_workspace_bytes(cfg, rows, max_frames);
+  return n < 0 ? n : n + fanout_tail_bytes(rows);
+}
+
+int qvc_infer_fanout_ragged(const qvc_config* cfg, const void* blob_dev, const float* unit, const int32_t* frames_dev,
+                            const int32_t* src_of_row_dev, const float* g, const float* noise, float* out, int32_t sources,
+                            int32_t rows, int32_t max_frames, void* workspace, int64_t workspace_bytes, void* stream) {
+  return infer_fanout(cfg, blob_dev, unit, false, frames_dev, src_of_row_dev, g, noise, out, sources, rows, max_frames, workspace,
+                      workspace_bytes, stream);
+}
+
+int qvc_infer_fanout_ragged_fm(const qvc_config* cfg, const void* blob_dev, const float* unit_fm, const int32_t* frames_dev,
+                               const int32_t* src_of_row_dev, const float* g, const float* noise, float* out, int32_t sources,
+                               int32_t rows, int32_t max_frames, void* workspace, int64_t workspace_bytes, void* stream) {
+  return infer_fanout(cfg, blob_dev, unit_fm, true, frames_dev, src_of_row_dev, g, noise, out, sources, rows, max_frames, workspace,
+                      workspace_bytes, stream);
 }
 
 int64_t qvc_stream_state_bytes(const qvc_config* cfg, int32_t batch, int32_t hop) {

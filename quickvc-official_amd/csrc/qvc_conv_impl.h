@@ -637,8 +637,31 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
           const f32x4 mu = acc[f][n], ls = acc[HF + f][n];
           const float n0 = nb[q], n1 = nb[(size_t)a.noise_ts + q], n2 = nb[2 * (size_t)a.noise_ts + q], n3 = nb[3 * (size_t)a.noise_ts + q];
           *reinterpret_cast<float4*>(zb + (size_t)q * a.y32_ts) =
-              make_float4((mu[0] + bm.x) + n0 * expf(ls[0] + bl.x), (mu[1] + bm.y) + n1 * expf(ls[1] + bl.y),
-                          (mu[2] + bm.z) + n2 * expf(ls[2] + bl.z), (mu[3] + bm.w) + n3 * expf(ls[3] + bl.w));
+              make_float4(gauss_sample(mu[0], bm.x, n0, ls[0], bl.x), gauss_sample(mu[1], bm.y, n1, ls[1], bl.y),
+                          gauss_sample(mu[2], bm.z, n2, ls[2], bl.z), gauss_sample(mu[3], bm.w, n3, ls[3], bl.w));
+        }
+      }
+    }
+  } else if constexpr (EPI == EPI_STATS) {
+    // the same paired rows, not sampled: mu + bias and log sigma + bias go out in fp32 as [q][mu | log sigma], for a
+    // draw per OUTPUT row taken later (sample_rows_kernel: several rows may share this source)
+    static_assert(EPI != EPI_STATS || MF % 2 == 0, "paired rows");
+    constexpr int HF = MF / 2;
+    const int C = a.gau_H;
+#pragma unroll
+    for (int f = 0; f < HF; ++f) {
+      const int ch0 = ((chunk * WM + wm) * HF + f) * 16 + lq * 4;
+      if (ch0 >= C) continue;
+      const float4 bm = *reinterpret_cast<const float4*>(a.bias + ch0);
+      const float4 bl = *reinterpret_cast<const float4*>(a.bias + C + ch0);
+      float* sb = a.y32 + (size_t)b * a.y32_bs + ch0;
+#pragma unroll
+      for (int n = 0; n < NF; ++n) {
+        const int q = qw + n * 16 + lrow;
+        if (q < a.Nq) {
+          const f32x4 mu = acc[f][n], ls = acc[HF + f][n];
+          *reinterpret_cast<float4*>(sb + (size_t)q * a.y32_ts) = make_float4(mu[0] + bm.x, mu[1] + bm.y, mu[2] + bm.z, mu[3] + bm.w);
+          *reinterpret_cast<float4*>(sb + (size_t)q * a.y32_ts + C) = make_float4(ls[0] + bl.x, ls[1] + bl.y, ls[2] + bl.z, ls[3] + bl.w);
         }
       }
     }
@@ -1474,6 +1497,15 @@ int launch_conv_typed(const ConvDesc& d, const ConvArgs& a, int batch, int epi, 
       case 2: return launch_nf<T, 2, 4, EPI_SAMPLE>(d, a, batch, stream, nf_out);
       case 4: return launch_nf<T, 4, 4, EPI_SAMPLE>(d, a, batch, stream, nf_out);
       case 6: return launch_nf<T, 6, 4, EPI_SAMPLE>(d, a, batch, stream, nf_out);
+      default: return QVC_ERR_BAD_CONFIG;
+    }
+  }
+  if (epi == EPI_STATS) {
+    if (d.WM != 4 || !d.gau || !a.y32 || !a.bias) return QVC_ERR_BAD_CONFIG;
+    switch (d.MF) {
+      case 2: return launch_nf<T, 2, 4, EPI_STATS>(d, a, batch, stream, nf_out);
+      case 4: return launch_nf<T, 4, 4, EPI_STATS>(d, a, batch, stream, nf_out);
+      case 6: return launch_nf<T, 6, 4, EPI_STATS>(d, a, batch, stream, nf_out);
       default: return QVC_ERR_BAD_CONFIG;
     }
   }

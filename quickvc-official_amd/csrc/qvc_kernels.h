@@ -2,6 +2,7 @@
 #pragma once
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdint>
 #include "qvc_plan.h"
 
@@ -75,9 +76,10 @@ struct ConvArgs {
   void* y16 = nullptr; int64_t y16_bs = 0; int32_t y16_ts = 0; float slope_out = 1.f;
   // res/skip split (WN 1x1, modules.py:104-112): rows >= split go to y32b[.. v-split] += val
   float* y32b = nullptr; int32_t split = 0;
-  int32_t gau_H = 0;       // EPI_GAU: hidden size (rows are [tanh | sigmoid]); EPI_SAMPLE: inter channels (rows [mu | log sigma])
+  int32_t gau_H = 0;       // EPI_GAU: hidden size (rows are [tanh | sigmoid]); EPI_SAMPLE / EPI_STATS: inter channels (rows [mu | log sigma])
   // EPI_SAMPLE: y32[b][q][c] = (mu + bias) + noise[b][c][q] * exp(log sigma + bias), noise in the reference's (B, C, T)
   const float* noise = nullptr; int64_t noise_bs = 0; int32_t noise_ts = 0;
+  // EPI_STATS: y32[b][q][c] = mu + bias, y32[b][q][gau_H + c] = log sigma + bias (the layout EPI_STD gives natural rows)
   int32_t ksize = 0;       // polyphase (up_s > 1): kernel size of the transposed conv -- phases with fewer real taps skip their zero ones
   int32_t lp = 0;          // ConvDesc::lp (lane-packed rows): EPI_STD with only a y16 output (the polyphase up-samplers)
   Ragged rg;               // per-utterance INPUT length (in T_in units); see Ragged
@@ -221,6 +223,30 @@ struct SampleArgs {   // z = mu + noise * exp(logs)   (models.py:93-94)
   int32_t batch, frames, C;
 };
 
+#if defined(__HIPCC__)
+// The draw of models.py:93-94 from the projection's raw rows and their biases.  ONE definition, always inlined, for the
+// conv epilogue (EPI_SAMPLE), sample_kernel and sample_rows_kernel: the compiler contracts it the same way in all
+// three, so a statistics hand-over through memory (fp32, nothing rounded) gives the bits of the fused epilogue.
+__device__ __forceinline__ float gauss_sample(float mu, float bm, float n, float ls, float bl) {
+  return (mu + bm) + n * expf(ls + bl);
+}
+#endif
+
+// Fan-out (one source, many target speakers): R output rows drawn from the statistics of U <= R encoded sources.
+//   z[r][t][c] = mu[s][t][c] + noise[r][c][t] * exp(logs[s][t][c]),  s = clamp(src[r], 0, U - 1),  t < frames[s]
+// and zeros from a row's length on (every consumer masks those frames).  The same launch hands the per-row lengths
+// over: row_frames[r] = frames[s], the Ragged::lens of every launch after it.  src / frames / row_frames are device
+// arrays; the grid comes from the host-known caps (R, T, C) alone.
+struct SampleRowsArgs {
+  const float* stats;       // [U][T][2C]: mu + bias | log sigma + bias
+  const float* noise;       // (R, C, T), the reference's layout
+  float* z;                 // [R][T][C]
+  const int32_t* src;       // [R]
+  const int32_t* frames;    // [U]
+  int32_t* row_frames;      // [R]
+  int32_t sources, rows, frames_max, C;
+};
+
 struct TailArgs {     // models.py:394-406 / pqmf.py:106-117; single band: models.py:171-176
   const float* post;  // [B][F][subbands*18]
   const float* fir;   // [subbands][63], gain folded (unused for one band)
@@ -360,6 +386,7 @@ struct CopyDesc {
 constexpr int kCopyBatchMax = 12;
 int launch_copy_batch(const CopyDesc* d, int n, void* stream);
 int launch_sample(const SampleArgs& a, void* stream);
+int launch_sample_rows(const SampleRowsArgs& a, void* stream);
 int launch_tail(const TailArgs& a, void* stream);
 int launch_post_tail(const ConvDesc& d, PostTailArgs a, int batch, int dtype, void* stream);   // bands = post_tail_bands(d)
 

@@ -20,6 +20,9 @@
 //                      optional:  static constexpr bool kSingleBandTail = true -- tail (TailArgs::bands == 1) and
 //                      post_tail (post_tail_bands(d) == 1) run the single-band decoder (QVC_DEC_ISTFT).  A backend that
 //                      does not say so gets QVC_ERR_BAD_CONFIG from the path for that decoder
+//                      optional:  static constexpr bool kFanout = true  with  int sample_rows(const SampleRowsArgs&);
+//                      and conv(..., EPI_STATS, ...) -- the fan-out form of the path (Path::infer_fanout).  A backend
+//                      that does not say so gets QVC_ERR_BAD_CONFIG from it
 //                      void fork(int n); void branch(int j); void branch_done(int j); void join(int n);
 //                      (stream fork/join; no-ops on one stream)
 #pragma once
@@ -36,11 +39,15 @@ namespace qvc {
 template <class B, class = void> constexpr bool single_band_tail = false;
 template <class B> constexpr bool single_band_tail<B, std::void_t<decltype(B::kSingleBandTail)>> = B::kSingleBandTail;
 
+// Backend::kFanout, false for a backend that does not state it (it then needs neither sample_rows nor EPI_STATS).
+template <class B, class = void> constexpr bool fanout_backend = false;
+template <class B> constexpr bool fanout_backend<B, std::void_t<decltype(B::kFanout)>> = B::kFanout;
+
 // Kinds of the steps a Path issues (one per backend call that enqueues device work), in the order they are counted.
 // (A single-band launch is counted as STEP_POST_TAIL1 / STEP_TAIL1: the same backend calls, told apart for the tests.)
 enum StepKind : int32_t {
   STEP_CONV = 0, STEP_ZERO, STEP_GEMV, STEP_SAMPLE, STEP_WN, STEP_WN_STACK, STEP_CHAIN, STEP_PAIR3, STEP_POST_TAIL,
-  STEP_POST_TAIL1, STEP_TAIL, STEP_TAIL1, STEP_KINDS
+  STEP_POST_TAIL1, STEP_TAIL, STEP_TAIL1, STEP_SAMPLE_ROWS, STEP_KINDS
 };
 
 template <class Backend>
@@ -120,6 +127,34 @@ struct Path {
     dec_trunk_wave(wsp<float>(W.z), wsp<float>(W.post), out);
   }
 
+  // ---- the same path for R = B output rows that come from U <= R distinct sources (any-to-many conversion: one source
+  // listed once per target speaker).  Nothing ahead of the draw z_p = mu + eps * exp(log sigma) depends on the speaker
+  // (models.py:638-640: only flow and dec see g), so enc_p runs once per SOURCE, as far as the projection's statistics,
+  // and a row-sampling step draws every row from its source's statistics with its own noise.  The two halves differ in
+  // batch and lengths only: B and lens are switched in between.
+  //   unit (U, ...) / frames [U]: the sources;  src [R]: the source of every row (device; clamped to [0, U-1] there);
+  //   g (R, gin), noise (R, C, T), out (R, ...): per row;  row_frames [R]: scratch, receives frames[src[r]]
+  void infer_fanout(const float* unit, const int32_t* frames, const int32_t* src, int U, const float* g, const float* noise,
+                    float* out, int32_t* row_frames) {
+    if constexpr (fanout_backend<Backend>) {
+      const int R = B;
+      if (U < 1 || U > R) { status = QVC_ERR_BAD_ARG; return; }
+      cond_table(g);                                 // R rows of conditioning
+      B = U; lens = frames;
+      enc(P.enc_pre, P.enc_wn, P.enc_proj, blob, unit, P.cfg.unit_channels, unit_fm,
+          reinterpret_cast<const float*>(blob + P.enc_wn.inbias_off), 0, nullptr, nullptr);   // -> W.stats, rows 0 .. U-1
+      B = R;
+      if (status != QVC_OK) return;
+      SampleRowsArgs sa{wsp<float>(W.stats), noise, wsp<float>(W.z), src, frames, row_frames, U, R, T, P.cfg.inter_channels};
+      if (step(STEP_SAMPLE_ROWS)) status = be.sample_rows(sa);
+      lens = row_frames;
+      flow(wsp<float>(W.z));
+      dec_trunk_wave(wsp<float>(W.z), wsp<float>(W.post), out);
+    } else {
+      status = QVC_ERR_BAD_CONFIG;
+    }
+  }
+
   // ---- WN stack over xw (in place) accumulating into oacc (modules.py:69-114)
   // bb: conditioning rows for layer 0 (+ l*2H per layer), bb_bs: batch stride (0 = shared)
   void wn(const WNPlan& wn, const float* bb, int64_t bb_bs, const char* wb = nullptr) {
@@ -168,7 +203,9 @@ struct Path {
   }
 
   // ---- enc_p (models.py:75-95) and enc_q (the same with cond = g, :582,617; own plan and blob): x, noise -> z.
-  // x: Cx channels, frame- or channel-major; wb: the blob the three descriptors point into; bb / bb_bs: see wn
+  // x: Cx channels, frame- or channel-major; wb: the blob the three descriptors point into; bb / bb_bs: see wn.
+  // z_out == nullptr: stop at the projection and leave its statistics, fp32 [mu + b | log sigma + b] per frame, in
+  // W.stats (paired rows: EPI_STATS instead of the sampling epilogue; natural rows: the conv below as it is)
   void enc(const ConvDesc& pre, const WNPlan& w, const ConvDesc& proj, const char* wb, const float* x, int Cx, bool x_fm,
            const float* bb, int64_t bb_bs, const float* noise, float* z_out) {
     const int H = P.cfg.hidden_channels, C = P.cfg.inter_channels;
@@ -185,11 +222,12 @@ struct Path {
       ConvArgs a = args(proj, wb);
       a.x = wsp<float>(W.oacc); a.x_kind = XK_F32_FM; a.x_bs = (int64_t)T * H; a.x_ts = H; a.T_in = T;
       a.Nq = T; a.T_out = T; a.rg = rg(1);
-      if (proj_and_sample(proj, a, noise, z_out)) return;
+      if (z_out && proj_and_sample(proj, a, noise, z_out)) return;
       a.y32 = wsp<float>(W.stats); a.y32_bs = (int64_t)T * 2 * C; a.y32_ts = 2 * C;
-      conv(proj, a, dtype_wn());
+      if (!z_out && proj.gau) a.gau_H = C;
+      conv(proj, a, dtype_wn(), !z_out && proj.gau ? EPI_STATS : EPI_STD);
     }
-    if (status != QVC_OK) return;
+    if (status != QVC_OK || !z_out) return;
     SampleArgs sa{wsp<float>(W.stats), noise, z_out, B, T, C};
     if (step(STEP_SAMPLE)) status = be.sample(sa);
   }

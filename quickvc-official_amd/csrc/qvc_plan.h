@@ -28,7 +28,8 @@ inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 enum EpiKind : int32_t { EPI_STD = 0, EPI_GAU = 1, EPI_RESSKIP = 2,
-                         EPI_SAMPLE = 3 };   // rows [mu | log sigma] paired like the gate rows: z = mu + noise * exp(log sigma)
+                         EPI_SAMPLE = 3,     // rows [mu | log sigma] paired like the gate rows: z = mu + noise * exp(log sigma)
+                         EPI_STATS = 4 };    // the same paired rows, handed over instead of sampled: fp32 [mu + b | log sigma + b] per frame
 
 // One conv expressed as an implicit GEMM  D[v][q] = sum_{tap,ci} Wv[v][tap][ci] * X[q + tap*dil - left][ci].
 struct ConvDesc {

@@ -1,6 +1,7 @@
 // qvc_small.hip -- the HBM-bound kernels around the conv trunk:
 //   * cond_gemv_kernel   : all 1x1 conditioning convs on g (modules.py:54,84; models.py:328,372)
 //   * sample_kernel      : z_p = mu + noise*exp(logs) (models.py:93-94), noise read in (B,C,T)
+//   * sample_rows_kernel : the same for R output rows that draw from U <= R encoded sources (fan-out)
 //   * istft_synth_kernel : exp / pi*sin / 16-point inverse real DFT / Hann overlap-add /
 //                          envelope / x4 zero-stuff / 63-tap synthesis FIR in ONE pass
 //                          (single-band decoder: the overlap-add output is the waveform)
@@ -124,7 +125,7 @@ __global__ __launch_bounds__(256) void sample_kernel(const SampleArgs a) {
     if (t < a.frames && c < a.C) {
       const size_t bt = (size_t)b * a.frames + t;
       const float mu = a.stats[bt * 2 * a.C + c], logs = a.stats[bt * 2 * a.C + a.C + c];
-      a.z[bt * a.C + c] = mu + s_n[tx][tt] * expf(logs);
+      a.z[bt * a.C + c] = gauss_sample(mu, 0.f, s_n[tx][tt], logs, 0.f);   // (the projection added the biases)
     }
   }
 }
@@ -132,6 +133,49 @@ __global__ __launch_bounds__(256) void sample_kernel(const SampleArgs a) {
 int launch_sample(const SampleArgs& a, void* stream) {
   if (a.batch <= 0 || a.frames <= 0 || a.C <= 0) return QVC_ERR_BAD_ARG;
   hipLaunchKernelGGL(sample_kernel, dim3((unsigned)ceil_div(a.frames, 32), (unsigned)ceil_div(a.C, 32), (unsigned)a.batch), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), a);
+  return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
+}
+
+// ------------------------------------------------------------------ sampling, R rows from U sources (fan-out)
+// sample_kernel with a row map (SampleRowsArgs): output row r draws from the statistics of source clamp(src[r]) with
+// its own noise -- the same 32 x 32 LDS transpose of the noise tile, so the noise is read along t and z written
+// along c.  Frames from the row's length on are written as zeros (nothing of the padding is read: neither the noise's
+// nor the statistics'); the workgroup of a row's first tile also hands the row's length over (one thread).
+__global__ __launch_bounds__(256) void sample_rows_kernel(const SampleRowsArgs a) {
+  __shared__ float s_n[32][33];
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int t0 = blockIdx.x * 32, c0 = blockIdx.y * 32, r = blockIdx.z;
+  const int T = a.frames_max, C = a.C;
+  int s = a.src[r];
+  s = s < 0 ? 0 : (s < a.sources ? s : a.sources - 1);
+  const int flen = a.frames[s];
+  const int len = flen < 0 ? 0 : (flen < T ? flen : T);
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) a.row_frames[r] = flen;   // consumers clamp (ragged_len)
+#pragma unroll
+  for (int cc = ty; cc < 32; cc += 8) {
+    const int c = c0 + cc, t = t0 + tx;
+    s_n[cc][tx] = (c < C && t < len) ? a.noise[((size_t)r * C + c) * T + t] : 0.f;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int tt = ty; tt < 32; tt += 8) {
+    const int t = t0 + tt, c = c0 + tx;
+    if (t < T && c < C) {
+      float z = 0.f;
+      if (t < len) {
+        const float* st = a.stats + ((size_t)s * T + t) * 2 * C;
+        z = gauss_sample(st[c], 0.f, s_n[tx][tt], st[C + c], 0.f);
+      }
+      a.z[((size_t)r * T + t) * C + c] = z;
+    }
+  }
+}
+
+int launch_sample_rows(const SampleRowsArgs& a, void* stream) {
+  if (a.sources <= 0 || a.rows < a.sources || a.rows > 65535 || a.frames_max <= 0 || a.C <= 0) return QVC_ERR_BAD_ARG;
+  if (!a.stats || !a.noise || !a.z || !a.src || !a.frames || !a.row_frames) return QVC_ERR_BAD_ARG;
+  hipLaunchKernelGGL(sample_rows_kernel, dim3((unsigned)ceil_div(a.frames_max, 32), (unsigned)ceil_div(a.C, 32), (unsigned)a.rows), dim3(256), 0,
                      static_cast<hipStream_t>(stream), a);
   return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
 }

@@ -92,20 +92,26 @@ class QvcEngine:
     def load_blob_(self, blob: torch.Tensor) -> None:
         self.blob.copy_(blob)
 
-    def alloc_workspace(self, batch: int, frames: int) -> torch.Tensor:
-        """A private workspace for (batch, frames).  Anything that bakes workspace pointers into a captured graph
-        must own the buffer it captured (the shared one below is replaced when a larger request arrives)."""
-        n = int(self.lib.qvc_workspace_bytes(ctypes.byref(self.cfg), batch, frames))
+    def _workspace_bytes(self, batch: int, frames: int, sources: Optional[int]) -> int:
+        if sources is None:
+            n, what = int(self.lib.qvc_workspace_bytes(ctypes.byref(self.cfg), batch, frames)), "qvc_workspace_bytes"
+        else:
+            n, what = int(self.lib.qvc_fanout_workspace_bytes(ctypes.byref(self.cfg), sources, batch, frames)), "qvc_fanout_workspace_bytes"
         if n < 0:
-            L.check(self.lib, n, "qvc_workspace_bytes")
-        return _aligned_empty(n, self.device)
+            L.check(self.lib, n, what)
+        return n
 
-    def workspace(self, batch: int, frames: int) -> torch.Tensor:
-        key = (batch, frames)
+    def alloc_workspace(self, batch: int, frames: int, sources: Optional[int] = None) -> torch.Tensor:
+        """A private workspace for (batch, frames).  Anything that bakes workspace pointers into a captured graph
+        must own the buffer it captured (the shared one below is replaced when a larger request arrives).
+        ``sources``: the fan-out form -- ``batch`` output rows from ``sources`` encoded sources (infer_fanout_ragged);
+        such a workspace also serves infer_batch_ragged at (batch, frames)."""
+        return _aligned_empty(self._workspace_bytes(batch, frames, sources), self.device)
+
+    def workspace(self, batch: int, frames: int, sources: Optional[int] = None) -> torch.Tensor:
+        key = (batch, frames, sources)
         if self._ws is None or self._ws_key != key:
-            n = int(self.lib.qvc_workspace_bytes(ctypes.byref(self.cfg), batch, frames))
-            if n < 0:
-                L.check(self.lib, n, "qvc_workspace_bytes")
+            n = self._workspace_bytes(batch, frames, sources)
             if self._ws is None or self._ws.numel() < n:
                 self._ws = _aligned_empty(n, self.device)
             self._ws_key = key
@@ -168,6 +174,47 @@ class QvcEngine:
                 noise.data_ptr(), out.data_ptr(), B, T, lens.data_ptr(), ws.data_ptr(), ws.numel(),
                 torch.cuda.current_stream(self.device).cuda_stream)
         L.check(self.lib, st, "qvc_infer_batch_ragged")
+        return out
+
+    @_on_device
+    def infer_fanout_ragged(self, unit: torch.Tensor, frames: torch.Tensor, src_of_row: torch.Tensor, g: torch.Tensor,
+                            noise: torch.Tensor, out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
+                            unit_fm: bool = False) -> torch.Tensor:
+        """R output rows from U <= R distinct sources (one source listed once per target speaker): unit (U,256,Tmax)
+        padded, frames (U,) int32 lengths, src_of_row (R,) int32 -- the source of every row --, g (R,gin), noise
+        (R,inter,Tmax) -> (R,1,Tmax*samples_per_frame).  Row r equals row r of ``infer_batch_ragged`` on the expanded batch
+        (unit[src_of_row], g, noise, frames[src_of_row]); enc_p runs once per source instead of once per row.
+        Host tensors have their ranges checked; device tensors are passed through untouched (the library clamps them on
+        the device and never reads them on the host, so the call can sit in a captured graph).
+        ``ws``: a caller-owned workspace from alloc_workspace(R, Tmax, sources=U); ``unit_fm``: unit is (U,Tmax,256)."""
+        mc = self.model_config
+        if unit_fm:
+            U, T, cu = unit.shape
+        else:
+            U, cu, T = unit.shape
+        R = int(src_of_row.shape[0]) if src_of_row.dim() == 1 else -1
+        if cu != mc.get("unit_channels", 256) or tuple(frames.shape) != (U,) or R < U or g.shape != (R, mc["gin_channels"]) or \
+                tuple(noise.shape) != (R, mc["inter_channels"], T):
+            raise ValueError(f"bad input shapes: unit {tuple(unit.shape)}, frames {tuple(frames.shape)}, src_of_row {tuple(src_of_row.shape)}, "
+                             f"g {tuple(g.shape)}, noise {tuple(noise.shape)} (rows >= sources >= 1)")
+        if frames.device.type != "cuda":                       # host-side values can be validated for free
+            if int(frames.min()) < 2 or int(frames.max()) > T:
+                raise ValueError(f"frames must lie in [2, {T}], got [{int(frames.min())}, {int(frames.max())}]")
+        if src_of_row.device.type != "cuda":
+            if int(src_of_row.min()) < 0 or int(src_of_row.max()) >= U:
+                raise ValueError(f"src_of_row must lie in [0, {U - 1}], got [{int(src_of_row.min())}, {int(src_of_row.max())}]")
+        unit, g, noise = (self._f32(t, self.device) for t in (unit, g, noise))
+        lens = frames.to(device=self.device, dtype=torch.int32).contiguous()
+        src = src_of_row.to(device=self.device, dtype=torch.int32).contiguous()
+        if out is None:
+            out = torch.empty(R, 1, T * self.samples_per_frame, dtype=torch.float32, device=self.device)
+        if ws is None:
+            ws = self.workspace(R, T, sources=U)
+        fn = self.lib.qvc_infer_fanout_ragged_fm if unit_fm else self.lib.qvc_infer_fanout_ragged
+        st = fn(ctypes.byref(self.cfg), self.blob.data_ptr(), unit.data_ptr(), lens.data_ptr(), src.data_ptr(), g.data_ptr(),
+                noise.data_ptr(), out.data_ptr(), U, R, T, ws.data_ptr(), ws.numel(),
+                torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib, st, "qvc_infer_fanout_ragged")
         return out
 
     # ---- streaming (qvc_stream_step): sizes, lags and one step; the state / workspace tensors belong to the caller

@@ -153,6 +153,18 @@ def declare(lib: ctypes.CDLL, prefix: str = "qvc") -> None:
         lib.qvc_trim_bounds.argtypes = [V, V, V, V, I, I, ctypes.c_float, I, I, V, L, V]
 
 
+    # the fan-out entry points (any-to-many conversion): only on a library that has them -- the emulation library and
+    # libraries built before they existed load through this function too
+    if hasattr(lib, prefix + "_infer_fanout_ragged"):
+        size_fn = getattr(lib, prefix + "_fanout_workspace_bytes")
+        size_fn.restype = L
+        size_fn.argtypes = [cfgp, I, I, I]
+        for name in ("_infer_fanout_ragged", "_infer_fanout_ragged_fm"):
+            fn = getattr(lib, prefix + name)
+            fn.restype = ctypes.c_int
+            fn.argtypes = [cfgp, V, V, V, V, V, V, V, I, I, I, V, L, V]
+
+
 _lib = None
 
 

@@ -379,3 +379,31 @@ class SynthesizerTrn(nn.Module):
         out = eng.infer_batch_ragged(unit, g.reshape(B, -1), noise, torch.tensor(lens, dtype=torch.int32))
         spf = self.samples_per_frame
         return [out[b, :, :lens[b] * spf] for b in range(B)]
+
+    @torch.no_grad()
+    def infer_fanout(self, units, src_of_row, g: Tensor, noises=None):
+        """Any-to-many conversion: ``units`` is the list of U DISTINCT sources ((256, F_u) / (1, 256, F_u) tensors),
+        ``src_of_row`` a list of R ints -- the source of every output row, each in [0, U) --, g (R, gin) or (R, gin, 1) the
+        target speaker of every row, ``noises`` an optional list of R draws (inter, F_src).  Returns a list of R
+        (1, 320*F_src) fp32 waveforms, each equal to what ``infer_ragged`` gives for that (source, g, noise); every
+        source is encoded once (enc_p does not see the speaker, models.py:638-640)."""
+        eng = self.engine()
+        dev = eng.device
+        us = [u.reshape(-1, u.shape[-1]) for u in units]
+        lens = [int(u.shape[-1]) for u in us]
+        src = [int(s) for s in src_of_row]
+        U, R, tmax, inter = len(us), len(src), max(lens), self.model_config["inter_channels"]
+        if not 1 <= U <= R or min(src) < 0 or max(src) >= U:
+            raise ValueError(f"{R} rows over {U} sources: every row names a source in [0, {U}) and rows >= sources >= 1")
+        unit = torch.zeros(U, us[0].shape[0], tmax, device=dev, dtype=torch.float32)
+        for u, x in enumerate(us):
+            unit[u, :, :lens[u]] = x.to(dev, torch.float32)
+        noise = torch.zeros(R, inter, tmax, device=dev, dtype=torch.float32)
+        for r, s in enumerate(src):
+            n = noises[r].reshape(inter, -1).to(dev, torch.float32) if noises is not None else \
+                torch.randn(inter, lens[s], device=dev, dtype=torch.float32)
+            noise[r, :, :lens[s]] = n
+        out = eng.infer_fanout_ragged(unit, torch.tensor(lens, dtype=torch.int32), torch.tensor(src, dtype=torch.int32),
+                                      g.reshape(R, -1), noise)
+        spf = self.samples_per_frame
+        return [out[r, :, :lens[s] * spf] for r, s in enumerate(src)]

@@ -13,6 +13,10 @@ Prints ONE JSON line.  The scratch directory is removed afterwards.
 The reference's own lists name a separate target recording on every line: `--targets N` equal to `--n` with
 `--target-seconds MIN MAX` (target lengths uniform in that range) times that shape; the target side is then reported as
 `setup_and_embed_s`, and `target_wav_read_s` says how much of it is reading the wav files on the host.
+
+`--fanout K` times the any-to-many shape: n / K distinct sources, each listed K times with K different targets (K
+consecutive lines).  `--pipeline-fanout off` converts the same list with the pipeline's source sharing switched off
+(the CLI's `--fanout off`), so the two runs measure what encoding every source once buys end to end.
 """
 from __future__ import annotations
 
@@ -41,6 +45,8 @@ def main() -> None:
     ap.add_argument("--io-threads", type=int, default=8)
     ap.add_argument("--lanes", type=int, default=2, help="batches converted at the same time in the pipeline")
     ap.add_argument("--scratch", default=None, help="parent of the scratch directory (default: the system temp dir)")
+    ap.add_argument("--fanout", type=int, default=1, metavar="K", help="every source is listed K times, with K different targets")
+    ap.add_argument("--pipeline-fanout", default="auto", choices=["auto", "off"], help="the CLI's --fanout: off = every line encodes its source")
     ap.add_argument("--repeat", type=int, default=2, help="end-to-end passes; the last one is reported (the first warms the page cache)")
     args = ap.parse_args()
 
@@ -65,16 +71,21 @@ def main() -> None:
         sr = d.sampling_rate
         tmin, tmax = sorted(float(v) for v in args.target_seconds)
         trng = np.random.RandomState(6)                         # its own stream: the unit files do not depend on the targets
+        K = max(1, args.fanout)
+        n_src = -(-args.n // K)
+        args.targets = max(args.targets, K)
         for k in range(args.targets):
             t = np.arange(int((tmin if tmax == tmin else trng.uniform(tmin, tmax)) * sr)) / sr
             wav = 0.3 * np.sin(2 * np.pi * (110.0 + 17.0 * (k % 64)) * t) + 0.02 * rng.randn(len(t))
             wavfile.write(os.path.join(td, f"tgt{k}.wav"), sr, (np.clip(wav, -1, 1) * 32767).astype(np.int16))
-        lens = rng.randint(args.min_frames, args.max_frames + 1, size=args.n)
+        src_lens = rng.randint(args.min_frames, args.max_frames + 1, size=n_src)
+        lens = src_lens[np.arange(args.n) // K]                 # per line
         t0 = time.perf_counter()
-        for i, n in enumerate(lens):
+        for i, n in enumerate(src_lens):
             np.save(os.path.join(td, f"u{i:05d}.npy"), rng.randn(int(n), 256).astype(np.float32))
         gen_s = time.perf_counter() - t0
-        items = [(f"o{i:05d}", os.path.join(td, f"u{i:05d}.npy"), os.path.join(td, f"tgt{i % args.targets}.wav")) for i in range(args.n)]
+        items = [(f"o{i:05d}", os.path.join(td, f"u{i // K:05d}.npy"), os.path.join(td, f"tgt{(i % K) if K > 1 else i % args.targets}.wav"))
+                 for i in range(args.n)]
         outdir = os.path.join(td, "out")
         os.makedirs(outdir)
 
@@ -84,7 +95,8 @@ def main() -> None:
             timings = {}
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            stats = cli.convert_items(net_g, d, items, outdir, 0, 1, args.batch, seed=7, io_threads=args.io_threads, timings=timings, lanes=args.lanes)
+            stats = cli.convert_items(net_g, d, items, outdir, 0, 1, args.batch, seed=7, io_threads=args.io_threads, timings=timings, lanes=args.lanes,
+                                      fanout=args.pipeline_fanout != "off")
             torch.cuda.synchronize()
             wall = time.perf_counter() - t0
             e2e.append(dict(wall_s=wall, **timings, stages={k: round(v, 4) for k, v in stats.items() if k.endswith("_s")}))
@@ -139,8 +151,8 @@ def main() -> None:
                            "pipeline_samples_per_s": samples / last["pipeline_s"], "passes": e2e},
             "kernel_only": {"wall_s": kernel_s, "samples_per_s": samples / kernel_s},
             "pipeline_vs_kernel_only": kernel_s / last["pipeline_s"], "end_to_end_vs_kernel_only": kernel_s / last["wall_s"],
-            "lanes": args.lanes,
-            "io": {"input_MB": float(lens.sum()) * 1024 / 1e6, "output_MB": samples * 4 / 1e6, "io_threads": args.io_threads,
+            "lanes": args.lanes, "fanout": K, "pipeline_fanout": args.pipeline_fanout, "encodes_saved": int(stats.get("encodes_saved", 0)),
+            "io": {"input_MB": float(src_lens.sum()) * 1024 / 1e6, "output_MB": samples * 4 / 1e6, "io_threads": args.io_threads,
                    "scratch": os.path.dirname(td), "corpus_generation_s": gen_s},
         }
         print(json.dumps(res))
