@@ -127,13 +127,13 @@ def describe(e):
 #   over1  max fraction of a buffer's valid elements more than one such ulp off;
 #   rel    max fp32 error relative to the buffer's RMS (f16 and bf16x modes); rel_bf16 the same in the all-bf16 mode.
 # frac_measured: the largest fraction of 2-byte elements seen to differ at all (the noise the comparator must accept).
-# No configuration covered here takes the separate sample launch (every proj is packed as paired rows): its bounds are
-# the conv epilogue's, unmeasured.
+# The separate sample launch is taken where proj keeps natural rows (the mini config at inter 256, plan info[0] == 0);
+# its bounds are the conv epilogue's, which draws z the same way (profiles/r11_memory_contract.txt).
 BOUNDS = {
     "gemv":      dict(ulp=0, over1=0.0, rel=2.5e-6, rel_bf16=2.5e-6),        # measured 6.3e-7
     "zero":      dict(ulp=0, over1=0.0, rel=0.0, rel_bf16=0.0),              # a memset: exact
     "conv":      dict(ulp=2, over1=1e-5, rel=2e-5, rel_bf16=2e-5),          # 1 ulp (0.15 % of elements); fp32 5.3e-6
-    "sample":    dict(ulp=2, over1=1e-5, rel=2e-5, rel_bf16=2e-5),          # not reached (see above)
+    "sample":    dict(ulp=2, over1=1e-5, rel=2e-5, rel_bf16=2e-5),          # fp32 z 8.6e-7 (23 % of the elements differ at all)
     "wn":        dict(ulp=0, over1=0.0, rel=1.5e-3, rel_bf16=2.3e-2),       # fp32 3.8e-4 (f16; bf16 as wn_stack)
     "wn_stack":  dict(ulp=0, over1=0.0, rel=4.5e-3, rel_bf16=2.3e-2),       # fp32 1.1e-3 (f16, bf16x), 5.8e-3 (bf16)
     "pair3":     dict(ulp=4, over1=1.5e-4, rel=0.0, rel_bf16=0.0),          # 2 ulp (bf16x), 1 ulp (f16, bf16); 3.7e-5 over 1

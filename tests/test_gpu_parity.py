@@ -855,6 +855,9 @@ def test_wide_config_takes_the_fallback_paths(lib, dev):
                   resblock_dilation_sizes=[[1, 2, 3], [1, 2, 3], [1, 2, 3]], upsample_initial_channel=384)),
     # multi-band decoder: fixed PQMF synthesis instead of the learned FIR (models.py:250-279, pqmf.py:106-117)
     ("multiband", dict(ms_istft_vits=False, mb_istft_vits=True, upsample_initial_channel=256, inter_channels=96, hidden_channels=128)),
+    # the mini config at inter 256: proj keeps natural rows (plan info[0] == 0: the paired-row kernels stop at 4 fragments
+    # per wave), so z_p is drawn by the separate sample launch -- the one projection route no other reference test takes
+    ("mini256", dict(inter_channels=256, hidden_channels=64, upsample_initial_channel=128, gin_channels=64)),
 ])
 def test_other_configurations_vs_oracle(lib, dev, name, over):
     """Configurations the goldens do not cover, against the CPU oracle (no golden: the reference was not run on
@@ -873,6 +876,9 @@ def test_other_configurations_vs_oracle(lib, dev, name, over):
     # bf16x: BASELINE.json's 40 dB bar on every configuration (measured 45.1-47.1 dB: profiles/r03_snr_configs.json)
     for dt, min_db in (("f16", 45.0), ("bf16x", 40.0)):
         eng = QvcEngine(dict(model.model_config, operand_dtype=dt), sd, dev)
+        if name == "mini256":
+            info = (ctypes.c_int32 * 8)()
+            assert lib.qvc_plan_info(ctypes.byref(eng.cfg), info) == 0 and info[0] == 0, list(info)
         out = eng.infer_batch(unit.to(dev), g.to(dev), noise.to(dev))
         lens = torch.tensor([T, 17, 30], dtype=torch.int32)
         rag = eng.infer_batch_ragged(unit.to(dev), g.to(dev), noise.to(dev), lens.to(dev))

@@ -197,6 +197,7 @@ def _other(name):
         "x4x4": dict(upsample_rates=[4, 4], upsample_kernel_sizes=[15, 16], resblock_kernel_sizes=[3, 5, 7],
                      resblock_dilation_sizes=[[1, 2, 3], [1, 2, 3], [1, 2, 3]], upsample_initial_channel=384),
         "multiband": dict(ms_istft_vits=False, mb_istft_vits=True, upsample_initial_channel=256, inter_channels=96, hidden_channels=128),
+        "mini256": dict(inter_channels=256, hidden_channels=64, upsample_initial_channel=128, gin_channels=64),
     }[name]
     cfg = dict(q.DEFAULT_MODEL_CONFIG, **over)
     model = q.SynthesizerTrn(641, 32, **cfg)
@@ -205,11 +206,12 @@ def _other(name):
     return model.model_config, sd, unit, g, noise
 
 
-@pytest.mark.parametrize("name", ["wide", "narrow", "x4x4", "multiband", "odd"])
+@pytest.mark.parametrize("name", ["wide", "narrow", "x4x4", "multiband", "odd", "mini256"])
 def test_other_configs_every_launch(dev, name):
     """Other configurations, plain batch, f16: the unfused conv1 / conv2 fallback with its 2-byte residual and WaveNet
     width 256 (wide), up-samplers that are not lane-packed and other proj pairings (narrow, x4x4), the PQMF tail
-    (multiband), odd channel counts (the odd golden config)."""
+    (multiband), odd channel counts (the odd golden config), natural proj rows with the separate sample launch (the
+    mini config at inter 256)."""
     if name == "odd":
         entry, _ = load_case("odd")
         model, sd, unit, g, noise = regenerate(entry)
@@ -220,6 +222,8 @@ def test_other_configs_every_launch(dev, name):
     kinds = _check_steps(f"{name}-f16", r, GpuRun(r, dev))
     if name == "wide":
         assert kinds.count("conv") > 5
+    if name == "mini256":
+        assert "sample" in kinds
 
 
 def test_posterior_every_launch(dev):
