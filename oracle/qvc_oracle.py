@@ -61,6 +61,13 @@ def conv_bias(sd: State, prefix: str) -> Optional[Tensor]:
 
 
 # --------------------------------------------------------------------------- WN
+def wn_geometry(cfg: dict) -> Dict[str, int]:
+    """The WaveNet geometry of a model config.  The reference pins it (kernel 5; 16 layers in enc_p / enc_q; 4 flows
+    of 4 layers: models.py:582-584); the optional keys wn_kernel_size / enc_layers / flow_layers / n_flows name another."""
+    return dict(kernel_size=int(cfg.get("wn_kernel_size", 5)), enc_layers=int(cfg.get("enc_layers", 16)),
+                flow_layers=int(cfg.get("flow_layers", 4)), n_flows=int(cfg.get("n_flows", 4)))
+
+
 def wn_forward(sd: State, prefix: str, x: Tensor, g: Optional[Tensor], hidden: int,
                kernel_size: int, n_layers: int, taps: Optional[dict] = None) -> Tensor:
     """WaveNet stack, modules.py:69-114.
@@ -97,8 +104,9 @@ def wn_forward(sd: State, prefix: str, x: Tensor, g: Optional[Tensor], hidden: i
 
 # --------------------------------------------------------------------------- enc_p / enc_q
 def cond_normal_wn(sd: State, prefix: str, series: Tensor, noise: Tensor, hidden: int, out_ch: int,
-                   cond: Optional[Tensor] = None, taps: Optional[dict] = None) -> Tuple[Tensor, Tensor, Tensor]:
-    """CondNormalWN.forward, models.py:75-95 (kernel 5, 16 layers: models.py:582-583).
+                   cond: Optional[Tensor] = None, taps: Optional[dict] = None,
+                   kernel_size: int = 5, n_layers: int = 16) -> Tuple[Tensor, Tensor, Tensor]:
+    """CondNormalWN.forward, models.py:75-95 (kernel 5, 16 layers: models.py:582-583, the defaults here).
 
     ``noise`` replaces ``torch.randn_like(mu)`` (models.py:94) so both sides of a
     parity test see the same sample.
@@ -106,7 +114,7 @@ def cond_normal_wn(sd: State, prefix: str, series: Tensor, noise: Tensor, hidden
     h = F.conv1d(series, conv_weight(sd, f"{prefix}.pre"), conv_bias(sd, f"{prefix}.pre"))
     if taps is not None:
         taps[f"{prefix}.pre"] = h.clone()
-    h = wn_forward(sd, f"{prefix}.enc", h, cond, hidden, 5, 16, taps)
+    h = wn_forward(sd, f"{prefix}.enc", h, cond, hidden, kernel_size, n_layers, taps)
     stats = F.conv1d(h, conv_weight(sd, f"{prefix}.proj"), conv_bias(sd, f"{prefix}.proj"))
     mu, logs = stats[:, :out_ch], stats[:, out_ch:]
     z = mu + noise * torch.exp(logs)
@@ -115,14 +123,14 @@ def cond_normal_wn(sd: State, prefix: str, series: Tensor, noise: Tensor, hidden
 
 # --------------------------------------------------------------------------- flow
 def flow_reverse(sd: State, z_p: Tensor, g: Tensor, channels: int, hidden: int, n_flows: int = 4,
-                 taps: Optional[dict] = None) -> Tensor:
+                 taps: Optional[dict] = None, kernel_size: int = 5, n_layers: int = 4) -> Tensor:
     """ResidualCouplingBlock.forward(reverse=True), models.py:39-51.
 
     The module list is [L0, Flip, L1', Flip, ...] stored as flows.{0,2,4,6} = layers
     and odd indices = Flip (models.py:33-37); reversed iteration therefore does
     Flip then layer, for layers 6,4,2,0.  Layer (modules.py:199-224):
     x0,x1 = halves; m = post(WN(pre(x0), g)); x1 <- x1 - m.  Flip = channel
-    reversal (modules.py:165-170).  WN: kernel 5, 4 layers (models.py:584).
+    reversal (modules.py:165-170).  WN: kernel 5, 4 layers (models.py:584, the defaults here).
     """
     half = channels // 2
     x = z_p
@@ -131,7 +139,7 @@ def flow_reverse(sd: State, z_p: Tensor, g: Tensor, channels: int, hidden: int, 
         p = f"flow.flows.{2 * idx}"
         x0, x1 = x[:, :half], x[:, half:]
         h = F.conv1d(x0, conv_weight(sd, f"{p}.pre"), conv_bias(sd, f"{p}.pre"))
-        h = wn_forward(sd, f"{p}.enc", h, g, hidden, 5, 4)
+        h = wn_forward(sd, f"{p}.enc", h, g, hidden, kernel_size, n_layers)
         m = F.conv1d(h, conv_weight(sd, f"{p}.post"), conv_bias(sd, f"{p}.post"))
         x = torch.cat([x0, x1 - m], 1)
         if taps is not None:
@@ -140,7 +148,7 @@ def flow_reverse(sd: State, z_p: Tensor, g: Tensor, channels: int, hidden: int, 
 
 
 def flow_forward(sd: State, z: Tensor, g: Tensor, channels: int, hidden: int, n_flows: int = 4,
-                 taps: Optional[dict] = None) -> Tensor:
+                 taps: Optional[dict] = None, kernel_size: int = 5, n_layers: int = 4) -> Tensor:
     """ResidualCouplingBlock.forward(reverse=False), models.py:39-51 (the posterior direction, models.py:618):
     layer then Flip, for layers 0,2,4,6; the coupling adds: x1 <- m + x1 (modules.py:217)."""
     half = channels // 2
@@ -149,7 +157,7 @@ def flow_forward(sd: State, z: Tensor, g: Tensor, channels: int, hidden: int, n_
         p = f"flow.flows.{2 * idx}"
         x0, x1 = x[:, :half], x[:, half:]
         h = F.conv1d(x0, conv_weight(sd, f"{p}.pre"), conv_bias(sd, f"{p}.pre"))
-        h = wn_forward(sd, f"{p}.enc", h, g, hidden, 5, 4)
+        h = wn_forward(sd, f"{p}.enc", h, g, hidden, kernel_size, n_layers)
         m = F.conv1d(h, conv_weight(sd, f"{p}.post"), conv_bias(sd, f"{p}.post"))
         x = torch.cat([x0, m + x1], 1)
         if taps is not None:
@@ -166,10 +174,12 @@ def posterior_encode(sd: State, cfg: dict, spec: Tensor, g: Tensor, noise: Tenso
     sd = {k: v.float() for k, v in sd.items() if torch.is_tensor(v) and v.is_floating_point()}
     inter, hidden = int(cfg["inter_channels"]), int(cfg["hidden_channels"])
     with torch.no_grad():
-        z, mu, logs = cond_normal_wn(sd, "enc_q", spec.float(), noise.float(), hidden, inter, g.float(), None)
+        wn = wn_geometry(cfg)
+        z, mu, logs = cond_normal_wn(sd, "enc_q", spec.float(), noise.float(), hidden, inter, g.float(), None,
+                                     wn["kernel_size"], wn["enc_layers"])
         if taps is not None:
             taps["enc_q.m"], taps["enc_q.logs"], taps["enc_q.z"] = mu.clone(), logs.clone(), z.clone()
-        z_p = flow_forward(sd, z, g.float(), inter, hidden, 4, taps)
+        z_p = flow_forward(sd, z, g.float(), inter, hidden, wn["n_flows"], taps, wn["kernel_size"], wn["flow_layers"])
         if taps is not None:
             taps["flow.z_p"] = z_p.clone()
     return z, z_p
@@ -359,10 +369,12 @@ def infer_from_g(sd: State, cfg: dict, unit: Tensor, g: Tensor, noise: Tensor,
     sd = {k: v.float() for k, v in sd.items() if torch.is_tensor(v) and v.is_floating_point()}
     inter, hidden = int(cfg["inter_channels"]), int(cfg["hidden_channels"])
     with torch.no_grad():
-        z_p, mu, logs = cond_normal_wn(sd, "enc_p", unit.float(), noise.float(), hidden, inter, None, taps)
+        wn = wn_geometry(cfg)
+        z_p, mu, logs = cond_normal_wn(sd, "enc_p", unit.float(), noise.float(), hidden, inter, None, taps,
+                                       wn["kernel_size"], wn["enc_layers"])
         if taps is not None:
             taps["enc_p.mu"], taps["enc_p.logs"], taps["enc_p.z_p"] = mu.clone(), logs.clone(), z_p.clone()
-        z = flow_reverse(sd, z_p, g.float(), inter, hidden, 4, taps)
+        z = flow_reverse(sd, z_p, g.float(), inter, hidden, wn["n_flows"], taps, wn["kernel_size"], wn["flow_layers"])
         o, y_mb = decoder_forward(sd, cfg, z, g.float(), taps)
         if taps is not None:
             taps["dec.y_mb"] = y_mb.clone()

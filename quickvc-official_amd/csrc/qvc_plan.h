@@ -237,6 +237,9 @@ inline int validate(const qvc_config& c) {
     // The single-band decoder (models.py:124-127): padding (k-s)//2, no output_padding -> s*T_in when k-s is even.
     if (single) { if (bad((k - s) % 2 != 0)) return QVC_ERR_BAD_CONFIG; }
     else if (bad((k - s + 1 - i) < 0 || (k - s + 1 - i) % 2 != 0 || i > 1)) return QVC_ERR_BAD_CONFIG;
+    // ... and output_padding 1-i must stay below the stride: a stride-1 FIRST stage is a ConvTranspose1d PyTorch refuses
+    // to build (output_padding 1 >= stride 1), so the reference has no such model and there is nothing to be equal to.
+    else if (bad(s <= 1 - i)) return QVC_ERR_BAD_CONFIG;
     if (bad(ch % 2)) return QVC_ERR_BAD_CONFIG;
     ch /= 2;
     if (bad(ch % 8)) return QVC_ERR_BAD_CONFIG;

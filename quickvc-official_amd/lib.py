@@ -208,7 +208,9 @@ def make_config(mc: dict) -> QvcConfig:
     c.unit_channels = int(mc.get("unit_channels", 256))
     c.inter_channels, c.hidden_channels = int(mc["inter_channels"]), int(mc["hidden_channels"])
     c.gin_channels = int(mc["gin_channels"])
-    c.wn_kernel_size, c.enc_layers, c.flow_layers, c.n_flows = 5, 16, 4, 4          # models.py:582-584
+    # the reference pins these four (models.py:582-584); a checkpoint of another WaveNet geometry names them as optional keys
+    c.wn_kernel_size, c.enc_layers = int(mc.get("wn_kernel_size", 5)), int(mc.get("enc_layers", 16))
+    c.flow_layers, c.n_flows = int(mc.get("flow_layers", 4)), int(mc.get("n_flows", 4))
     c.upsample_initial_channel = int(mc["upsample_initial_channel"])
     ups, ks = list(mc["upsample_rates"]), list(mc["upsample_kernel_sizes"])
     rk, rd = list(mc["resblock_kernel_sizes"]), [list(d) for d in mc["resblock_dilation_sizes"]]

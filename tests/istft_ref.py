@@ -52,10 +52,12 @@ def infer_from_g_single(sd, cfg, unit, g, noise, taps: Optional[dict] = None):
     sd = {k: v.float() for k, v in sd.items() if torch.is_tensor(v) and v.is_floating_point()}
     inter, hidden = int(cfg["inter_channels"]), int(cfg["hidden_channels"])
     with torch.no_grad():
-        z_p, mu, logs = oracle.cond_normal_wn(sd, "enc_p", unit.float(), noise.float(), hidden, inter, None, taps)
+        wn = oracle.wn_geometry(cfg)
+        z_p, mu, logs = oracle.cond_normal_wn(sd, "enc_p", unit.float(), noise.float(), hidden, inter, None, taps,
+                                              wn["kernel_size"], wn["enc_layers"])
         if taps is not None:
             taps["enc_p.mu"], taps["enc_p.logs"], taps["enc_p.z_p"] = mu.clone(), logs.clone(), z_p.clone()
-        z = oracle.flow_reverse(sd, z_p, g.float(), inter, hidden, 4, taps)
+        z = oracle.flow_reverse(sd, z_p, g.float(), inter, hidden, wn["n_flows"], taps, wn["kernel_size"], wn["flow_layers"])
         return decoder_forward_single(sd, cfg, z, g.float(), taps)
 
 

@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 import torch
 
+import config_space as CS
 import emu as E
 import memguard as M
 import stepcheck as S
@@ -288,6 +289,9 @@ def _small_config(name):
     """(model_config, state dict) of the other configurations, B = 2, T = 24."""
     import quickvc_official_amd as q
     from quickvc_official_amd.synth import make_synthetic_state_dict
+    if name in CS.ROWS:                                                # the accepted configuration space (tests/config_space.py)
+        _cfg, mc, sd = CS.problem(name)
+        return mc, sd
     if name in ("wide", "multiband"):
         import test_gpu_step_parity as SP
         mc, sd, *_ = SP._other(name)
@@ -300,8 +304,9 @@ def _small_config(name):
 
 
 @pytest.mark.parametrize("entry", ["plain", "ragged"])
-@pytest.mark.parametrize("name", ["wide", "multiband", "odd", "mini256", "istft"])
+@pytest.mark.parametrize("name", ["wide", "multiband", "odd", "mini256", "istft"] + list(CS.ROWS))
 def test_whole_path_other_configs(lib, dev, name, entry):
+    """... and every row of tests/config_space.py: new halo and tile shapes are where a store lands past a buffer."""
     from quickvc_official_amd.synth import make_synthetic_inputs
     mc, sd = _small_config(name)
     if name == "mini256":
