@@ -247,6 +247,53 @@ int qvc_stream_step(const qvc_config* cfg, const void* blob_dev, void* state, in
 int qvc_stream_reset_slot(const qvc_config* cfg, void* state, int64_t state_bytes, int32_t batch, int32_t hop,
                           int32_t slot, int32_t length, int32_t* pos_dev, int32_t* len_dev, void* stream);
 
+/* ---- the noise drawn on the device: a counter-based generator instead of a noise tensor ---------------------------
+ * The N(0,1) draw of models.py:94 as a pure function of (seed, utterance key, channel, absolute frame), computed where
+ * it is consumed: Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (frame, channel / 4,
+ * key & 0xffffffff, key >> 32); the four outputs give the normals of channels 4g .. 4g+3 by Box-Muller from 24-bit
+ * uniforms (DESIGN.md has the exact recipe).  What an utterance gets depends on ITS key alone -- not on the batch it
+ * rides in, its row, the padding, the shard, or the streaming window -- so an utterance converted alone, in any batch,
+ * as a fan-out row or streamed under the same (seed, key) draws the same noise.  Rows with equal keys draw equal noise.
+ * Each _rng entry point is its twin above with `rng` in place of the noise pointer: same arguments, same workspace
+ * query, asynchronous, allocation-free, graph-capturable; nothing of a noise tensor is allocated, staged or read.
+ *   keys_dev   DEVICE uint64, one key per row (fan-out: per OUTPUT row; streaming: per slot); read in [0, rows) only.
+ *              Streaming: the caller writes keys_dev[slot] when it admits a stream, as it does with the slot's g row;
+ *              the frame of the counter is the stream's absolute frame, so there is no noise lag to align.
+ *   scale      noise_scale: multiplies the normal; 1.0f = the reference's draw, 0.0f = the deterministic mean conversion
+ * The descriptor itself is read on the host during the call (its fields are baked into the launches). */
+typedef struct qvc_noise_rng {
+  uint64_t seed;
+  const uint64_t* keys_dev;   /* DEVICE, one key per row / stream slot; read in [0, rows) only */
+  float scale;                /* noise_scale; 1.0f = the reference's draw */
+} qvc_noise_rng;
+int qvc_infer_batch_ragged_rng(const qvc_config* cfg, const void* blob_dev,
+                               const float* unit, const float* g, const qvc_noise_rng* rng, float* out,
+                               int32_t batch, int32_t max_frames, const int32_t* frames_dev,
+                               void* workspace, int64_t workspace_bytes, void* stream);
+int qvc_infer_batch_ragged_rng_fm(const qvc_config* cfg, const void* blob_dev,
+                                  const float* unit_fm, const float* g, const qvc_noise_rng* rng, float* out,
+                                  int32_t batch, int32_t max_frames, const int32_t* frames_dev,
+                                  void* workspace, int64_t workspace_bytes, void* stream);
+int qvc_infer_fanout_ragged_rng(const qvc_config* cfg, const void* blob_dev,
+                                const float* unit, const int32_t* frames_dev, const int32_t* src_of_row_dev,
+                                const float* g, const qvc_noise_rng* rng, float* out,
+                                int32_t sources, int32_t rows, int32_t max_frames,
+                                void* workspace, int64_t workspace_bytes, void* stream);
+int qvc_infer_fanout_ragged_rng_fm(const qvc_config* cfg, const void* blob_dev,
+                                   const float* unit_fm, const int32_t* frames_dev, const int32_t* src_of_row_dev,
+                                   const float* g, const qvc_noise_rng* rng, float* out,
+                                   int32_t sources, int32_t rows, int32_t max_frames,
+                                   void* workspace, int64_t workspace_bytes, void* stream);
+int qvc_stream_step_rng(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes,
+                        const float* unit_new, const float* g, const qvc_noise_rng* rng, float* out,
+                        int32_t batch, int32_t hop, const int32_t* pos_dev, const int32_t* len_dev,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+/* The generator's draw written out: noise_out (rows, channels, frames) fp32 in the reference's layout holds the normals
+ * of frames [frame0, frame0 + frames) for keys_dev[0 .. rows) -- the tensor that, handed to a pointer entry point, gives
+ * the bits of its _rng twin (the bridge between the two forms, and the way to inspect a draw).  channels % 4 == 0. */
+int qvc_noise_fill(uint64_t seed, const uint64_t* keys_dev, float scale, int32_t rows, int32_t channels, int32_t frames,
+                   int32_t frame0, float* noise_out, void* stream);
+
 /* ---- optional fork/join resources: lets the three independent ResBlocks of an MRF stage
  * (models.py:378-384) run as parallel branches (two auxiliary non-blocking streams + events), so a
  * memory-bound k=3 launch overlaps a compute-bound k=11 launch.  Created/destroyed by the caller

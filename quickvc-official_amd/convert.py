@@ -6,7 +6,10 @@ source side takes pre-extracted units -- ``src`` may be a ``.npy`` file of shape
 (the reference's own on-disk unit format, dataset/encode.py:38) or a ``.wav`` that has such a file
 next to it (``x.wav`` -> ``x.npy``).  New optional flags: ``--batch`` (utterances converted per
 launch), ``--seed`` (noise), ``--dtype``, ``--fanout`` (a source listed several times in a batch -- once per target
-speaker, the usual any-to-many list -- is read, uploaded and encoded once: ``qvc_infer_fanout_ragged``).
+speaker, the usual any-to-many list -- is read, uploaded and encoded once: ``qvc_infer_fanout_ragged``), ``--noise``
+(``torch``: one ``torch.randn`` draw per batch, so an utterance's noise depends on how the list was batched and sharded;
+``native``: the library's counter-based generator keyed by the utterance's position in the list, so its wav is the same
+whatever ``--batch``, ``--fanout``, the number of GPUs, or whether it is converted alone) and ``--noise-scale``.
 
 Corpus scale (BASELINE.json configs[3]): the per-line loop of the reference (convert.py:58-86: load, infer, write, one
 utterance at a time) becomes a three-stage pipeline (``CorpusPipeline``): a loader thread reads the next batches' unit
@@ -133,8 +136,10 @@ def rank_plan(items, rank: int, world: int, batch: int, pool=None):
 
 def batch_noise(seed: int, key: int, n: int, inter: int, frames: int, device) -> torch.Tensor:
     """The N(0,1) draw of models.py:94 for one batch of the pipeline: (n, inter, frames) from a generator seeded with
-    (seed, key) -- key = the global index of the batch's first list line -- so a run is reproducible per batch whatever
-    the sharding, and a test can regenerate the draw of any utterance."""
+    (seed, key) -- key = the global index of the batch's first list line.  A run repeats exactly when it is cut up the
+    same way, and a test can regenerate a batch's draw; but the noise an utterance gets depends on the batch it lands in
+    (its first line, its row, the padded length), i.e. on ``--batch``, the shard, ``--fanout`` and its neighbours'
+    lengths.  ``--noise native`` (the library's counter-based generator, keyed per utterance) does not."""
     gen = torch.Generator(device=device)
     gen.manual_seed((int(seed) * 1000003 + int(key)) & 0x7FFFFFFFFFFFFFFF)
     return torch.randn((n, inter, frames), generator=gen, device=device, dtype=torch.float32)
@@ -167,8 +172,15 @@ class CorpusPipeline:
     """
 
     def __init__(self, net_g, batch: int, max_frames: int, sampling_rate: int, slots: int = 4, io_threads: int = 8,
-                 seed: int = 0, lanes: int = 2, fanout: bool = True):
+                 seed: int = 0, lanes: int = 2, fanout: bool = True, noise: str = "torch", noise_scale: float = 1.0):
+        """``noise``: "torch" -- one ``batch_noise`` tensor per batch; "native" -- no noise tensor at all: the draw is
+        computed on the device from (seed, the utterance's item index, channel, frame), scaled by ``noise_scale``."""
         from .fileio import IoPool
+        if noise not in ("torch", "native"):
+            raise ValueError(f"noise must be 'torch' or 'native', got {noise!r}")
+        if noise == "torch" and noise_scale != 1.0:
+            raise ValueError("noise_scale needs noise='native'")
+        self.noise, self.noise_scale = noise, float(noise_scale)
         self.fanout = bool(fanout)
         self.net_g, self.engine = net_g, net_g.engine()
         self.dev = self.engine.device
@@ -306,14 +318,18 @@ class CorpusPipeline:
                     lane = bi % self.lanes                    # a stream's order keeps a lane's workspace to one batch at a time
                     stream = self.streams[lane]
                     with torch.cuda.stream(stream):
-                        noise = batch_noise(self.seed, idxs[0], n, self.inter, tmax, self.dev)
-                        g = g_rows.index_select(0, idx_dev[offs[bi]:offs[bi] + n])
+                        rows = idx_dev[offs[bi]:offs[bi] + n]
+                        if self.noise == "native":            # a row's key = its item index: already on the device
+                            noise, rng = None, (self.seed, rows, self.noise_scale)
+                        else:
+                            noise, rng = batch_noise(self.seed, idxs[0], n, self.inter, tmax, self.dev), None
+                        g = g_rows.index_select(0, rows)
                         out = s["out_dev"][:n * tmax * self.spf].view(n, 1, tmax * self.spf)
                         stream.wait_event(s["up"])
                         if nu < n:                            # repeated sources: encode each once, draw every row from it
-                            self.engine.infer_fanout_ragged(unit, lens, src, g, noise, out=out, ws=self.ws[lane], unit_fm=True)
+                            self.engine.infer_fanout_ragged(unit, lens, src, g, noise, out=out, ws=self.ws[lane], unit_fm=True, rng=rng)
                         else:
-                            self.engine.infer_batch_ragged(unit, g, noise, lens, out=out, ws=self.ws[lane], unit_fm=True)
+                            self.engine.infer_batch_ragged(unit, g, noise, lens, out=out, ws=self.ws[lane], unit_fm=True, rng=rng)
                         s["comp"].record(stream)
                         # the caching allocator hands noise / g back to THIS stream's pool once they go out of scope
                     bi += 1
@@ -351,7 +367,14 @@ def main(argv=None):
     p.add_argument("--lanes", type=int, default=2, help="batches converted at the same time (compute streams); the output does not depend on it")
     p.add_argument("--fanout", default="auto", choices=["auto", "off"],
                    help="auto: a source listed several times in a batch is read, uploaded and encoded once; off: once per line")
+    p.add_argument("--noise", default="torch", choices=["torch", "native"],
+                   help="torch: one torch.randn draw per batch (an utterance's noise depends on --batch, the shard and --fanout); "
+                        "native: the library's counter-based generator keyed by the utterance's position in --txtpath "
+                        "(blank lines not counted): the same wav however the list is batched, sharded or fanned out")
+    p.add_argument("--noise-scale", type=float, default=1.0, help="noise_scale of the prior draw (needs --noise native); 0 = the mean conversion")
     args = p.parse_args(argv)
+    if args.noise != "native" and args.noise_scale != 1.0:
+        p.error("--noise-scale needs --noise native")
 
     os.makedirs(args.outdir, exist_ok=True)
     hps = get_hparams_from_file(args.hpfile)
@@ -374,12 +397,15 @@ def main(argv=None):
 
     print("Synthesizing...")
     return convert_items(net_g, hps.data, items, args.outdir, rank, world, args.batch, seed, args.use_timestamp, args.io_threads,
-                         lanes=args.lanes, fanout=args.fanout != "off")      # the pipeline's stats, for callers in-process
+                         lanes=args.lanes, fanout=args.fanout != "off", noise=args.noise,
+                         noise_scale=args.noise_scale)                        # the pipeline's stats, for callers in-process
 
 
 def convert_items(net_g, d, items, outdir: str, rank: int = 0, world: int = 1, batch: int = 32, seed: int = 0,
-                  use_timestamp: bool = False, io_threads: int = 8, timings: dict = None, lanes: int = 2, fanout: bool = True):
-    """Convert this rank's shard of ``items`` = [(title, src, tgt)] into ``outdir`` (the body of convert.py:58-86)."""
+                  use_timestamp: bool = False, io_threads: int = 8, timings: dict = None, lanes: int = 2, fanout: bool = True,
+                  noise: str = "torch", noise_scale: float = 1.0):
+    """Convert this rank's shard of ``items`` = [(title, src, tgt)] into ``outdir`` (the body of convert.py:58-86).
+    ``noise="native"``: the key of an utterance is its index in ``items`` -- taken before sharding and length-sorting."""
     from .fileio import IoPool
     t0 = time.perf_counter()
     with torch.no_grad():
@@ -453,7 +479,8 @@ def convert_items(net_g, d, items, outdir: str, rank: int = 0, world: int = 1, b
             try:
                 with torch.cuda.device(dev_index):
                     box["pipe"] = CorpusPipeline(net_g, min(batch, max(len(b) for b in batches)), max(lengths[i] for i in mine),
-                                                 d.sampling_rate, io_threads=io_threads, seed=seed, lanes=lanes, fanout=fanout)
+                                                 d.sampling_rate, io_threads=io_threads, seed=seed, lanes=lanes, fanout=fanout,
+                                                 noise=noise, noise_scale=noise_scale)
             except Exception as exc:                                      # noqa: BLE001 -- re-raised below
                 box["error"] = exc
 

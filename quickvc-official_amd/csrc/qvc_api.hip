@@ -89,6 +89,7 @@ struct HipBackend {
   int sample(const SampleArgs& a) { return launch_sample(a, stream); }
   static constexpr bool kFanout = true;           // Path::infer_fanout: EPI_STATS in launch_conv + the row-sampling launch
   int sample_rows(const SampleRowsArgs& a) { return launch_sample_rows(a, stream); }
+  static constexpr bool kNoiseRng = true;         // the three draw sites compute the noise when a launch carries a NoiseRng
   int tail(const TailArgs& a) { return launch_tail(a, stream); }
   bool post_tail_ok(const ConvDesc& d) const { return debug_get(DBG_POST_TAIL) != 0 && post_tail_supported(d); }
   int post_tail(const ConvDesc& d, const PostTailArgs& a, int batch, int dtype) { return launch_post_tail(d, a, batch, dtype, stream); }
@@ -246,13 +247,23 @@ int run_path(Backend& be, bool whole, bool args_ok, const qvc_config* cfg, const
   return c.status != QVC_OK ? c.status : fin;
 }
 
-// qvc_infer_batch_ragged / _fm: the whole path over utterances of different lengths (unit_fm: units frame-major as on disk)
+// qvc_noise_rng -> the kernels' view of it (false: no descriptor or no key array, the caller's error)
+bool rng_view(const qvc_noise_rng* r, NoiseRng& v) {
+  if (!r || !r->keys_dev) return false;
+  v.keys = r->keys_dev; v.seed_lo = (uint32_t)r->seed; v.seed_hi = (uint32_t)(r->seed >> 32); v.scale = r->scale;
+  return true;
+}
+
+// qvc_infer_batch_ragged / _fm: the whole path over utterances of different lengths (unit_fm: units frame-major as on disk).
+// Exactly one of noise / rng: the _rng twins pass the generator and no tensor.
 int infer_ragged(const qvc_config* cfg, const void* blob_dev, const float* unit, bool unit_fm, const float* g, const float* noise,
                  float* out, int32_t batch, int32_t max_frames, const int32_t* frames_dev, void* workspace, int64_t workspace_bytes,
-                 void* stream) {
+                 void* stream, const qvc_noise_rng* rng = nullptr) {
   HipBackend be(stream);
-  return run_path(be, true, unit && g && noise && out && frames_dev, cfg, blob_dev, batch, max_frames, workspace, workspace_bytes,
-                  [&](Ctx& c) { c.lens = frames_dev; c.unit_fm = unit_fm; c.infer(unit, g, noise, out); });
+  NoiseRng rv;
+  const bool draw = rng ? (!noise && rng_view(rng, rv)) : noise != nullptr;
+  return run_path(be, true, unit && g && draw && out && frames_dev, cfg, blob_dev, batch, max_frames, workspace, workspace_bytes,
+                  [&](Ctx& c) { c.lens = frames_dev; c.unit_fm = unit_fm; c.rng = rv; c.infer(unit, g, noise, out); });
 }
 
 // qvc_infer_fanout_ragged / _fm: `rows` output rows from `sources` encoded sources.  The per-row length array follows the
@@ -260,13 +271,34 @@ int infer_ragged(const qvc_config* cfg, const void* blob_dev, const float* unit,
 inline int64_t fanout_tail_bytes(int32_t rows) { return align_up((int64_t)rows * 4, 256); }
 int infer_fanout(const qvc_config* cfg, const void* blob_dev, const float* unit, bool unit_fm, const int32_t* frames_dev,
                  const int32_t* src_dev, const float* g, const float* noise, float* out, int32_t sources, int32_t rows,
-                 int32_t max_frames, void* workspace, int64_t workspace_bytes, void* stream) {
+                 int32_t max_frames, void* workspace, int64_t workspace_bytes, void* stream, const qvc_noise_rng* rng = nullptr) {
   HipBackend be(stream);
-  const bool ok = unit && frames_dev && src_dev && g && noise && out && sources >= 1 && sources <= rows;
+  NoiseRng rv;
+  const bool draw = rng ? (!noise && rng_view(rng, rv)) : noise != nullptr;
+  const bool ok = unit && frames_dev && src_dev && g && draw && out && sources >= 1 && sources <= rows;
   return run_path(be, true, ok, cfg, blob_dev, rows, max_frames, workspace, workspace_bytes - (ok ? fanout_tail_bytes(rows) : 0), [&](Ctx& c) {
-    c.unit_fm = unit_fm;
+    c.unit_fm = unit_fm; c.rng = rv;
     c.infer_fanout(unit, frames_dev, src_dev, sources, g, noise, out, c.wsp<int32_t>(c.W.bytes));
   });
+}
+
+// qvc_stream_step (noise_new) and qvc_stream_step_rng (rng): exactly one of the two
+int stream_step_api(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
+                    const float* g, const float* noise_new, const qvc_noise_rng* rng, float* out, int32_t batch, int32_t hop,
+                    const int32_t* pos_dev, const int32_t* len_dev, void* workspace, int64_t workspace_bytes, void* stream) {
+  NoiseRng rv;
+  const bool draw = rng ? (!noise_new && rng_view(rng, rv)) : noise_new != nullptr;
+  if (!blob_dev || !state || !unit_new || !g || !draw || !out || !pos_dev || !len_dev || !workspace || batch <= 0) return QVC_ERR_BAD_ARG;
+  Plan P; StreamGeom G;
+  const int gs = stream_plan(cfg, hop, P, G);
+  if (gs != QVC_OK) return gs;
+  if (state_bytes < carve_stream_state(P, G, batch).bytes || workspace_bytes < carve_stream_scratch(P, G, batch).bytes) return QVC_ERR_SMALL_BUFFER;
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255) || (reinterpret_cast<uintptr_t>(blob_dev) & 255) || (reinterpret_cast<uintptr_t>(state) & 255))
+    return QVC_ERR_BAD_ARG;
+  HipBackend be(stream);
+  const int st = stream_step(P, static_cast<const char*>(blob_dev), static_cast<char*>(state), static_cast<char*>(workspace), unit_new, g,
+                             noise_new, out, batch, hop, pos_dev, len_dev, be, rng ? &rv : nullptr);
+  return st != QVC_OK ? st : be.finish();
 }
 
 }  // namespace
@@ -387,6 +419,28 @@ int qvc_infer_batch_ragged_fm(const qvc_config* cfg, const void* blob_dev, const
   return infer_ragged(cfg, blob_dev, unit_fm, true, g, noise, out, batch, max_frames, frames_dev, workspace, workspace_bytes, stream);
 }
 
+int qvc_infer_batch_ragged_rng(const qvc_config* cfg, const void* blob_dev, const float* unit, const float* g,
+                               const qvc_noise_rng* rng, float* out, int32_t batch, int32_t max_frames, const int32_t* frames_dev,
+                               void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!rng) return QVC_ERR_BAD_ARG;
+  return infer_ragged(cfg, blob_dev, unit, false, g, nullptr, out, batch, max_frames, frames_dev, workspace, workspace_bytes, stream, rng);
+}
+
+int qvc_infer_batch_ragged_rng_fm(const qvc_config* cfg, const void* blob_dev, const float* unit_fm, const float* g,
+                                  const qvc_noise_rng* rng, float* out, int32_t batch, int32_t max_frames, const int32_t* frames_dev,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!rng) return QVC_ERR_BAD_ARG;
+  return infer_ragged(cfg, blob_dev, unit_fm, true, g, nullptr, out, batch, max_frames, frames_dev, workspace, workspace_bytes, stream, rng);
+}
+
+int qvc_noise_fill(uint64_t seed, const uint64_t* keys_dev, float scale, int32_t rows, int32_t channels, int32_t frames,
+                   int32_t frame0, float* noise_out, void* stream) {
+  const qvc_noise_rng r{seed, keys_dev, scale};
+  NoiseRng rv;
+  if (!rng_view(&r, rv)) return QVC_ERR_BAD_ARG;
+  return launch_noise_fill(rv, rows, channels, frames, frame0, noise_out, stream);
+}
+
 int64_t qvc_fanout_workspace_bytes(const qvc_config* cfg, int32_t sources, int32_t rows, int32_t max_frames) {
   if (sources < 1 || sources > rows) return QVC_ERR_BAD_ARG;
   const int64_t n = qvc_workspace_bytes(cfg, rows, max_frames);
@@ -405,6 +459,22 @@ int qvc_infer_fanout_ragged_fm(const qvc_config* cfg, const void* blob_dev, cons
                                int32_t rows, int32_t max_frames, void* workspace, int64_t workspace_bytes, void* stream) {
   return infer_fanout(cfg, blob_dev, unit_fm, true, frames_dev, src_of_row_dev, g, noise, out, sources, rows, max_frames, workspace,
                       workspace_bytes, stream);
+}
+
+int qvc_infer_fanout_ragged_rng(const qvc_config* cfg, const void* blob_dev, const float* unit, const int32_t* frames_dev,
+                                const int32_t* src_of_row_dev, const float* g, const qvc_noise_rng* rng, float* out, int32_t sources,
+                                int32_t rows, int32_t max_frames, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!rng) return QVC_ERR_BAD_ARG;
+  return infer_fanout(cfg, blob_dev, unit, false, frames_dev, src_of_row_dev, g, nullptr, out, sources, rows, max_frames, workspace,
+                      workspace_bytes, stream, rng);
+}
+
+int qvc_infer_fanout_ragged_rng_fm(const qvc_config* cfg, const void* blob_dev, const float* unit_fm, const int32_t* frames_dev,
+                                   const int32_t* src_of_row_dev, const float* g, const qvc_noise_rng* rng, float* out, int32_t sources,
+                                   int32_t rows, int32_t max_frames, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!rng) return QVC_ERR_BAD_ARG;
+  return infer_fanout(cfg, blob_dev, unit_fm, true, frames_dev, src_of_row_dev, g, nullptr, out, sources, rows, max_frames, workspace,
+                      workspace_bytes, stream, rng);
 }
 
 int64_t qvc_stream_state_bytes(const qvc_config* cfg, int32_t batch, int32_t hop) {
@@ -434,17 +504,16 @@ int32_t qvc_stream_noise_lag_frames(const qvc_config* cfg) {
 int qvc_stream_step(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
                     const float* g, const float* noise_new, float* out, int32_t batch, int32_t hop, const int32_t* pos_dev,
                     const int32_t* len_dev, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!blob_dev || !state || !unit_new || !g || !noise_new || !out || !pos_dev || !len_dev || !workspace || batch <= 0) return QVC_ERR_BAD_ARG;
-  Plan P; StreamGeom G;
-  const int gs = stream_plan(cfg, hop, P, G);
-  if (gs != QVC_OK) return gs;
-  if (state_bytes < carve_stream_state(P, G, batch).bytes || workspace_bytes < carve_stream_scratch(P, G, batch).bytes) return QVC_ERR_SMALL_BUFFER;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255) || (reinterpret_cast<uintptr_t>(blob_dev) & 255) || (reinterpret_cast<uintptr_t>(state) & 255))
-    return QVC_ERR_BAD_ARG;
-  HipBackend be(stream);
-  const int st = stream_step(P, static_cast<const char*>(blob_dev), static_cast<char*>(state), static_cast<char*>(workspace), unit_new, g,
-                             noise_new, out, batch, hop, pos_dev, len_dev, be);
-  return st != QVC_OK ? st : be.finish();
+  return stream_step_api(cfg, blob_dev, state, state_bytes, unit_new, g, noise_new, nullptr, out, batch, hop, pos_dev, len_dev, workspace,
+                         workspace_bytes, stream);
+}
+
+int qvc_stream_step_rng(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
+                        const float* g, const qvc_noise_rng* rng, float* out, int32_t batch, int32_t hop, const int32_t* pos_dev,
+                        const int32_t* len_dev, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!rng) return QVC_ERR_BAD_ARG;
+  return stream_step_api(cfg, blob_dev, state, state_bytes, unit_new, g, nullptr, rng, out, batch, hop, pos_dev, len_dev, workspace,
+                         workspace_bytes, stream);
 }
 
 int qvc_stream_reset_slot(const qvc_config* cfg, void* state, int64_t state_bytes, int32_t batch, int32_t hop, int32_t slot,

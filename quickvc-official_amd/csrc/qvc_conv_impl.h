@@ -422,6 +422,10 @@ __device__ __forceinline__ void stage_stream_tile(const TS* xb, int C, int cpr, 
   }
 }
 
+// Kernel-side variant of EPI_SAMPLE, chosen by launch_conv_typed when the launch carries a generator instead of a noise
+// tensor (ConvArgs::rng); callers and backends only ever name EPI_SAMPLE.
+constexpr int EPI_SAMPLE_RNG = 16;
+
 // WM waves along M, WN = 4/WM along the frames; block tile = [WM*MF*16 rows] x [WN*NF*16 frames].
 // CL ("chunk loop"): the workgroup stages its tile once and walks all the row chunks itself (grid z = 1) instead of
 // one workgroup per chunk each staging the same tile -- for convs whose staging is the expensive part (up-sampler 1:
@@ -614,6 +618,36 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
         const int q = qw + n * 16 + lrow;
         if (q < a.Nq) {
           *reinterpret_cast<typename O::quad*>(yb + (size_t)q * a.y16_ts) = gate4<T>(acc[f][n], acc[HF + f][n], bt, bs);
+        }
+      }
+    }
+  } else if constexpr (EPI == EPI_SAMPLE_RNG) {
+    // the EPI_SAMPLE epilogue below with the lane's four normals computed instead of loaded (ConvArgs::rng): a lane
+    // holds channels ch0 .. ch0+3 of frame q, exactly one noise_normal4 call.  An instantiation of its own, so the
+    // tensor form's kernels are the code they were.
+    static_assert(EPI != EPI_SAMPLE_RNG || MF % 2 == 0, "paired rows");
+    constexpr int HF = MF / 2;
+    const int C = a.gau_H;
+    const uint32_t seed_lo = a.rng.seed_lo, seed_hi = a.rng.seed_hi;
+    const float nscale = a.rng.scale;
+    const uint64_t key = a.rng.keys[b];
+    const int frame0 = a.rg.pos ? a.rg.pos[b] - a.rg.off : 0;       // absolute frame of buffer row 0
+#pragma unroll
+    for (int f = 0; f < HF; ++f) {
+      const int ch0 = ((chunk * WM + wm) * HF + f) * 16 + lq * 4;
+      if (ch0 >= C) continue;
+      const float4 bm = *reinterpret_cast<const float4*>(a.bias + ch0);
+      const float4 bl = *reinterpret_cast<const float4*>(a.bias + C + ch0);
+      float* zb = a.y32 + (size_t)b * a.y32_bs + ch0;
+#pragma unroll
+      for (int n = 0; n < NF; ++n) {
+        const int q = qw + n * 16 + lrow;
+        if (q < a.Nq) {
+          const f32x4 mu = acc[f][n], ls = acc[HF + f][n];
+          const Normal4 nz = noise_normal4(seed_lo, seed_hi, key, (uint32_t)frame0 + (uint32_t)q, (uint32_t)(ch0 >> 2), nscale);
+          *reinterpret_cast<float4*>(zb + (size_t)q * a.y32_ts) =
+              make_float4(gauss_sample(mu[0], bm.x, nz.v[0], ls[0], bl.x), gauss_sample(mu[1], bm.y, nz.v[1], ls[1], bl.y),
+                          gauss_sample(mu[2], bm.z, nz.v[2], ls[2], bl.z), gauss_sample(mu[3], bm.w, nz.v[3], ls[3], bl.w));
         }
       }
     }
@@ -1466,14 +1500,17 @@ inline int launch_one(const ConvArgs& a, int batch, size_t lds, hipStream_t stre
 template <typename T, int MF, int WM, int EPI>
 inline int launch_nf(const ConvDesc& d, const ConvArgs& a, int batch, hipStream_t stream, int* nf_out) {
   static const int nfs[] = {2, 4, 5, 8, 10};
-  const TileChoice tc = choose_tile(d, a.Nq, batch, nfs, 5);
+  // (the generator epilogue is not built at NF 10: at MF 4 its 160 accumulators plus the generator's temporaries spill,
+  //  656 B of scratch per lane; the tile changes no bit of the result)
+  constexpr bool kRng = EPI == EPI_SAMPLE_RNG;
+  const TileChoice tc = choose_tile(d, a.Nq, batch, nfs, kRng ? 4 : 5);
   if (nf_out) *nf_out = tc.NF;
   switch (tc.NF) {
     case 2: return launch_one<T, MF, 2, WM, EPI>(a, batch, tc.lds, stream);
     case 4: return launch_one<T, MF, 4, WM, EPI>(a, batch, tc.lds, stream);
     case 5: if constexpr (MF * 5 * 4 <= 160) return launch_one<T, MF, 5, WM, EPI>(a, batch, tc.lds, stream); break;
     case 8: if constexpr (MF * 8 * 4 <= 160) return launch_one<T, MF, 8, WM, EPI>(a, batch, tc.lds, stream); break;
-    case 10: if constexpr (MF * 10 * 4 <= 160) return launch_one<T, MF, 10, WM, EPI>(a, batch, tc.lds, stream); break;
+    case 10: if constexpr (MF * 10 * 4 <= 160 && !kRng) return launch_one<T, MF, 10, WM, EPI>(a, batch, tc.lds, stream); break;
     default: break;
   }
   return QVC_ERR_BAD_CONFIG;                                 // no tile fits LDS / registers
@@ -1488,6 +1525,15 @@ int launch_conv_typed(const ConvDesc& d, const ConvArgs& a, int batch, int epi, 
       case 2: return launch_nf<T, 2, 4, EPI_GAU>(d, a, batch, stream, nf_out);
       case 4: return launch_nf<T, 4, 4, EPI_GAU>(d, a, batch, stream, nf_out);
       case 6: return launch_nf<T, 6, 4, EPI_GAU>(d, a, batch, stream, nf_out);
+      default: return QVC_ERR_BAD_CONFIG;
+    }
+  }
+  if (epi == EPI_SAMPLE && !a.noise && a.rng.keys) {          // the draw computed in the epilogue (ConvArgs::rng)
+    if (d.WM != 4 || !d.gau || !a.y32 || !a.bias || a.rg.mul != 1) return QVC_ERR_BAD_CONFIG;
+    switch (d.MF) {
+      case 2: return launch_nf<T, 2, 4, EPI_SAMPLE_RNG>(d, a, batch, stream, nf_out);
+      case 4: return launch_nf<T, 4, 4, EPI_SAMPLE_RNG>(d, a, batch, stream, nf_out);
+      case 6: return launch_nf<T, 6, 4, EPI_SAMPLE_RNG>(d, a, batch, stream, nf_out);
       default: return QVC_ERR_BAD_CONFIG;
     }
   }

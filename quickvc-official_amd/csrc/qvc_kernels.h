@@ -47,6 +47,51 @@ QVC_HD int ragged_lo(const Ragged r, int b) {                  // lo
   return d <= 0 ? 0 : d * r.mul;
 }
 
+// ---- the N(0,1) draw of models.py:94 without a noise tensor: a counter-based generator evaluated where the draw is
+// consumed.  The value is a pure function of (seed, utterance key, channel, absolute frame) -- not of the batch, the
+// shard, the padding or the streaming window an utterance happens to sit in.  Philox4x32-10 (Salmon et al., SC'11;
+// the Random123 constants) with key (seed_lo, seed_hi) and counter (frame, channel / 4, key_lo, key_hi); one call
+// yields the four normals of channels 4g .. 4g+3 at that frame -- what a lane of the EPI_SAMPLE epilogue holds.
+struct NoiseRng {
+  const uint64_t* keys = nullptr;   // one key per row / stream slot (device memory); null = the noise comes as a tensor
+  uint32_t seed_lo = 0, seed_hi = 0;
+  float scale = 1.f;                // noise_scale: multiplies the normal before gauss_sample (n * 1.0f is exact)
+};
+struct U32x4 { uint32_t v[4]; };
+struct Normal4 { float v[4]; };
+QVC_HD U32x4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return U32x4{{c0, c1, c2, c3}};
+}
+// ONE definition, always inlined, for every draw site (conv epilogue, sample_rng_kernel, sample_rows_rng_kernel,
+// noise_fill_kernel) and the host: 24-bit uniforms u1 in (0, 1], u2 in [0, 1), Box-Muller with the accurate logf /
+// sqrtf / sincosf.  Contraction is off and no product feeds a sum, so every call site gives the same bits.
+QVC_HD Normal4 noise_normal4(uint32_t seed_lo, uint32_t seed_hi, uint64_t key, uint32_t frame, uint32_t group, float scale) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const U32x4 x = philox4x32_10(frame, group, (uint32_t)key, (uint32_t)(key >> 32), seed_lo, seed_hi);
+  constexpr float k24 = 5.9604644775390625e-08f, kTwoPi = 6.283185307179586f;   // 2^-24
+  Normal4 out;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const float u1 = (float)((x.v[2 * h] >> 8) + 1u) * k24;
+    const float u2 = (float)(x.v[2 * h + 1] >> 8) * k24;
+    const float r = sqrtf(-2.f * logf(u1));
+    float s, c;
+    sincosf(kTwoPi * u2, &s, &c);
+    out.v[2 * h] = (r * c) * scale;
+    out.v[2 * h + 1] = (r * s) * scale;
+  }
+  return out;
+}
+
 // Arguments of one implicit-GEMM conv launch.  All strides in elements.
 struct ConvArgs {
   // ---- input
@@ -83,6 +128,9 @@ struct ConvArgs {
   int32_t ksize = 0;       // polyphase (up_s > 1): kernel size of the transposed conv -- phases with fewer real taps skip their zero ones
   int32_t lp = 0;          // ConvDesc::lp (lane-packed rows): EPI_STD with only a y16 output (the polyphase up-samplers)
   Ragged rg;               // per-utterance INPUT length (in T_in units); see Ragged
+  // EPI_SAMPLE with noise == nullptr and rng.keys set: the normals are computed in the epilogue (noise_normal4) for
+  // key rng.keys[b], channel group ch / 4 and the row's absolute frame, (rg.pos ? rg.pos[b] - rg.off : 0) + q
+  NoiseRng rng;
 };
 // The geometry fields of a conv launch, from its descriptor (the one place that copies them).
 inline void conv_geometry(ConvArgs& a, const ConvDesc& d) {
@@ -221,6 +269,9 @@ struct GemvArgs {
 struct SampleArgs {   // z = mu + noise * exp(logs)   (models.py:93-94)
   const float* stats; const float* noise; float* z;
   int32_t batch, frames, C;
+  // noise == nullptr and rng.keys set: drawn in the kernel for key rng.keys[b] at absolute frame (pos ? pos[b] - off : 0) + t
+  NoiseRng rng = {};
+  const int32_t* pos = nullptr; int32_t off = 0;
 };
 
 #if defined(__HIPCC__)
@@ -245,6 +296,7 @@ struct SampleRowsArgs {
   const int32_t* frames;    // [U]
   int32_t* row_frames;      // [R]
   int32_t sources, rows, frames_max, C;
+  NoiseRng rng = {};        // noise == nullptr and rng.keys set: drawn in the kernel for key rng.keys[r] at the source's frame t
 };
 
 struct TailArgs {     // models.py:394-406 / pqmf.py:106-117; single band: models.py:171-176
@@ -387,6 +439,8 @@ constexpr int kCopyBatchMax = 12;
 int launch_copy_batch(const CopyDesc* d, int n, void* stream);
 int launch_sample(const SampleArgs& a, void* stream);
 int launch_sample_rows(const SampleRowsArgs& a, void* stream);
+// (rows, channels, frames) fp32 in the reference's layout, frames [frame0, frame0 + frames): the tensor the draw sites would compute
+int launch_noise_fill(const NoiseRng& rng, int rows, int channels, int frames, int frame0, float* out, void* stream);
 int launch_tail(const TailArgs& a, void* stream);
 int launch_post_tail(const ConvDesc& d, PostTailArgs a, int batch, int dtype, void* stream);   // bands = post_tail_bands(d)
 

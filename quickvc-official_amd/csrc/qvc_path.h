@@ -23,6 +23,10 @@
 //                      optional:  static constexpr bool kFanout = true  with  int sample_rows(const SampleRowsArgs&);
 //                      and conv(..., EPI_STATS, ...) -- the fan-out form of the path (Path::infer_fanout).  A backend
 //                      that does not say so gets QVC_ERR_BAD_CONFIG from it
+//                      optional:  static constexpr bool kNoiseRng = true -- conv(..., EPI_SAMPLE, ...), sample and
+//                      sample_rows honour ConvArgs::rng / SampleArgs::rng / SampleRowsArgs::rng when the noise pointer
+//                      is null (Path::rng: the draw computed where it is consumed).  A backend that does not say so
+//                      gets QVC_ERR_BAD_CONFIG from the path in that mode
 //                      void fork(int n); void branch(int j); void branch_done(int j); void join(int n);
 //                      (stream fork/join; no-ops on one stream)
 #pragma once
@@ -42,6 +46,10 @@ template <class B> constexpr bool single_band_tail<B, std::void_t<decltype(B::kS
 // Backend::kFanout, false for a backend that does not state it (it then needs neither sample_rows nor EPI_STATS).
 template <class B, class = void> constexpr bool fanout_backend = false;
 template <class B> constexpr bool fanout_backend<B, std::void_t<decltype(B::kFanout)>> = B::kFanout;
+
+// Backend::kNoiseRng, false for a backend that does not state it (it never sees a launch without its noise tensor).
+template <class B, class = void> constexpr bool noise_rng_backend = false;
+template <class B> constexpr bool noise_rng_backend<B, std::void_t<decltype(B::kNoiseRng)>> = B::kNoiseRng;
 
 // Kinds of the steps a Path issues (one per backend call that enqueues device work), in the order they are counted.
 // (A single-band launch is counted as STEP_POST_TAIL1 / STEP_TAIL1: the same backend calls, told apart for the tests.)
@@ -73,6 +81,15 @@ struct Path {
   // the WaveNet stacks may run in the continuous-stream kernel's 64-frame tile (launch_wn_stack picks it where the grid
   // is large); the streaming windows keep the 32-frame tile, not measured there
   bool wn_wide = true;
+  // the N(0,1) draw of models.py:94 computed at its draw site (NoiseRng) -- used where a call passes noise == nullptr
+  NoiseRng rng;
+  // which source of the draw a call with this `noise` pointer uses; false (and status set) if there is none
+  bool draw_ok(const float* noise) {
+    if (noise) return true;
+    if (!rng.keys) status = QVC_ERR_BAD_ARG;
+    else if (!noise_rng_backend<Backend>) status = QVC_ERR_BAD_CONFIG;
+    return status == QVC_OK;
+  }
   // Step window (tests): every backend call that enqueues device work is one step, numbered from 0 in issue order.
   // Steps outside [step_lo, step_hi) are counted but not issued; nothing else the path does changes.  The whole-path
   // state lives in the workspace and the output buffers, so a run can be stopped after any step and resumed from a
@@ -139,6 +156,7 @@ struct Path {
     if constexpr (fanout_backend<Backend>) {
       const int R = B;
       if (U < 1 || U > R) { status = QVC_ERR_BAD_ARG; return; }
+      if (!draw_ok(noise)) return;
       cond_table(g);                                 // R rows of conditioning
       B = U; lens = frames;
       enc(P.enc_pre, P.enc_wn, P.enc_proj, blob, unit, P.cfg.unit_channels, unit_fm,
@@ -146,6 +164,7 @@ struct Path {
       B = R;
       if (status != QVC_OK) return;
       SampleRowsArgs sa{wsp<float>(W.stats), noise, wsp<float>(W.z), src, frames, row_frames, U, R, T, P.cfg.inter_channels};
+      if (!noise) sa.rng = rng;
       if (step(STEP_SAMPLE_ROWS)) status = be.sample_rows(sa);
       lens = row_frames;
       flow(wsp<float>(W.z));
@@ -209,6 +228,7 @@ struct Path {
   void enc(const ConvDesc& pre, const WNPlan& w, const ConvDesc& proj, const char* wb, const float* x, int Cx, bool x_fm,
            const float* bb, int64_t bb_bs, const float* noise, float* z_out) {
     const int H = P.cfg.hidden_channels, C = P.cfg.inter_channels;
+    if (z_out && !draw_ok(noise)) return;
     {
       ConvArgs a = args(pre, wb);
       a.x = x; a.x_bs = (int64_t)Cx * T; a.T_in = T;
@@ -229,6 +249,7 @@ struct Path {
     }
     if (status != QVC_OK || !z_out) return;
     SampleArgs sa{wsp<float>(W.stats), noise, z_out, B, T, C};
+    if (!noise) { sa.rng = rng; sa.pos = pos; sa.off = off; }
     if (step(STEP_SAMPLE)) status = be.sample(sa);
   }
   void enc_p(const float* unit, const float* noise, float* z_out) {
@@ -245,6 +266,7 @@ struct Path {
     if (!d.gau) return false;
     const int C = P.cfg.inter_channels;
     a.gau_H = C; a.noise = noise; a.noise_bs = (int64_t)C * T; a.noise_ts = T;
+    if (!noise) a.rng = rng;
     a.y32 = z_out; a.y32_bs = (int64_t)T * C; a.y32_ts = C;
     conv(d, a, dtype_wn(), EPI_SAMPLE);
     return true;

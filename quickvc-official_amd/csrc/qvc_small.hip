@@ -2,6 +2,8 @@
 //   * cond_gemv_kernel   : all 1x1 conditioning convs on g (modules.py:54,84; models.py:328,372)
 //   * sample_kernel      : z_p = mu + noise*exp(logs) (models.py:93-94), noise read in (B,C,T)
 //   * sample_rows_kernel : the same for R output rows that draw from U <= R encoded sources (fan-out)
+//   * sample_rng_kernel / sample_rows_rng_kernel : the two above with the noise computed (noise_normal4), not read
+//   * noise_fill_kernel  : that generator's draw written out as a (rows, C, T) tensor
 //   * istft_synth_kernel : exp / pi*sin / 16-point inverse real DFT / Hann overlap-add /
 //                          envelope / x4 zero-stuff / 63-tap synthesis FIR in ONE pass
 //                          (single-band decoder: the overlap-add output is the waveform)
@@ -130,8 +132,30 @@ __global__ __launch_bounds__(256) void sample_kernel(const SampleArgs a) {
   }
 }
 
+// The same draw with the normals computed (SampleArgs::rng) instead of read: a thread owns the four channels of one
+// noise_normal4 call at one frame, so there is no noise tile and no LDS transpose -- 8 neighbouring threads read and
+// write 128 contiguous bytes of a frame.  Same tile and grid as sample_kernel.
+__global__ __launch_bounds__(256) void sample_rng_kernel(const SampleArgs a) {
+  const int t = blockIdx.x * 32 + (threadIdx.x >> 3), c = blockIdx.y * 32 + (threadIdx.x & 7) * 4, b = blockIdx.z;
+  if (t >= a.frames || c >= a.C) return;
+  const int frame0 = a.pos ? a.pos[b] - a.off : 0;
+  const Normal4 n = noise_normal4(a.rng.seed_lo, a.rng.seed_hi, a.rng.keys[b], (uint32_t)frame0 + (uint32_t)t, (uint32_t)(c >> 2), a.rng.scale);
+  const size_t bt = (size_t)b * a.frames + t;
+  const float4 mu = *reinterpret_cast<const float4*>(a.stats + bt * 2 * a.C + c);
+  const float4 ls = *reinterpret_cast<const float4*>(a.stats + bt * 2 * a.C + a.C + c);
+  *reinterpret_cast<float4*>(a.z + bt * a.C + c) =
+      make_float4(gauss_sample(mu.x, 0.f, n.v[0], ls.x, 0.f), gauss_sample(mu.y, 0.f, n.v[1], ls.y, 0.f),
+                  gauss_sample(mu.z, 0.f, n.v[2], ls.z, 0.f), gauss_sample(mu.w, 0.f, n.v[3], ls.w, 0.f));
+}
+
 int launch_sample(const SampleArgs& a, void* stream) {
   if (a.batch <= 0 || a.frames <= 0 || a.C <= 0) return QVC_ERR_BAD_ARG;
+  if (!a.noise) {
+    if (!a.rng.keys || a.C % 4 || !a.stats || !a.z) return QVC_ERR_BAD_ARG;
+    hipLaunchKernelGGL(sample_rng_kernel, dim3((unsigned)ceil_div(a.frames, 32), (unsigned)ceil_div(a.C, 32), (unsigned)a.batch), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), a);
+    return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
+  }
   hipLaunchKernelGGL(sample_kernel, dim3((unsigned)ceil_div(a.frames, 32), (unsigned)ceil_div(a.C, 32), (unsigned)a.batch), dim3(256), 0,
                      static_cast<hipStream_t>(stream), a);
   return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
@@ -172,11 +196,59 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(const SampleRowsArgs a
   }
 }
 
+// sample_rows_kernel with the normals computed (SampleRowsArgs::rng): key rng.keys[r] of the OUTPUT row, frame t of the
+// source; a thread owns four channels of one frame as in sample_rng_kernel.
+__global__ __launch_bounds__(256) void sample_rows_rng_kernel(const SampleRowsArgs a) {
+  const int t = blockIdx.x * 32 + (threadIdx.x >> 3), c = blockIdx.y * 32 + (threadIdx.x & 7) * 4, r = blockIdx.z;
+  const int T = a.frames_max, C = a.C;
+  int s = a.src[r];
+  s = s < 0 ? 0 : (s < a.sources ? s : a.sources - 1);
+  const int flen = a.frames[s];
+  const int len = flen < 0 ? 0 : (flen < T ? flen : T);
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) a.row_frames[r] = flen;   // consumers clamp (ragged_len)
+  if (t >= T || c >= C) return;
+  float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (t < len) {
+    const Normal4 n = noise_normal4(a.rng.seed_lo, a.rng.seed_hi, a.rng.keys[r], (uint32_t)t, (uint32_t)(c >> 2), a.rng.scale);
+    const float* st = a.stats + ((size_t)s * T + t) * 2 * C;
+    const float4 mu = *reinterpret_cast<const float4*>(st + c), ls = *reinterpret_cast<const float4*>(st + C + c);
+    z = make_float4(gauss_sample(mu.x, 0.f, n.v[0], ls.x, 0.f), gauss_sample(mu.y, 0.f, n.v[1], ls.y, 0.f),
+                    gauss_sample(mu.z, 0.f, n.v[2], ls.z, 0.f), gauss_sample(mu.w, 0.f, n.v[3], ls.w, 0.f));
+  }
+  *reinterpret_cast<float4*>(a.z + ((size_t)r * T + t) * C + c) = z;
+}
+
 int launch_sample_rows(const SampleRowsArgs& a, void* stream) {
   if (a.sources <= 0 || a.rows < a.sources || a.rows > 65535 || a.frames_max <= 0 || a.C <= 0) return QVC_ERR_BAD_ARG;
+  if (!a.noise && a.rng.keys) {
+    if (!a.stats || !a.z || !a.src || !a.frames || !a.row_frames || a.C % 4) return QVC_ERR_BAD_ARG;
+    hipLaunchKernelGGL(sample_rows_rng_kernel, dim3((unsigned)ceil_div(a.frames_max, 32), (unsigned)ceil_div(a.C, 32), (unsigned)a.rows), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), a);
+    return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
+  }
   if (!a.stats || !a.noise || !a.z || !a.src || !a.frames || !a.row_frames) return QVC_ERR_BAD_ARG;
   hipLaunchKernelGGL(sample_rows_kernel, dim3((unsigned)ceil_div(a.frames_max, 32), (unsigned)ceil_div(a.C, 32), (unsigned)a.rows), dim3(256), 0,
                      static_cast<hipStream_t>(stream), a);
+  return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
+}
+
+// ------------------------------------------------------------------ the generator's draw as a tensor
+// out[r][c][t - frame0] = the normal every draw site computes for (rng.keys[r], channel c, absolute frame t), in the
+// reference's (rows, channels, frames) layout.  A thread owns the four channels of one call; consecutive threads walk
+// along the frames, so each of its four stores is coalesced.
+__global__ __launch_bounds__(256) void noise_fill_kernel(const NoiseRng rng, int channels, int frames, int frame0, float* __restrict__ out) {
+  const int t = blockIdx.x * 256 + threadIdx.x, g = blockIdx.y, r = blockIdx.z;
+  if (t >= frames) return;
+  const Normal4 n = noise_normal4(rng.seed_lo, rng.seed_hi, rng.keys[r], (uint32_t)frame0 + (uint32_t)t, (uint32_t)g, rng.scale);
+  float* o = out + ((size_t)r * channels + (size_t)g * 4) * frames + t;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) o[(size_t)i * frames] = n.v[i];
+}
+
+int launch_noise_fill(const NoiseRng& rng, int rows, int channels, int frames, int frame0, float* out, void* stream) {
+  if (!rng.keys || !out || rows <= 0 || rows > 65535 || channels <= 0 || channels % 4 || channels / 4 > 65535 || frames <= 0) return QVC_ERR_BAD_ARG;
+  hipLaunchKernelGGL(noise_fill_kernel, dim3((unsigned)ceil_div(frames, 256), (unsigned)(channels / 4), (unsigned)rows), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), rng, channels, frames, frame0, out);
   return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
 }
 

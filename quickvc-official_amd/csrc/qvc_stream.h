@@ -129,9 +129,12 @@ inline StreamScratch carve_stream_scratch(const Plan& P, const StreamGeom& G, in
 //   out       (B, hop * samples_per_frame): waveform of frames [pos - lag, pos - lag + hop); zeros where that is
 //                                           outside [0, lens[b])
 //   pos, lens (B,) int32 in the backend's memory: first new frame of this step / sequence length (large if unknown)
+//   rng       with noise_new == nullptr: the draw is computed in enc_p's draw site for key rng->keys[slot] at the absolute
+//             frame of every window row (Path::rng) -- no noise staging, X.noise stays untouched
 template <class Backend>
 int stream_step(const Plan& P, const char* blob, char* state, char* ws, const float* unit_new, const float* g,
-                const float* noise_new, float* out, int B, int hop, const int32_t* pos, const int32_t* lens, Backend& be) {
+                const float* noise_new, float* out, int B, int hop, const int32_t* pos, const int32_t* lens, Backend& be,
+                const NoiseRng* rng = nullptr) {
   const StreamGeom G = stream_geom(P, hop);
   if (G.status != QVC_OK) return G.status;
   const StreamState S = carve_stream_state(P, G, B);
@@ -187,12 +190,15 @@ int stream_step(const Plan& P, const char* blob, char* state, char* ws, const fl
     char* ring = state + S.unit;
     char* nz = ws + X.noise;                                       // zeros either side of the step's noise
     add(ring + (size_t)2 * He * 4, (size_t)T * 4, unit_new, (size_t)h * 4, (size_t)h * 4, (size_t)B * UC);
-    add(nz, (size_t)T * 4, nullptr, 0, (size_t)He * 4, (size_t)B * C);
-    add(nz + (size_t)He * 4, (size_t)T * 4, noise_new, (size_t)h * 4, (size_t)h * 4, (size_t)B * C);
-    add(nz + (size_t)(He + h) * 4, (size_t)T * 4, nullptr, 0, (size_t)He * 4, (size_t)B * C);
+    if (noise_new) {
+      add(nz, (size_t)T * 4, nullptr, 0, (size_t)He * 4, (size_t)B * C);
+      add(nz + (size_t)He * 4, (size_t)T * 4, noise_new, (size_t)h * 4, (size_t)h * 4, (size_t)B * C);
+      add(nz + (size_t)(He + h) * 4, (size_t)T * 4, nullptr, 0, (size_t)He * 4, (size_t)B * C);
+    }
     flush();
     Path<Backend> p = make(T, 0);
-    p.enc_p(reinterpret_cast<const float*>(ring), reinterpret_cast<const float*>(ws + X.noise), p.template wsp<float>(p.W.z));
+    if (!noise_new && rng) p.rng = *rng;     // (neither: enc_p refuses)
+    p.enc_p(reinterpret_cast<const float*>(ring), noise_new ? reinterpret_cast<const float*>(nz) : nullptr, p.template wsp<float>(p.W.z));
     ok(p.status);
     if (G.nf > 0) feed_flow(0, ws + p.W.z + (size_t)He * zrow, T);
     else {

@@ -121,6 +121,44 @@ class QvcEngine:
     def _f32(t: torch.Tensor, device) -> torch.Tensor:
         return t.to(device=device, dtype=torch.float32).contiguous()
 
+    def _draw(self, noise, rng, rows: int, noise_shape):
+        """The two ways to supply the N(0,1) draw: ``noise`` (a tensor of ``noise_shape``) or ``rng = (seed, keys, scale)``
+        -- the counter-based generator of include/qvc.h, ``keys`` one integer per row (a sequence or an int64 tensor; on
+        this device it is passed through untouched).  Exactly one of the two -> (noise tensor or None, descriptor or
+        None, the tensors the descriptor points into)."""
+        if (noise is None) == (rng is None):
+            raise ValueError("pass exactly one of noise and rng=(seed, keys, scale)")
+        if noise is not None:
+            if tuple(noise.shape) != tuple(noise_shape):
+                raise ValueError(f"noise must be {tuple(noise_shape)}, got {tuple(noise.shape)}")
+            return self._f32(noise, self.device), None, None
+        try:
+            seed, keys, scale = rng
+        except (TypeError, ValueError):
+            raise ValueError("rng must be (seed, keys, scale)") from None
+        if not torch.is_tensor(keys):
+            u64 = [int(k) & 0xFFFFFFFFFFFFFFFF for k in keys]
+            keys = torch.tensor([k - (1 << 64) if k >> 63 else k for k in u64], dtype=torch.int64)
+        if keys.dtype != torch.int64 or tuple(keys.shape) != (rows,):
+            raise ValueError(f"rng keys must be {rows} integers (int64), got {keys.dtype} {tuple(keys.shape)}")
+        keys = keys.to(self.device).contiguous()       # the library reads them as uint64: the same 64 bits
+        desc = L.QvcNoiseRng(int(seed) & 0xFFFFFFFFFFFFFFFF, keys.data_ptr(), float(scale))
+        return None, desc, keys
+
+    @_on_device
+    def noise_fill(self, seed: int, keys, channels: int, frames: int, frame0: int = 0, scale: float = 1.0,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """qvc_noise_fill: the generator's draw as a tensor -- (rows, channels, frames) fp32 for frames
+        [frame0, frame0 + frames) of the rows' keys; fed to a ``noise=`` call it gives the bits of the ``rng=`` call."""
+        rows = int(keys.shape[0]) if torch.is_tensor(keys) else len(keys)
+        _, desc, keys_dev = self._draw(None, (seed, keys, scale), rows, None)
+        if out is None:
+            out = torch.empty(rows, channels, frames, dtype=torch.float32, device=self.device)
+        st = self.lib.qvc_noise_fill(desc.seed, keys_dev.data_ptr(), desc.scale, rows, int(channels), int(frames), int(frame0),
+                                     out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib, st, "qvc_noise_fill")
+        return out
+
     @_on_device
     def infer_batch(self, unit: torch.Tensor, g: torch.Tensor, noise: torch.Tensor,
                     out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -144,75 +182,88 @@ class QvcEngine:
         return out
 
     @_on_device
-    def infer_batch_ragged(self, unit: torch.Tensor, g: torch.Tensor, noise: torch.Tensor, frames: torch.Tensor,
+    def infer_batch_ragged(self, unit: torch.Tensor, g: torch.Tensor, noise: Optional[torch.Tensor], frames: torch.Tensor,
                            out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
-                           unit_fm: bool = False) -> torch.Tensor:
+                           unit_fm: bool = False, rng=None) -> torch.Tensor:
         """A batch of utterances of DIFFERENT lengths: unit (B,256,Tmax) / noise (B,inter,Tmax) padded (the padding's
         content is ignored), frames (B,) int32 lengths -> (B,1,Tmax*samples_per_frame); row b holds utterance b's
         waveform in its first frames[b]*samples_per_frame samples and zeros after.
         ``unit_fm``: unit is (B,Tmax,256) -- frame-major, as the reference's unit files are on disk
-        (dataset/encode.py:38), so a batch read by fileio.IoPool.load_units uploads as it is."""
+        (dataset/encode.py:38), so a batch read by fileio.IoPool.load_units uploads as it is.
+        ``rng``: with ``noise=None``, ``(seed, keys, scale)`` -- the draw computed on the device from one key per row
+        (qvc_infer_batch_ragged_rng): no noise tensor exists, and a row's result depends on its key alone."""
         mc = self.model_config
         if unit_fm:
             B, T, cu = unit.shape
         else:
             B, cu, T = unit.shape
-        if cu != mc.get("unit_channels", 256) or g.shape != (B, mc["gin_channels"]) or \
-                tuple(noise.shape) != (B, mc["inter_channels"], T) or tuple(frames.shape) != (B,):
-            raise ValueError(f"bad input shapes: unit {tuple(unit.shape)}, g {tuple(g.shape)}, noise {tuple(noise.shape)}, frames {tuple(frames.shape)}")
+        if cu != mc.get("unit_channels", 256) or g.shape != (B, mc["gin_channels"]) or tuple(frames.shape) != (B,):
+            raise ValueError(f"bad input shapes: unit {tuple(unit.shape)}, g {tuple(g.shape)}, frames {tuple(frames.shape)}")
+        noise, desc, keys_dev = self._draw(noise, rng, B, (B, mc["inter_channels"], T))
         if frames.device.type != "cuda":                       # host-side lengths can be validated for free
             if int(frames.min()) < 2 or int(frames.max()) > T:
                 raise ValueError(f"frames must lie in [2, {T}], got [{int(frames.min())}, {int(frames.max())}]")
-        unit, g, noise = (self._f32(t, self.device) for t in (unit, g, noise))
+        unit, g = (self._f32(t, self.device) for t in (unit, g))
         lens = frames.to(device=self.device, dtype=torch.int32).contiguous()
         if out is None:
             out = torch.empty(B, 1, T * self.samples_per_frame, dtype=torch.float32, device=self.device)
         if ws is None:
             ws = self.workspace(B, T)
-        fn = self.lib.qvc_infer_batch_ragged_fm if unit_fm else self.lib.qvc_infer_batch_ragged
+        if desc is None:
+            fn = self.lib.qvc_infer_batch_ragged_fm if unit_fm else self.lib.qvc_infer_batch_ragged
+            draw = noise.data_ptr()
+        else:
+            fn = self.lib.qvc_infer_batch_ragged_rng_fm if unit_fm else self.lib.qvc_infer_batch_ragged_rng
+            draw = ctypes.byref(desc)
         st = fn(ctypes.byref(self.cfg), self.blob.data_ptr(), unit.data_ptr(), g.data_ptr(),
-                noise.data_ptr(), out.data_ptr(), B, T, lens.data_ptr(), ws.data_ptr(), ws.numel(),
+                draw, out.data_ptr(), B, T, lens.data_ptr(), ws.data_ptr(), ws.numel(),
                 torch.cuda.current_stream(self.device).cuda_stream)
         L.check(self.lib, st, "qvc_infer_batch_ragged")
         return out
 
     @_on_device
     def infer_fanout_ragged(self, unit: torch.Tensor, frames: torch.Tensor, src_of_row: torch.Tensor, g: torch.Tensor,
-                            noise: torch.Tensor, out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
-                            unit_fm: bool = False) -> torch.Tensor:
+                            noise: Optional[torch.Tensor], out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
+                            unit_fm: bool = False, rng=None) -> torch.Tensor:
         """R output rows from U <= R distinct sources (one source listed once per target speaker): unit (U,256,Tmax)
         padded, frames (U,) int32 lengths, src_of_row (R,) int32 -- the source of every row --, g (R,gin), noise
         (R,inter,Tmax) -> (R,1,Tmax*samples_per_frame).  Row r equals row r of ``infer_batch_ragged`` on the expanded batch
         (unit[src_of_row], g, noise, frames[src_of_row]); enc_p runs once per source instead of once per row.
         Host tensors have their ranges checked; device tensors are passed through untouched (the library clamps them on
         the device and never reads them on the host, so the call can sit in a captured graph).
-        ``ws``: a caller-owned workspace from alloc_workspace(R, Tmax, sources=U); ``unit_fm``: unit is (U,Tmax,256)."""
+        ``ws``: a caller-owned workspace from alloc_workspace(R, Tmax, sources=U); ``unit_fm``: unit is (U,Tmax,256).
+        ``rng``: with ``noise=None``, ``(seed, keys, scale)`` with one key per OUTPUT row (qvc_infer_fanout_ragged_rng)."""
         mc = self.model_config
         if unit_fm:
             U, T, cu = unit.shape
         else:
             U, cu, T = unit.shape
         R = int(src_of_row.shape[0]) if src_of_row.dim() == 1 else -1
-        if cu != mc.get("unit_channels", 256) or tuple(frames.shape) != (U,) or R < U or g.shape != (R, mc["gin_channels"]) or \
-                tuple(noise.shape) != (R, mc["inter_channels"], T):
+        if cu != mc.get("unit_channels", 256) or tuple(frames.shape) != (U,) or R < U or g.shape != (R, mc["gin_channels"]):
             raise ValueError(f"bad input shapes: unit {tuple(unit.shape)}, frames {tuple(frames.shape)}, src_of_row {tuple(src_of_row.shape)}, "
-                             f"g {tuple(g.shape)}, noise {tuple(noise.shape)} (rows >= sources >= 1)")
+                             f"g {tuple(g.shape)} (rows >= sources >= 1)")
+        noise, desc, keys_dev = self._draw(noise, rng, R, (R, mc["inter_channels"], T))
         if frames.device.type != "cuda":                       # host-side values can be validated for free
             if int(frames.min()) < 2 or int(frames.max()) > T:
                 raise ValueError(f"frames must lie in [2, {T}], got [{int(frames.min())}, {int(frames.max())}]")
         if src_of_row.device.type != "cuda":
             if int(src_of_row.min()) < 0 or int(src_of_row.max()) >= U:
                 raise ValueError(f"src_of_row must lie in [0, {U - 1}], got [{int(src_of_row.min())}, {int(src_of_row.max())}]")
-        unit, g, noise = (self._f32(t, self.device) for t in (unit, g, noise))
+        unit, g = (self._f32(t, self.device) for t in (unit, g))
         lens = frames.to(device=self.device, dtype=torch.int32).contiguous()
         src = src_of_row.to(device=self.device, dtype=torch.int32).contiguous()
         if out is None:
             out = torch.empty(R, 1, T * self.samples_per_frame, dtype=torch.float32, device=self.device)
         if ws is None:
             ws = self.workspace(R, T, sources=U)
-        fn = self.lib.qvc_infer_fanout_ragged_fm if unit_fm else self.lib.qvc_infer_fanout_ragged
+        if desc is None:
+            fn = self.lib.qvc_infer_fanout_ragged_fm if unit_fm else self.lib.qvc_infer_fanout_ragged
+            draw = noise.data_ptr()
+        else:
+            fn = self.lib.qvc_infer_fanout_ragged_rng_fm if unit_fm else self.lib.qvc_infer_fanout_ragged_rng
+            draw = ctypes.byref(desc)
         st = fn(ctypes.byref(self.cfg), self.blob.data_ptr(), unit.data_ptr(), lens.data_ptr(), src.data_ptr(), g.data_ptr(),
-                noise.data_ptr(), out.data_ptr(), U, R, T, ws.data_ptr(), ws.numel(),
+                draw, out.data_ptr(), U, R, T, ws.data_ptr(), ws.numel(),
                 torch.cuda.current_stream(self.device).cuda_stream)
         L.check(self.lib, st, "qvc_infer_fanout_ragged")
         return out
@@ -230,14 +281,26 @@ class QvcEngine:
         return vals
 
     @_on_device
-    def stream_step(self, state: torch.Tensor, ws: torch.Tensor, unit_new: torch.Tensor, g: torch.Tensor, noise_new: torch.Tensor,
-                    out: torch.Tensor, pos: torch.Tensor, lens: torch.Tensor) -> None:
-        """One hop for every stream (all tensors fp32 / int32, contiguous, on this device; see include/qvc.h)."""
+    def stream_step(self, state: torch.Tensor, ws: torch.Tensor, unit_new: torch.Tensor, g: torch.Tensor, noise_new: Optional[torch.Tensor],
+                    out: torch.Tensor, pos: torch.Tensor, lens: torch.Tensor, rng=None) -> None:
+        """One hop for every stream (all tensors fp32 / int32, contiguous, on this device; see include/qvc.h).
+        ``rng``: with ``noise_new=None``, ``(seed, keys, scale)`` with ``keys`` an int64 tensor of one key per slot ON THIS
+        DEVICE (qvc_stream_step_rng): the caller writes keys[slot] when it admits a stream; a captured step holds the
+        array's pointer, so the tensor must outlive the graph."""
         B, _, hop = unit_new.shape
-        st = self.lib.qvc_stream_step(ctypes.byref(self.cfg), self.blob.data_ptr(), state.data_ptr(), state.numel(),
-                                      unit_new.data_ptr(), g.data_ptr(), noise_new.data_ptr(), out.data_ptr(), B, hop,
-                                      pos.data_ptr(), lens.data_ptr(), ws.data_ptr(), ws.numel(),
-                                      torch.cuda.current_stream(self.device).cuda_stream)
+        if rng is not None and not (torch.is_tensor(rng[1]) and rng[1].device == self.device):
+            raise ValueError("stream_step needs the rng keys as an int64 tensor on the engine's device (slots are rewritten in place)")
+        noise_new, desc, _ = self._draw(noise_new, rng, B, (B, self.model_config["inter_channels"], hop))
+        if desc is None:
+            st = self.lib.qvc_stream_step(ctypes.byref(self.cfg), self.blob.data_ptr(), state.data_ptr(), state.numel(),
+                                          unit_new.data_ptr(), g.data_ptr(), noise_new.data_ptr(), out.data_ptr(), B, hop,
+                                          pos.data_ptr(), lens.data_ptr(), ws.data_ptr(), ws.numel(),
+                                          torch.cuda.current_stream(self.device).cuda_stream)
+        else:
+            st = self.lib.qvc_stream_step_rng(ctypes.byref(self.cfg), self.blob.data_ptr(), state.data_ptr(), state.numel(),
+                                              unit_new.data_ptr(), g.data_ptr(), ctypes.byref(desc), out.data_ptr(), B, hop,
+                                              pos.data_ptr(), lens.data_ptr(), ws.data_ptr(), ws.numel(),
+                                              torch.cuda.current_stream(self.device).cuda_stream)
         L.check(self.lib, st, "qvc_stream_step")
 
     @_on_device

@@ -46,6 +46,11 @@ class QvcLaunchRecord(ctypes.Structure):
                 ("bytes", ctypes.c_double)]
 
 
+class QvcNoiseRng(ctypes.Structure):
+    """qvc_noise_rng: the noise as a counter-based generator (seed, one uint64 key per row on the device, noise_scale)."""
+    _fields_ = [("seed", ctypes.c_uint64), ("keys_dev", ctypes.c_void_p), ("scale", ctypes.c_float)]
+
+
 class QvcError(RuntimeError):
     pass
 
@@ -163,6 +168,23 @@ def declare(lib: ctypes.CDLL, prefix: str = "qvc") -> None:
             fn = getattr(lib, prefix + name)
             fn.restype = ctypes.c_int
             fn.argtypes = [cfgp, V, V, V, V, V, V, V, I, I, I, V, L, V]
+    # the generator forms (the noise computed at its draw site): one _rng twin per whole-path entry point + qvc_noise_fill
+    if hasattr(lib, prefix + "_noise_fill"):
+        rngp = P(QvcNoiseRng)
+        for name in ("_infer_batch_ragged_rng", "_infer_batch_ragged_rng_fm"):
+            fn = getattr(lib, prefix + name)
+            fn.restype = ctypes.c_int
+            fn.argtypes = [cfgp, V, V, V, rngp, V, I, I, V, V, L, V]
+        for name in ("_infer_fanout_ragged_rng", "_infer_fanout_ragged_rng_fm"):
+            fn = getattr(lib, prefix + name)
+            fn.restype = ctypes.c_int
+            fn.argtypes = [cfgp, V, V, V, V, V, rngp, V, I, I, I, V, L, V]
+        fn = getattr(lib, prefix + "_stream_step_rng")
+        fn.restype = ctypes.c_int
+        fn.argtypes = [cfgp, V, V, L, V, V, rngp, V, I, I, V, V, V, L, V]
+        fn = getattr(lib, prefix + "_noise_fill")
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_uint64, V, ctypes.c_float, I, I, I, I, V, V]
 
 
 _lib = None

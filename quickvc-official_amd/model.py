@@ -350,43 +350,64 @@ class SynthesizerTrn(nn.Module):
         return g
 
     @torch.no_grad()
-    def infer_batch(self, unit: Tensor, g: Tensor, noise: Optional[Tensor] = None) -> Tensor:
-        """Batched path: unit (B,256,F), g (B,gin) or (B,gin,1), noise (B,inter,F) -> (B,1,320*F)."""
+    def infer_batch(self, unit: Tensor, g: Tensor, noise: Optional[Tensor] = None, seed: Optional[int] = None, keys=None,
+                    noise_scale: float = 1.0) -> Tensor:
+        """Batched path: unit (B,256,F), g (B,gin) or (B,gin,1), noise (B,inter,F) -> (B,1,320*F).
+        ``seed``: draw the noise on the device instead (the library's counter-based generator): row b's draw is a function
+        of (seed, keys[b], channel, frame) alone -- ``keys`` B integers, default 0 .. B-1 -- scaled by ``noise_scale``."""
         eng = self.engine()
+        if seed is not None:
+            B, F = unit.shape[0], unit.shape[2]
+            return eng.infer_batch_ragged(unit, g.reshape(B, -1), None, torch.full((B,), F, dtype=torch.int32),
+                                          rng=self._rng(seed, keys, noise_scale, B, noise))
         if noise is None:
             noise = torch.randn(unit.shape[0], self.model_config["inter_channels"], unit.shape[2],
                                 device=unit.device, dtype=torch.float32)
         return eng.infer_batch(unit, g.reshape(g.shape[0], -1), noise)
 
+    @staticmethod
+    def _rng(seed, keys, noise_scale, rows: int, noise):
+        if noise is not None:
+            raise ValueError("pass noise or seed, not both")
+        keys = list(range(rows)) if keys is None else keys
+        if (int(keys.shape[0]) if torch.is_tensor(keys) else len(keys)) != rows:
+            raise ValueError(f"{rows} rows need {rows} keys")
+        return (int(seed), keys, float(noise_scale))
+
     @torch.no_grad()
-    def infer_ragged(self, units, g: Tensor, noises=None):
+    def infer_ragged(self, units, g: Tensor, noises=None, seed: Optional[int] = None, keys=None, noise_scale: float = 1.0):
         """Utterances of DIFFERENT lengths in one launch sequence (the reference converts any length per call,
         convert.py:58-86): ``units`` is a list of (256, F_b) / (1, 256, F_b) tensors, g (B, gin) or (B, gin, 1),
         ``noises`` an optional list of (inter, F_b) draws.  Returns a list of (1, 320*F_b) fp32 waveforms -- each
-        equal to the utterance converted alone (every conv sees ITS sequence end, not the padded batch's)."""
+        equal to the utterance converted alone (every conv sees ITS sequence end, not the padded batch's).
+        ``seed`` / ``keys`` / ``noise_scale``: as ``infer_batch`` -- with them an utterance's waveform does not depend on
+        the batch it is converted in either."""
         eng = self.engine()
         dev = eng.device
         us = [u.reshape(-1, u.shape[-1]) for u in units]
         lens = [int(u.shape[-1]) for u in us]
         B, tmax, inter = len(us), max(lens), self.model_config["inter_channels"]
+        rng = self._rng(seed, keys, noise_scale, B, noises) if seed is not None else None
         unit = torch.zeros(B, us[0].shape[0], tmax, device=dev, dtype=torch.float32)
-        noise = torch.zeros(B, inter, tmax, device=dev, dtype=torch.float32)
+        noise = torch.zeros(B, inter, tmax, device=dev, dtype=torch.float32) if rng is None else None
         for b, u in enumerate(us):
             unit[b, :, :lens[b]] = u.to(dev, torch.float32)
-            n = noises[b].reshape(inter, -1).to(dev, torch.float32) if noises is not None else \
-                torch.randn(inter, lens[b], device=dev, dtype=torch.float32)
-            noise[b, :, :lens[b]] = n
-        out = eng.infer_batch_ragged(unit, g.reshape(B, -1), noise, torch.tensor(lens, dtype=torch.int32))
+            if rng is None:
+                n = noises[b].reshape(inter, -1).to(dev, torch.float32) if noises is not None else \
+                    torch.randn(inter, lens[b], device=dev, dtype=torch.float32)
+                noise[b, :, :lens[b]] = n
+        out = eng.infer_batch_ragged(unit, g.reshape(B, -1), noise, torch.tensor(lens, dtype=torch.int32), rng=rng)
         spf = self.samples_per_frame
         return [out[b, :, :lens[b] * spf] for b in range(B)]
 
     @torch.no_grad()
-    def infer_fanout(self, units, src_of_row, g: Tensor, noises=None):
+    def infer_fanout(self, units, src_of_row, g: Tensor, noises=None, seed: Optional[int] = None, keys=None, noise_scale: float = 1.0):
         """Any-to-many conversion: ``units`` is the list of U DISTINCT sources ((256, F_u) / (1, 256, F_u) tensors),
         ``src_of_row`` a list of R ints -- the source of every output row, each in [0, U) --, g (R, gin) or (R, gin, 1) the
         target speaker of every row, ``noises`` an optional list of R draws (inter, F_src).  Returns a list of R
         (1, 320*F_src) fp32 waveforms, each equal to what ``infer_ragged`` gives for that (source, g, noise); every
-        source is encoded once (enc_p does not see the speaker, models.py:638-640)."""
+        source is encoded once (enc_p does not see the speaker, models.py:638-640).
+        ``seed`` / ``keys`` (one per OUTPUT row, default 0 .. R-1) / ``noise_scale``: as ``infer_batch``."""
         eng = self.engine()
         dev = eng.device
         us = [u.reshape(-1, u.shape[-1]) for u in units]
@@ -398,12 +419,15 @@ class SynthesizerTrn(nn.Module):
         unit = torch.zeros(U, us[0].shape[0], tmax, device=dev, dtype=torch.float32)
         for u, x in enumerate(us):
             unit[u, :, :lens[u]] = x.to(dev, torch.float32)
-        noise = torch.zeros(R, inter, tmax, device=dev, dtype=torch.float32)
+        rng = self._rng(seed, keys, noise_scale, R, noises) if seed is not None else None
+        noise = torch.zeros(R, inter, tmax, device=dev, dtype=torch.float32) if rng is None else None
         for r, s in enumerate(src):
+            if rng is not None:
+                break
             n = noises[r].reshape(inter, -1).to(dev, torch.float32) if noises is not None else \
                 torch.randn(inter, lens[s], device=dev, dtype=torch.float32)
             noise[r, :, :lens[s]] = n
         out = eng.infer_fanout_ragged(unit, torch.tensor(lens, dtype=torch.int32), torch.tensor(src, dtype=torch.int32),
-                                      g.reshape(R, -1), noise)
+                                      g.reshape(R, -1), noise, rng=rng)
         spf = self.samples_per_frame
         return [out[r, :, :lens[s] * spf] for r, s in enumerate(src)]

@@ -96,9 +96,15 @@ class StreamConverter:
     object, every step is ONE replay of a captured hipGraph (fixed shapes; the stream position is a device
     counter the graph itself advances), and a frame costs about (2*H + hop)/hop of its offline cost per segment
     instead of (2*88 + hop)/hop.  Output lags the input by ``self.lag`` frames -- the look-ahead the non-causal
-    network needs; it is exact, including the first and last frames of a stream."""
+    network needs; it is exact, including the first and last frames of a stream.
 
-    def __init__(self, model, streams: int, hop_frames: int = 320, use_graph: bool = True):
+    The noise comes either as a tensor per step (``step(unit_new, noise_new)``, aligned by ``noise_lag``) or from the
+    library's counter-based generator (``seed``: ``step(unit_new)`` alone; every slot draws from the key given to
+    ``start`` / ``convert`` at the stream's absolute frames, so a streamed utterance equals its offline conversion under
+    the same (seed, key) with nothing to align)."""
+
+    def __init__(self, model, streams: int, hop_frames: int = 320, use_graph: bool = True, seed: Optional[int] = None,
+                 noise_scale: float = 1.0):
         from .engine import aligned_empty
         self.model, self.streams, self.hop = model, int(streams), int(hop_frames)
         self.engine = model.engine()
@@ -119,6 +125,10 @@ class StreamConverter:
         self._graph = None
         self._pos_host = [0] * S
         self._len_host = [2 ** 30] * S
+        self._keys = torch.zeros(S, dtype=torch.int64, device=dev)   # generator key per slot (read by the step as uint64)
+        self._use_graph = use_graph
+        self._rng = None                                         # (seed, noise_scale) of the generator form, once asked for
+        self._rng_graph = None
         self.reset()
         if use_graph:
             with torch.cuda.stream(self._stream):
@@ -128,10 +138,32 @@ class StreamConverter:
                 with torch.cuda.graph(self._graph, stream=self._stream):
                     self._one_step()
             self.reset()
+        if seed is not None:
+            self.set_seed(seed, noise_scale)
 
-    def _one_step(self):
-        self.engine.stream_step(self._state, self._ws, self._unit, self._g, self._noise, self._out, self._pos, self._len)
+    def _one_step(self, rng: bool = False):
+        if rng:
+            self.engine.stream_step(self._state, self._ws, self._unit, self._g, None, self._out, self._pos, self._len,
+                                    rng=(self._rng[0], self._keys, self._rng[1]))
+        else:
+            self.engine.stream_step(self._state, self._ws, self._unit, self._g, self._noise, self._out, self._pos, self._len)
         self._pos.add_(self.hop)                                 # inside the graph: the position advances with every replay
+
+    def set_seed(self, seed: int, noise_scale: float = 1.0) -> None:
+        """Choose the generator form's seed and noise_scale.  They are baked into the captured step, so a new pair means
+        a warm-up step and a new capture: ALL slots are reset.  The same pair again is free."""
+        if self._rng == (int(seed), float(noise_scale)):
+            return
+        self._rng = (int(seed), float(noise_scale))
+        self._rng_graph = None
+        if self._use_graph:
+            with torch.cuda.stream(self._stream):
+                self._one_step(rng=True)                          # warm-up (code objects)
+                self._stream.synchronize()
+                self._rng_graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self._rng_graph, stream=self._stream):
+                    self._one_step(rng=True)
+        self.reset()
 
     def _after_caller(self, *tensors) -> None:
         """Order the side stream after the caller's current stream (inputs such as a freshly computed ``g`` may still be
@@ -165,10 +197,11 @@ class StreamConverter:
         self._len_host = [int(v) for v in torch.as_tensor(lengths).tolist()]
 
     # ---- per-slot lifecycle: streams of a server start and end at different times
-    def start(self, slot: int, g: torch.Tensor, length: Optional[int] = None) -> None:
+    def start(self, slot: int, g: torch.Tensor, length: Optional[int] = None, key: Optional[int] = None) -> None:
         """Admit a new stream into ``slot``: that slot's ring rows are zeroed and its position goes back to 0 on the
         device (qvc_stream_reset_slot); the other slots keep running and the captured graph is unchanged.  ``g`` (gin,)
-        or (1, gin): the stream's speaker embedding; ``length``: its frame count if already known."""
+        or (1, gin): the stream's speaker embedding; ``length``: its frame count if already known; ``key``: the
+        stream's generator key (the slot keeps its previous one if None)."""
         if not 0 <= slot < self.streams:
             raise ValueError(f"slot {slot} outside [0, {self.streams})")
         n = 2 ** 30 if length is None else int(length)
@@ -176,6 +209,9 @@ class StreamConverter:
         with torch.cuda.stream(self._stream):
             self.engine.stream_reset_slot(self._state, self.streams, self.hop, slot, n, self._pos, self._len)
             self._g[slot].copy_(g.reshape(-1), non_blocking=True)
+            if key is not None:
+                k = int(key) & 0xFFFFFFFFFFFFFFFF
+                self._keys[slot:slot + 1].fill_(k - (1 << 64) if k >> 63 else k)
         self._pos_host[slot] = 0
         self._len_host[slot] = n
 
@@ -194,19 +230,24 @@ class StreamConverter:
         return self._pos_host[slot] - self.lag >= self._len_host[slot]
 
     @torch.no_grad()
-    def step(self, unit_new: torch.Tensor, noise_new: torch.Tensor) -> torch.Tensor:
+    def step(self, unit_new: torch.Tensor, noise_new: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Feed frames [pos, pos+hop) of every stream (unit_new (S, 256, hop)) and the noise for frames
         [pos - noise_lag, ... + hop) (noise_new (S, inter, hop)); returns the waveform of frames
-        [pos - lag, pos - lag + hop) as (S, hop * samples_per_frame) -- zeros where that lies outside the stream."""
+        [pos - lag, pos - lag + hop) as (S, hop * samples_per_frame) -- zeros where that lies outside the stream.
+        ``noise_new=None``: the generator form (needs a seed: the constructor's, ``set_seed`` or ``convert(seed=...)``)."""
+        if noise_new is None and self._rng is None:
+            raise ValueError("step() without noise_new needs a seed (StreamConverter(seed=...) or set_seed)")
         dev = self.engine.device
         self._stream.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(self._stream):
             self._unit.copy_(unit_new, non_blocking=True)
-            self._noise.copy_(noise_new, non_blocking=True)
-            if self._graph is not None:
-                self._graph.replay()
+            if noise_new is not None:
+                self._noise.copy_(noise_new, non_blocking=True)
+            graph = self._graph if noise_new is not None else self._rng_graph
+            if graph is not None:
+                graph.replay()
             else:
-                self._one_step()
+                self._one_step(rng=noise_new is None)
             out = self._out.clone()
         torch.cuda.current_stream(dev).wait_stream(self._stream)
         self._pos_host = [p + self.hop for p in self._pos_host]
@@ -214,27 +255,41 @@ class StreamConverter:
 
     @torch.no_grad()
     def convert(self, unit: torch.Tensor, g: torch.Tensor, noise: Optional[torch.Tensor] = None,
-                lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+                lengths: Optional[torch.Tensor] = None, seed: Optional[int] = None, keys=None) -> torch.Tensor:
         """Convenience: stream whole utterances through the step interface.  unit (S, 256, T), g (S, gin),
         noise (S, inter, T) -> (S, 1, T * samples_per_frame); equals infer_batch on the whole thing.  ``lengths`` (S,):
-        streams that end before T (their rows are zero after the end, as with infer_batch_ragged)."""
+        streams that end before T (their rows are zero after the end, as with infer_batch_ragged).
+        ``seed`` / ``keys`` (S integers, default 0 .. S-1) instead of ``noise``: the generator form -- equals
+        ``infer_batch_ragged(..., rng=(seed, keys, noise_scale))``; the noise_scale is the constructor's / ``set_seed``'s."""
         S, UC, T = unit.shape
         if S != self.streams:
             raise ValueError(f"built for {self.streams} streams, got {S}")
+        if seed is not None and noise is not None:
+            raise ValueError("pass noise or seed, not both")
         dev = self.engine.device
         inter = self.model.model_config["inter_channels"]
-        if noise is None:
+        use_rng = seed is not None
+        if use_rng:
+            self.set_seed(seed, self._rng[1] if self._rng else 1.0)
+        elif noise is None:
             noise = torch.randn(S, inter, T, device=dev)
-        unit, noise = unit.to(dev, torch.float32), noise.to(dev, torch.float32)
+        unit = unit.to(dev, torch.float32)
         h, lag, nl, spf = self.hop, self.lag, self.noise_lag, self.spf
         self.reset(g.to(dev, torch.float32), torch.full((S,), T, dtype=torch.int32) if lengths is None else lengths)
         out = torch.zeros(S, 1, T * spf, device=dev)
         pad_u = torch.nn.functional.pad(unit, (0, h + lag))                      # frames past the end: ignored by the kernels
-        pad_n = torch.nn.functional.pad(noise, (nl, h + lag))                    # frame f of the noise sits at column f + nl
+        if use_rng:
+            u64 = [int(k) & 0xFFFFFFFFFFFFFFFF for k in (range(S) if keys is None else keys)]
+            if len(u64) != S:
+                raise ValueError(f"{S} streams need {S} keys, got {len(u64)}")
+            with torch.cuda.stream(self._stream):
+                self._keys.copy_(torch.tensor([k - (1 << 64) if k >> 63 else k for k in u64], dtype=torch.int64))
+        else:
+            pad_n = torch.nn.functional.pad(noise.to(dev, torch.float32), (nl, h + lag))   # frame f of the noise sits at column f + nl
         steps = -(-(T + lag) // h)
         for n in range(steps):
             s = n * h
-            chunk = self.step(pad_u[:, :, s:s + h], pad_n[:, :, s:s + h])         # noise frames [s - nl, s - nl + h)
+            chunk = self.step(pad_u[:, :, s:s + h], None if use_rng else pad_n[:, :, s:s + h])   # noise frames [s - nl, s - nl + h)
             f0 = s - lag
             lo, hi = max(f0, 0), min(f0 + h, T)
             if hi > lo:
