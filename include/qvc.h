@@ -120,7 +120,7 @@ int qvc_device_check(void);
 /* Developer / test switches (launch-shape and kernel-selection variants that must give identical results; the GPU
  * tests flip them in-process).  The library never reads environment variables: a switch changes only through this
  * call.  Names: "post_tail", "post_tail_nf", "pair_wide_launch", "pair_cm4", "conv_cl", "wn_chunk", "pair_chain3",
- * "wn_kernel", "launch_stop" (-1 = off; n >= 0: the whole-path entry points -- qvc_infer_batch[_ex|_timed|_ragged[_fm]],
+ * "wn_kernel", "live_trim" (1: qvc_live_step trims each stage's window, 0: every stage over the whole window), "launch_stop" (-1 = off; n >= 0: the whole-path entry points -- qvc_infer_batch[_ex|_timed|_ragged[_fm]],
  * qvc_infer_fanout_ragged[_fm], qvc_enc_q, qvc_flow_forward -- issue only their first n launches).  qvc_debug_get also reads "launch_steps" (read-only:
  * the launches the last such call would have issued without a stop).  Unknown name: QVC_ERR_BAD_ARG.  No reference
  * counterpart. */
@@ -293,6 +293,45 @@ int qvc_stream_step_rng(const qvc_config* cfg, const void* blob_dev, void* state
  * the bits of its _rng twin (the bridge between the two forms, and the way to inspect a draw).  channels % 4 == 0. */
 int qvc_noise_fill(uint64_t seed, const uint64_t* keys_dev, float scale, int32_t rows, int32_t channels, int32_t frames,
                    int32_t frame0, float* noise_out, void* stream);
+
+/* ---- streaming with a bounded look-ahead: a windowed step for EVERY decoder ---------------------------------------
+ * qvc_stream_step is exact and cheap, but its output lags the input by the whole receptive field (90 frames = 1.8 s at
+ * the shipped config) and it takes the band-synthesis decoders with two up-samplers only.  qvc_live_step lets the
+ * caller choose the lag, L = look_ahead in [0, C], C = qvc_live_context_frames(cfg), and takes every configuration the
+ * offline path takes.  The state is ONE ring per stream: the last W = C + L + hop unit frames (and their noise frames).
+ * A step appends the new frames, runs the whole path over the W-row window -- whose last row is the newest frame, so
+ * the kernels see a sequence that ends there -- and delivers rows [C, C + hop):
+ *   out = frames [pos[b] - L, pos[b] - L + hop) of qvc_infer_batch_ragged on the stream's first min(len, pos + hop)
+ *   frames (same g, same noise or (seed, key)); zeros outside [0, len[b]).
+ * That is the prefix conversion, defined exactly, not an approximation of the whole-utterance result; with L = C the
+ * two agree and the concatenated outputs ARE the whole-utterance conversion (exact streaming -- for the single-band
+ * decoder and one-up-sampler decoders the only streaming form).  A frame costs (C + L + hop) / hop of its offline cost
+ * in enc_p, less in the stages after it: rows a stage can no longer use are dropped before the next stage runs.
+ *   state      caller-owned device buffer of qvc_live_state_bytes(); a slot is started with qvc_live_reset_slot
+ *              (or the whole buffer zeroed and pos = 0)
+ *   unit_new   (B, unit_channels, hop) fp32: unit frames [pos[b], pos[b] + hop) (anything past the sequence end)
+ *   noise_new  (B, inter_channels, hop) fp32: the N(0,1) draw for the SAME frames -- no noise lag.  The _rng twin
+ *              draws at the absolute frame of every window row instead (keys_dev: one key per slot)
+ *   out        (B, hop * samples_per_frame) fp32
+ *   pos_dev, len_dev  as qvc_stream_step: the caller advances pos by hop between steps; a stream of length n is
+ *              flushed once pos - L >= n.
+ * hop < 1, batch < 1 or look_ahead outside [0, C]: QVC_ERR_BAD_ARG (the size queries return the code as their value).
+ * Asynchronous, allocation-free, capturable on one stream.  csrc/qvc_stream.h (live_step) has the details. */
+int32_t qvc_live_context_frames(const qvc_config* cfg);
+int64_t qvc_live_state_bytes(const qvc_config* cfg, int32_t batch, int32_t hop, int32_t look_ahead);
+int64_t qvc_live_workspace_bytes(const qvc_config* cfg, int32_t batch, int32_t hop, int32_t look_ahead);
+int qvc_live_step(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes,
+                  const float* unit_new, const float* g, const float* noise_new, float* out,
+                  int32_t batch, int32_t hop, int32_t look_ahead, const int32_t* pos_dev, const int32_t* len_dev,
+                  void* workspace, int64_t workspace_bytes, void* stream);
+int qvc_live_step_rng(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes,
+                      const float* unit_new, const float* g, const qvc_noise_rng* rng, float* out,
+                      int32_t batch, int32_t hop, int32_t look_ahead, const int32_t* pos_dev, const int32_t* len_dev,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+/* Admit a new stream into slot `slot`: zeroes that slot's ring rows and sets pos_dev[slot] = 0, len_dev[slot] = length
+ * on `stream` (as qvc_stream_reset_slot; the caller copies the slot's g row and generator key itself). */
+int qvc_live_reset_slot(const qvc_config* cfg, void* state, int64_t state_bytes, int32_t batch, int32_t hop,
+                        int32_t look_ahead, int32_t slot, int32_t length, int32_t* pos_dev, int32_t* len_dev, void* stream);
 
 /* ---- optional fork/join resources: lets the three independent ResBlocks of an MRF stage
  * (models.py:378-384) run as parallel branches (two auxiliary non-blocking streams + events), so a

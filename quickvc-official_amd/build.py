@@ -3,6 +3,7 @@
   libqvc_hip.so      -- the product: gfx950 kernels + C ABI + host packer (hipcc --offload-arch=gfx950)
   libqvc_io.so       -- the product's host-side batch file I/O (g++; include/qvc_io.h)
   oracle/_build/libqvc_emu.so -- TEST-ONLY host emulation of the launch sequence (g++/hipcc host code)
+  oracle/_build/libqvc_emu_live.so -- TEST-ONLY CPU twin of qvc_live_step on the same emulation (tests/emu_live.cpp)
 
 hipcc cross-compiles gfx950 without a GPU.  Translation units compile in parallel.
 """
@@ -22,6 +23,7 @@ LIB = os.path.join(PKG, "libqvc_hip.so")
 IO_LIB = os.path.join(PKG, "libqvc_io.so")
 EMU_DIR = os.path.join(ROOT, "oracle", "_build")
 EMU_LIB = os.path.join(EMU_DIR, "libqvc_emu.so")
+EMU_LIVE_LIB = os.path.join(EMU_DIR, "libqvc_emu_live.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
@@ -106,9 +108,21 @@ def build_emu(force: bool = False) -> str:
     return EMU_LIB
 
 
+def build_emu_live(force: bool = False) -> str:
+    """The CPU twin of qvc_live_step (tests only): tests/emu_live.cpp includes the frozen oracle/qvc_emu.cpp and adds
+    qvc_emu_live_step on its backend -- a library of its own, the emulation library stays as it was."""
+    os.makedirs(EMU_DIR, exist_ok=True)
+    srcs = [os.path.join(ROOT, "tests", "emu_live.cpp"), os.path.join(CSRC, "qvc_pack.cpp")]
+    deps = srcs + [os.path.join(ROOT, "oracle", "qvc_emu.cpp")] + [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(ROOT, "include", "qvc.h")]
+    if force or not _newer(EMU_LIVE_LIB, deps):
+        _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", EMU_LIVE_LIB] + srcs)
+    return EMU_LIVE_LIB
+
+
 if __name__ == "__main__":
     force = "--force" in sys.argv
     print(build_hip(force, verbose=True))
     print(build_hip(force, variant="sat"))
     print(build_io(force))
     print(build_emu(force))
+    print(build_emu_live(force))

@@ -301,6 +301,26 @@ int stream_step_api(const qvc_config* cfg, const void* blob_dev, void* state, in
   return st != QVC_OK ? st : be.finish();
 }
 
+// qvc_live_step (noise_new) and qvc_live_step_rng (rng): exactly one of the two
+int live_step_api(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
+                  const float* g, const float* noise_new, const qvc_noise_rng* rng, float* out, int32_t batch, int32_t hop,
+                  int32_t look_ahead, const int32_t* pos_dev, const int32_t* len_dev, void* workspace, int64_t workspace_bytes,
+                  void* stream) {
+  NoiseRng rv;
+  const bool draw = rng ? (!noise_new && rng_view(rng, rv)) : noise_new != nullptr;
+  if (!blob_dev || !state || !unit_new || !g || !draw || !out || !pos_dev || !len_dev || !workspace || batch <= 0) return QVC_ERR_BAD_ARG;
+  Plan P; LiveGeom G;
+  const int gs = live_plan(cfg, hop, look_ahead, P, G);
+  if (gs != QVC_OK) return gs;
+  if (state_bytes < carve_live_state(P, G, batch).bytes || workspace_bytes < carve_live_scratch(P, G, batch).bytes) return QVC_ERR_SMALL_BUFFER;
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255) || (reinterpret_cast<uintptr_t>(blob_dev) & 255) || (reinterpret_cast<uintptr_t>(state) & 255))
+    return QVC_ERR_BAD_ARG;
+  HipBackend be(stream);
+  const int st = live_step(P, G, static_cast<const char*>(blob_dev), static_cast<char*>(state), static_cast<char*>(workspace), unit_new, g,
+                           noise_new, out, batch, pos_dev, len_dev, be, rng ? &rv : nullptr, debug_get(DBG_LIVE_TRIM) != 0);
+  return st != QVC_OK ? st : be.finish();
+}
+
 }  // namespace
 
 extern "C" {
@@ -538,6 +558,61 @@ int qvc_stream_reset_slot(const qvc_config* cfg, void* state, int64_t state_byte
   for (int j = 0; j < 3; ++j) zero(S.s0[j], (int64_t)(2 * G.Hd2 + G.hop) * G.r0 * P.stages[0].ch * 2);
   ok = ok && hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(pos_dev + slot), 0, 1, st) == hipSuccess;
   ok = ok && hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(len_dev + slot), length, 1, st) == hipSuccess;   // no host buffer involved
+  return ok ? QVC_OK : QVC_ERR_LAUNCH;
+}
+
+int32_t qvc_live_context_frames(const qvc_config* cfg) {
+  Plan P; LiveGeom G;
+  const int st = live_plan(cfg, 1, 0, P, G);
+  return st != QVC_OK ? st : G.C();
+}
+
+int64_t qvc_live_state_bytes(const qvc_config* cfg, int32_t batch, int32_t hop, int32_t look_ahead) {
+  Plan P; LiveGeom G;
+  const int st = batch > 0 ? live_plan(cfg, hop, look_ahead, P, G) : QVC_ERR_BAD_ARG;
+  return st != QVC_OK ? st : carve_live_state(P, G, batch).bytes;
+}
+
+int64_t qvc_live_workspace_bytes(const qvc_config* cfg, int32_t batch, int32_t hop, int32_t look_ahead) {
+  Plan P; LiveGeom G;
+  const int st = batch > 0 ? live_plan(cfg, hop, look_ahead, P, G) : QVC_ERR_BAD_ARG;
+  return st != QVC_OK ? st : carve_live_scratch(P, G, batch).bytes;
+}
+
+int qvc_live_step(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
+                  const float* g, const float* noise_new, float* out, int32_t batch, int32_t hop, int32_t look_ahead,
+                  const int32_t* pos_dev, const int32_t* len_dev, void* workspace, int64_t workspace_bytes, void* stream) {
+  return live_step_api(cfg, blob_dev, state, state_bytes, unit_new, g, noise_new, nullptr, out, batch, hop, look_ahead, pos_dev, len_dev,
+                       workspace, workspace_bytes, stream);
+}
+
+int qvc_live_step_rng(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
+                      const float* g, const qvc_noise_rng* rng, float* out, int32_t batch, int32_t hop, int32_t look_ahead,
+                      const int32_t* pos_dev, const int32_t* len_dev, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!rng) return QVC_ERR_BAD_ARG;
+  return live_step_api(cfg, blob_dev, state, state_bytes, unit_new, g, nullptr, rng, out, batch, hop, look_ahead, pos_dev, len_dev,
+                       workspace, workspace_bytes, stream);
+}
+
+int qvc_live_reset_slot(const qvc_config* cfg, void* state, int64_t state_bytes, int32_t batch, int32_t hop, int32_t look_ahead,
+                        int32_t slot, int32_t length, int32_t* pos_dev, int32_t* len_dev, void* stream) {
+  if (!state || !pos_dev || !len_dev || batch <= 0 || slot < 0 || slot >= batch || length < 0) return QVC_ERR_BAD_ARG;
+  Plan P; LiveGeom G;
+  const int gs = live_plan(cfg, hop, look_ahead, P, G);
+  if (gs != QVC_OK) return gs;
+  const LiveState S = carve_live_state(P, G, batch);
+  if (state_bytes < S.bytes) return QVC_ERR_SMALL_BUFFER;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char* base = static_cast<char*>(state);
+  bool ok = true;
+  // both rings are batch-major, so a stream's rows are one contiguous range per ring
+  auto zero = [&](int64_t ring, int64_t per_stream) {
+    ok = ok && hipMemsetAsync(base + ring + (int64_t)slot * per_stream, 0, (size_t)per_stream, st) == hipSuccess;
+  };
+  zero(S.unit, (int64_t)P.cfg.unit_channels * G.W * 4);
+  zero(S.noise, (int64_t)P.cfg.inter_channels * G.W * 4);
+  ok = ok && hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(pos_dev + slot), 0, 1, st) == hipSuccess;
+  ok = ok && hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(len_dev + slot), length, 1, st) == hipSuccess;
   return ok ? QVC_OK : QVC_ERR_LAUNCH;
 }
 

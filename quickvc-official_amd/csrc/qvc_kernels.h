@@ -396,16 +396,17 @@ enum DebugSwitch : int32_t {
                             //    bit-identical, measured SLOWER -- the k 3 pairs cost less riding in the three-chain launches)
   DBG_WN_KERNEL,            // WaveNet stack kernel variant (0 = default; 1 generic, 2 / 3 the 32- / 64-frame continuous-stream tile)
   DBG_LAUNCH_STOP,          // -1 (default): off; n >= 0: the whole-path entry points issue only their steps [0, n) (Path::step)
+  DBG_LIVE_TRIM,            // 1 (default): qvc_live_step drops the rows a stage can no longer use before the next stage; 0: every stage over the whole window
   DBG_COUNT
 };
 inline std::atomic<int32_t>* debug_table() {
-  static std::atomic<int32_t> t[DBG_COUNT] = {{1}, {4}, {1}, {1}, {1}, {0}, {0}, {0}, {-1}};
+  static std::atomic<int32_t> t[DBG_COUNT] = {{1}, {4}, {1}, {1}, {1}, {0}, {0}, {0}, {-1}, {1}};
   return t;
 }
 inline int debug_get(int which) { return debug_table()[which].load(std::memory_order_relaxed); }
 inline const char* const* debug_names() {
   static const char* const n[DBG_COUNT] = {"post_tail", "post_tail_nf", "pair_wide_launch", "pair_cm4", "conv_cl", "wn_chunk", "pair_chain3", "wn_kernel",
-                                           "launch_stop"};
+                                           "launch_stop", "live_trim"};
   return n;
 }
 // Read-only companion of launch_stop (qvc_debug_get "launch_steps"): the steps the last whole-path call would have issued.

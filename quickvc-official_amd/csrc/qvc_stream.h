@@ -258,4 +258,201 @@ int stream_step(const Plan& P, const char* blob, char* state, char* ws, const fl
   return st;
 }
 
+// ---------------------------------------------------------------- windowed step with a bounded look-ahead (live_step)
+// The segment rings above are exact and cheap, but their output lags the input by lag() frames and stream_geom takes
+// the band-synthesis decoders with two up-samplers only.  live_step trades cost for latency and takes EVERY plan: it
+// keeps ONE ring -- the last W = C + L + hop unit frames of each stream (and, for the pointer form of the noise, their
+// noise frames) -- and runs the whole path (Path::infer) over that window, whose last row is the newest frame:
+//
+//     row:   0 ............. C ......... C+hop ......... C+L = W-hop ............ W
+//            |  left context  | delivered |   look-ahead  |  this step's new frames |
+//     frame: pos-L-C       pos-L       pos-L+hop         pos                     pos+hop
+//
+// The window ends where the stream has got to, so the kernels see a sequence that ends there (Ragged: the buffer end is
+// the sequence end unless lens[b] comes first): the delivered frames [pos - L, pos - L + hop) are those of the OFFLINE
+// conversion of the prefix [0, min(len, pos + hop)) -- exact by definition, not an approximation of the whole-utterance
+// result.  L = look_ahead in [0, C] is the caller's trade: 0 = no lag at all, C = the whole receptive field, where the
+// prefix conversion and the whole-utterance conversion agree on the delivered frames (exact streaming).
+// C bounds the one-sided receptive field of the path in unit frames: the window's first row is not the sequence start
+// (once pos - L > C), so the rows nearer than C to it lack left context and are never delivered.
+//     C = He + nf * Hf + Hdec,   Hdec = 3 (conv_pre) + r_0,   r_n = mrf + 8 at the last stage's output
+//     (conv_post k 7 + reflect pad, iSTFT overlap, synthesis FIR),   r_i = taps_i + ceil(r_{i+1} / rate_i) + 1 at stage
+//     i's input, + mrf for the ResBlocks of stage i - 1 in front of it
+// (89 at the shipped config; stream_geom's lag is 90, the measured receptive field 84).
+// Plain form: every stage over all W rows -- a frame costs W / hop of its offline cost in every stage.
+// Trimmed form (the default): a stage's first rows lack left context and no later stage can use them, so they are
+// dropped before the next stage runs.  Three segments, each a Path with its own T and off and a compact hand-off through
+// copy_batch, as stream_step's:
+//     E  enc_p                    rows [0, W)                    T = W
+//     F  the flow                 rows [He, W)                   T = W - He
+//     D  the decoder and the tail rows [He + nf * Hf, W)         T = Hdec + L + hop, delivered rows [Hdec, Hdec + hop)
+// The decoder -- 80 % of the path's FLOPs -- then costs (Hdec + L + hop) / hop per frame instead of W / hop (49 rows
+// instead of 113 at the shipped config, hop 16, L 8).  Every delivered row keeps the left context its stage needs, so
+// both forms compute the same values for it.
+struct LiveGeom {
+  int32_t status = QVC_OK;
+  int32_t He = 0, Hf = 0, nf = 0, Hdec = 0;
+  int32_t hop = 0, L = 0, W = 0;                   // set by live_plan
+  int C() const { return He + nf * Hf + Hdec; }
+};
+
+inline LiveGeom live_geom(const Plan& P) {
+  LiveGeom G;
+  if (P.status != QVC_OK) { G.status = P.status; return G; }
+  const qvc_config& c = P.cfg;
+  const int K2 = (c.wn_kernel_size - 1) / 2;
+  G.He = c.enc_layers * K2; G.Hf = c.flow_layers * K2; G.nf = c.n_flows;
+  int mrf = 0;               // one-sided reach of a ResBlock stack in its own frames (as in stream_geom)
+  for (int j = 0; j < c.n_resblocks; ++j) {
+    int s = 0;
+    for (int q = 0; q < 3; ++q) s += (c.resblock_kernel_sizes[j] - 1) / 2 * (c.resblock_dilations[j][q] + 1);
+    mrf = std::max(mrf, s);
+  }
+  int r = mrf + 8;
+  for (int i = c.n_ups - 1; i >= 0; --i) {
+    r = P.stages[(size_t)i].up.taps + ceil_div(r, c.upsample_rates[i]) + 1;
+    if (i > 0) r += mrf;
+  }
+  G.Hdec = 3 + r;
+  return G;
+}
+
+// What every live entry point starts from: the plan and the window for (cfg, hop, look_ahead), or why not.
+inline int live_plan(const qvc_config* cfg, int hop, int look_ahead, Plan& P, LiveGeom& G) {
+  if (!cfg || hop < 1) return QVC_ERR_BAD_ARG;
+  P = build_plan(*cfg);
+  G = live_geom(P);
+  if (G.status != QVC_OK) return G.status;
+  if (look_ahead < 0 || look_ahead > G.C()) return G.status = QVC_ERR_BAD_ARG;
+  if ((int64_t)G.C() + look_ahead + hop > (1 << 24)) return G.status = QVC_ERR_BAD_ARG;
+  G.hop = hop; G.L = look_ahead; G.W = G.C() + look_ahead + hop;
+  return QVC_OK;
+}
+
+struct LiveState {       // byte offsets into the caller-owned state buffer
+  int64_t unit = 0;      // fp32 (B, unit_channels, W), the reference's (B, C, T) layout
+  int64_t noise = 0;     // fp32 (B, inter_channels, W): the noise of the same frames (pointer form only)
+  int64_t bytes = 0;
+};
+
+inline LiveState carve_live_state(const Plan& P, const LiveGeom& G, int B) {
+  LiveState S;
+  int64_t off = 0;
+  auto take = [&](int64_t n) { int64_t o = off; off = align_up(off + n, 256); return o; };
+  S.unit = take((int64_t)B * P.cfg.unit_channels * G.W * 4);
+  S.noise = take((int64_t)B * P.cfg.inter_channels * G.W * 4);
+  S.bytes = off;
+  return S;
+}
+
+struct LiveScratch {     // carved from the END of the step's workspace, after the path's own workspace
+  int64_t path_bytes = 0;   // carve_workspace(P, B, W): the widest segment
+  int64_t zf = 0;           // fp32 [B][W - He][C]: z handed to the flow, updated in place (trimmed form)
+  int64_t zd = 0;           // fp32 [B][W - He - nf * Hf][C]: z handed to the decoder (trimmed form)
+  int64_t wave = 0;         // fp32 (B, spf * W): the window's waveform (trimmed form: of the decoder's rows)
+  int64_t tmp[2] = {};      // slide buffers: the kept W - hop frames of the unit / noise ring
+  int64_t bytes = 0;
+};
+
+inline LiveScratch carve_live_scratch(const Plan& P, const LiveGeom& G, int B) {
+  LiveScratch X;
+  X.path_bytes = carve_workspace(P, B, G.W).bytes;
+  int64_t off = X.path_bytes;
+  auto take = [&](int64_t n) { int64_t o = off; off = align_up(off + n, 256); return o; };
+  X.zf = take((int64_t)B * (G.W - G.He) * P.cfg.inter_channels * 4);
+  X.zd = take((int64_t)B * (G.W - G.He - G.nf * G.Hf) * P.cfg.inter_channels * 4);
+  X.wave = take((int64_t)B * samples_per_frame(P) * G.W * 4);
+  X.tmp[0] = take((int64_t)B * P.cfg.unit_channels * (G.W - G.hop) * 4);
+  X.tmp[1] = take((int64_t)B * P.cfg.inter_channels * (G.W - G.hop) * 4);
+  X.bytes = off;
+  return X;
+}
+
+// One step (G from live_plan).  Backend: as stream_step.
+//   unit_new  (B, unit_channels, hop) fp32: unit frames [pos, pos + hop) of every stream
+//   noise_new (B, inter, hop) fp32:         the N(0,1) draw of models.py:94 for the SAME frames (no noise lag)
+//   out       (B, hop * samples_per_frame): waveform of frames [pos - L, pos - L + hop); zeros where that is outside
+//                                           [0, lens[b])
+//   pos, lens, rng: as stream_step (rng: the draw at the absolute frame of every window row; the noise ring stays untouched)
+//   trim      false: the plain form (one Path over the window)
+template <class Backend>
+int live_step(const Plan& P, const LiveGeom& G, const char* blob, char* state, char* ws, const float* unit_new, const float* g,
+              const float* noise_new, float* out, int B, const int32_t* pos, const int32_t* lens, Backend& be,
+              const NoiseRng* rng = nullptr, bool trim = true) {
+  if (G.status != QVC_OK || G.W < 2) return G.status != QVC_OK ? G.status : QVC_ERR_BAD_ARG;
+  const LiveState S = carve_live_state(P, G, B);
+  const LiveScratch X = carve_live_scratch(P, G, B);
+  const qvc_config& c = P.cfg;
+  const size_t W = (size_t)G.W, h = (size_t)G.hop, keep = W - h;
+  const size_t spf = (size_t)samples_per_frame(P);
+  int st = QVC_OK;
+  auto ok = [&](int rc) { if (st == QVC_OK && rc != QVC_OK) st = rc; };
+  CopyDesc cd[kCopyBatchMax];
+  int ncd = 0;
+  auto flush = [&]() { if (ncd) ok(be.copy_batch(cd, ncd)); ncd = 0; };
+  auto add = [&](void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows) {
+    if ((dpitch | spitch | width | rows) >> 32) { ok(QVC_ERR_BAD_ARG); return; }
+    cd[ncd++] = CopyDesc{dst, src, (uint32_t)dpitch, (uint32_t)spitch, (uint32_t)width, (uint32_t)rows};
+  };
+  char* uring = state + S.unit;
+  char* nring = state + S.noise;
+  const size_t urows = (size_t)B * c.unit_channels, nrows = (size_t)B * c.inter_channels;
+  // ---- append the new frames behind the kept ones
+  add(uring + keep * 4, W * 4, unit_new, h * 4, h * 4, urows);
+  if (noise_new) add(nring + keep * 4, W * 4, noise_new, h * 4, h * 4, nrows);
+  flush();
+  // a segment over the window's last T rows: its buffer row T - hop is absolute frame pos[b]
+  auto make = [&](int T) {
+    Path<Backend> p{P, blob, ws, carve_workspace(P, B, T), B, T, be};
+    p.lens = lens; p.pos = pos; p.off = T - G.hop;
+    p.wn_wide = false;
+    return p;
+  };
+  const float* unit = reinterpret_cast<const float*>(uring);
+  const float* noise = noise_new ? reinterpret_cast<const float*>(nring) : nullptr;
+  float* wave = reinterpret_cast<float*>(ws + X.wave);
+  size_t wave_rows = W, first = (size_t)G.C();                     // rows of `wave`, and the first delivered one
+  if (!trim) {
+    Path<Backend> p = make(G.W);
+    if (!noise_new && rng) p.rng = *rng;     // (neither: enc_p refuses)
+    p.infer(unit, g, noise, wave);
+    ok(p.status);
+  } else {
+    const size_t zrow = (size_t)c.inter_channels * 4;              // one frame of z
+    const int Tf = G.W - G.He, Td = Tf - G.nf * G.Hf;
+    {   // E: the conditioning table (every segment's workspace keeps it at the same place) and enc_p
+      Path<Backend> p = make(G.W);
+      if (!noise_new && rng) p.rng = *rng;
+      p.cond_table(g);
+      p.enc_p(unit, noise, p.template wsp<float>(p.W.z));
+      ok(p.status);
+      add(ws + X.zf, (size_t)Tf * zrow, ws + p.W.z + (size_t)G.He * zrow, W * zrow, (size_t)Tf * zrow, (size_t)B);
+      flush();
+    }
+    {   // F: the flow, in place on its rows
+      Path<Backend> p = make(Tf);
+      p.flow(reinterpret_cast<float*>(ws + X.zf));
+      ok(p.status);
+      add(ws + X.zd, (size_t)Td * zrow, ws + X.zf + (size_t)(Tf - Td) * zrow, (size_t)Tf * zrow, (size_t)Td * zrow, (size_t)B);
+      flush();
+    }
+    {   // D: the decoder and the tail
+      Path<Backend> p = make(Td);
+      p.dec_trunk_wave(reinterpret_cast<const float*>(ws + X.zd), p.template wsp<float>(p.W.post), wave);
+      ok(p.status);
+    }
+    wave_rows = (size_t)Td; first = (size_t)G.Hdec;
+  }
+  // ---- deliver rows [first, first + hop) and slide the rings by one hop: kept parts out, then back in (they overlap
+  //      their destination)
+  add(out, h * spf * 4, ws + X.wave + first * spf * 4, wave_rows * spf * 4, h * spf * 4, (size_t)B);
+  add(ws + X.tmp[0], keep * 4, uring + h * 4, W * 4, keep * 4, urows);
+  if (noise_new) add(ws + X.tmp[1], keep * 4, nring + h * 4, W * 4, keep * 4, nrows);
+  flush();
+  add(uring, W * 4, ws + X.tmp[0], keep * 4, keep * 4, urows);
+  if (noise_new) add(nring, W * 4, ws + X.tmp[1], keep * 4, keep * 4, nrows);
+  flush();
+  return st;
+}
+
 }  // namespace qvc

@@ -312,6 +312,44 @@ class QvcEngine:
                                             torch.cuda.current_stream(self.device).cuda_stream)
         L.check(self.lib, st, "qvc_stream_reset_slot")
 
+    # ---- windowed streaming with a bounded look-ahead (qvc_live_step): every decoder, the lag is the caller's choice
+    def live_sizes(self, batch: int, hop: int, look_ahead: int):
+        """(state_bytes, workspace_bytes, context_frames) for `batch` streams fed `hop` frames per step whose output lags
+        the input by `look_ahead` frames (0 <= look_ahead <= context_frames); the window is context + look_ahead + hop."""
+        cfg = ctypes.byref(self.cfg)
+        vals = (int(self.lib.qvc_live_state_bytes(cfg, batch, hop, look_ahead)),
+                int(self.lib.qvc_live_workspace_bytes(cfg, batch, hop, look_ahead)),
+                int(self.lib.qvc_live_context_frames(cfg)))
+        for v in vals:
+            if v < 0:
+                L.check(self.lib, v, "qvc_live_*_bytes")
+        return vals
+
+    @_on_device
+    def live_step(self, state: torch.Tensor, ws: torch.Tensor, unit_new: torch.Tensor, g: torch.Tensor, noise_new: Optional[torch.Tensor],
+                  out: torch.Tensor, pos: torch.Tensor, lens: torch.Tensor, look_ahead: int, rng=None) -> None:
+        """One hop for every stream (all tensors fp32 / int32, contiguous, on this device; see include/qvc.h): `out`
+        receives frames [pos - look_ahead, ... + hop) of the conversion of each stream's prefix.  ``noise_new``: the draw
+        for the frames of ``unit_new``; ``rng``: as stream_step."""
+        B, _, hop = unit_new.shape
+        if rng is not None and not (torch.is_tensor(rng[1]) and rng[1].device == self.device):
+            raise ValueError("live_step needs the rng keys as an int64 tensor on the engine's device (slots are rewritten in place)")
+        noise_new, desc, _ = self._draw(noise_new, rng, B, (B, self.model_config["inter_channels"], hop))
+        fn, draw = (self.lib.qvc_live_step, noise_new.data_ptr()) if desc is None else (self.lib.qvc_live_step_rng, ctypes.byref(desc))
+        st = fn(ctypes.byref(self.cfg), self.blob.data_ptr(), state.data_ptr(), state.numel(), unit_new.data_ptr(), g.data_ptr(),
+                draw, out.data_ptr(), B, hop, int(look_ahead), pos.data_ptr(), lens.data_ptr(), ws.data_ptr(), ws.numel(),
+                torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib, st, "qvc_live_step")
+
+    @_on_device
+    def live_reset_slot(self, state: torch.Tensor, batch: int, hop: int, look_ahead: int, slot: int, length: int, pos: torch.Tensor,
+                        lens: torch.Tensor) -> None:
+        """qvc_live_reset_slot: zero slot `slot`'s ring rows, pos[slot] = 0, lens[slot] = length (on the current stream)."""
+        st = self.lib.qvc_live_reset_slot(ctypes.byref(self.cfg), state.data_ptr(), state.numel(), batch, hop, int(look_ahead), int(slot),
+                                          int(length), pos.data_ptr(), lens.data_ptr(),
+                                          torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib, st, "qvc_live_reset_slot")
+
     def _pack_spk(self) -> None:
         if self._spk_blob is None:
             if not self._spk_sd:

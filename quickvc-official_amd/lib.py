@@ -185,6 +185,24 @@ def declare(lib: ctypes.CDLL, prefix: str = "qvc") -> None:
         fn = getattr(lib, prefix + "_noise_fill")
         fn.restype = ctypes.c_int
         fn.argtypes = [ctypes.c_uint64, V, ctypes.c_float, I, I, I, I, V, V]
+    # the windowed step with a bounded look-ahead (qvc_live_*): only on a library that has it, as above
+    if hasattr(lib, prefix + "_live_step"):
+        fn = getattr(lib, prefix + "_live_context_frames")
+        fn.restype = I
+        fn.argtypes = [cfgp]
+        for name in ("_live_state_bytes", "_live_workspace_bytes"):
+            fn = getattr(lib, prefix + name)
+            fn.restype = L
+            fn.argtypes = [cfgp, I, I, I]
+        fn = getattr(lib, prefix + "_live_step")
+        fn.restype = ctypes.c_int
+        fn.argtypes = [cfgp, V, V, L, V, V, V, V, I, I, I, V, V, V, L, V]
+        fn = getattr(lib, prefix + "_live_step_rng")
+        fn.restype = ctypes.c_int
+        fn.argtypes = [cfgp, V, V, L, V, V, P(QvcNoiseRng), V, I, I, I, V, V, V, L, V]
+        fn = getattr(lib, prefix + "_live_reset_slot")
+        fn.restype = ctypes.c_int
+        fn.argtypes = [cfgp, V, L, I, I, I, I, I, V, V, V]
 
 
 _lib = None

@@ -110,7 +110,7 @@ class StreamConverter:
         self.engine = model.engine()
         dev = self.engine.device
         mc = model.model_config
-        n_state, n_ws, self.lag, self.noise_lag = self.engine.stream_sizes(self.streams, self.hop)
+        n_state, n_ws = self._sizes()
         self.spf = model.samples_per_frame
         self._state = aligned_empty(n_state, dev)
         self._ws = aligned_empty(n_ws, dev)
@@ -141,12 +141,22 @@ class StreamConverter:
         if seed is not None:
             self.set_seed(seed, noise_scale)
 
+    # the three calls that differ between the segment rings and LiveConverter's window
+    def _sizes(self):
+        n_state, n_ws, self.lag, self.noise_lag = self.engine.stream_sizes(self.streams, self.hop)
+        return n_state, n_ws
+
+    def _engine_step(self, noise, rng) -> None:
+        self.engine.stream_step(self._state, self._ws, self._unit, self._g, noise, self._out, self._pos, self._len, rng=rng)
+
+    def _engine_reset_slot(self, slot: int, length: int) -> None:
+        self.engine.stream_reset_slot(self._state, self.streams, self.hop, slot, length, self._pos, self._len)
+
     def _one_step(self, rng: bool = False):
         if rng:
-            self.engine.stream_step(self._state, self._ws, self._unit, self._g, None, self._out, self._pos, self._len,
-                                    rng=(self._rng[0], self._keys, self._rng[1]))
+            self._engine_step(None, (self._rng[0], self._keys, self._rng[1]))
         else:
-            self.engine.stream_step(self._state, self._ws, self._unit, self._g, self._noise, self._out, self._pos, self._len)
+            self._engine_step(self._noise, None)
         self._pos.add_(self.hop)                                 # inside the graph: the position advances with every replay
 
     def set_seed(self, seed: int, noise_scale: float = 1.0) -> None:
@@ -207,7 +217,7 @@ class StreamConverter:
         n = 2 ** 30 if length is None else int(length)
         self._after_caller(g)
         with torch.cuda.stream(self._stream):
-            self.engine.stream_reset_slot(self._state, self.streams, self.hop, slot, n, self._pos, self._len)
+            self._engine_reset_slot(slot, n)
             self._g[slot].copy_(g.reshape(-1), non_blocking=True)
             if key is not None:
                 k = int(key) & 0xFFFFFFFFFFFFFFFF
@@ -296,3 +306,33 @@ class StreamConverter:
                 out[:, 0, lo * spf:hi * spf] = chunk[:, (lo - f0) * spf:(hi - f0) * spf]
         torch.cuda.synchronize(dev)
         return out
+
+
+class LiveConverter(StreamConverter):
+    """Streaming with a bounded look-ahead, for EVERY decoder (qvc_live_step).  StreamConverter's surface -- ``start`` /
+    ``end_slot`` / ``finished`` / ``position`` / ``reset`` / ``end`` / ``set_seed`` / ``step`` / ``convert``, one graph
+    replay per step, the position a device counter the graph advances -- with the lag chosen by the caller:
+    ``lag == look_ahead`` frames, ``0 <= look_ahead <= context``.  Each stream keeps ONE ring of its last
+    ``window = context + look_ahead + hop`` unit frames; a step runs the whole path over that window and returns frames
+    [pos - look_ahead, pos - look_ahead + hop) of the OFFLINE conversion of the stream's prefix [0, min(length, pos + hop))
+    -- the result is defined exactly, whatever the look-ahead.  ``look_ahead == context`` is exact streaming: the
+    concatenated outputs equal the whole-utterance conversion, also for the single-band decoder and decoders with one
+    up-sampler, which StreamConverter refuses.  A frame costs ``window / hop`` of its offline cost.
+    The noise tensor of ``step(unit_new, noise_new)`` is for the frames of ``unit_new`` (``noise_lag == 0``)."""
+
+    def __init__(self, model, streams: int, hop_frames: int, look_ahead: int, use_graph: bool = True, seed: Optional[int] = None,
+                 noise_scale: float = 1.0):
+        self.look_ahead = int(look_ahead)
+        super().__init__(model, streams, hop_frames, use_graph=use_graph, seed=seed, noise_scale=noise_scale)
+
+    def _sizes(self):
+        n_state, n_ws, self.context = self.engine.live_sizes(self.streams, self.hop, self.look_ahead)
+        self.window = self.context + self.look_ahead + self.hop
+        self.lag, self.noise_lag = self.look_ahead, 0
+        return n_state, n_ws
+
+    def _engine_step(self, noise, rng) -> None:
+        self.engine.live_step(self._state, self._ws, self._unit, self._g, noise, self._out, self._pos, self._len, self.look_ahead, rng=rng)
+
+    def _engine_reset_slot(self, slot: int, length: int) -> None:
+        self.engine.live_reset_slot(self._state, self.streams, self.hop, self.look_ahead, slot, length, self._pos, self._len)

@@ -1,7 +1,11 @@
 """BASELINE.json configs[4]: streaming conversion, 64 concurrent streams, hipGraph replay per step.
 Times one step of (a) StreamConverter -- incremental, segment rings (qvc_stream_step) -- and (b) ChunkedConverter --
 exact windows over the whole path -- against (c) the offline whole-batch conversion of the same number of frames.
-usage: python tools/stream_bench.py [streams] [hop_frames ...]"""
+With --live, also (d) LiveConverter -- the windowed step with a bounded look-ahead (qvc_live_step) -- at each of the given
+look-aheads ("C" = the whole context): StreamConverter and the LiveConverters of a hop are timed in alternating rounds
+of one process and the median round is reported; every look-ahead runs in the trimmed form (the default) and in the
+plain form (every stage over the whole window).
+usage: python tools/stream_bench.py [--live L[,L...]] [streams] [hop_frames ...]"""
 import json
 import os
 import sys
@@ -11,7 +15,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import quickvc_official_amd as q  # noqa: E402
-from quickvc_official_amd.streaming import ChunkedConverter, StreamConverter  # noqa: E402
+from quickvc_official_amd.lib import debug_set  # noqa: E402
+from quickvc_official_amd.streaming import ChunkedConverter, LiveConverter, StreamConverter  # noqa: E402
 from quickvc_official_amd.synth import make_synthetic_inputs, make_synthetic_state_dict  # noqa: E402
 
 
@@ -33,9 +38,37 @@ def timed_replays(conv, n=20):
     return e0.elapsed_time(e1) / n
 
 
+def live_rows(model, streams, hop, looks, rounds=5):
+    """ms per step of StreamConverter and of LiveConverter at every look-ahead of `looks`, alternating, median of `rounds`."""
+    convs = {"stream": StreamConverter(model, streams, hop_frames=hop)}
+    context = model.engine().live_sizes(streams, hop, 0)[2]
+    for look in looks:
+        L = context if look == "C" else int(look)
+        convs[f"live_L{L}"] = LiveConverter(model, streams, hop, L)
+        debug_set("live_trim", 0)            # read when the step is issued, i.e. at capture: the plain form of the same step
+        convs[f"live_L{L}_plain"] = LiveConverter(model, streams, hop, L)
+        debug_set("live_trim", 1)
+    ms = {k: [] for k in convs}
+    for _ in range(rounds):
+        for k, conv in convs.items():
+            ms[k].append(timed_replays(conv))
+    out = {"context_frames": context}
+    for k, conv in convs.items():
+        mid = sorted(ms[k])[len(ms[k]) // 2]
+        out[k] = {"ms_per_step": mid, "ms_rounds": [round(v, 4) for v in ms[k]], "lag_frames": conv.lag,
+                  "window_frames": getattr(conv, "window", None), "us_per_frame": mid * 1e3 / (streams * hop)}
+    return out
+
+
 def main():
-    streams = int(sys.argv[1]) if len(sys.argv) > 1 else 64
-    hops = [int(x) for x in sys.argv[2:]] or [320, 16]
+    argv = sys.argv[1:]
+    looks = None
+    if "--live" in argv:
+        i = argv.index("--live")
+        looks = argv[i + 1].split(",")
+        del argv[i:i + 2]
+    streams = int(argv[0]) if argv else 64
+    hops = [int(x) for x in argv[1:]] or [320, 16]
     model = q.SynthesizerTrn(641, 32, **q.DEFAULT_MODEL_CONFIG)
     model.load_state_dict(make_synthetic_state_dict(model, 1234))
     model = model.cuda().eval()
@@ -77,6 +110,9 @@ def main():
             del ch
         except Exception as exc:                      # e.g. out of memory at a tiny hop x many streams
             row["windowed_error"] = str(exc)[:120]
+        if looks is not None:
+            torch.cuda.empty_cache()
+            row["live"] = live_rows(model, streams, hop, looks)
         res["hops"][str(hop)] = row
         torch.cuda.empty_cache()
     print(json.dumps(res))
