@@ -333,6 +333,44 @@ int qvc_live_step_rng(const qvc_config* cfg, const void* blob_dev, void* state, 
 int qvc_live_reset_slot(const qvc_config* cfg, void* state, int64_t state_bytes, int32_t batch, int32_t hop,
                         int32_t look_ahead, int32_t slot, int32_t length, int32_t* pos_dev, int32_t* len_dev, void* stream);
 
+/* ---- the tick form of the windowed step: per-slot frame counts per call ------------------------------------------
+ * qvc_live_step moves every slot by exactly `hop` frames.  A real audio front end does not deliver like that: a packet
+ * is late (nothing at this tick), a client catches up (less or more than usual), the last chunk is short.  In a tick
+ * slot b brings n = clamp(n_new_dev[b], 0, hop) frames -- the counts live in device memory, are clamped there and never
+ * read on the host; `hop` is the MOST a slot may bring and sizes the buffers and the window W = C + L + hop.
+ *   unit_new   (B, unit_channels, hop) fp32: columns [0, n) of row b are frames [pos[b], pos[b] + n); columns [n, hop)
+ *              -- the whole row of a slot with n = 0 -- are never read
+ *   noise_new  (B, inter_channels, hop) fp32, the same rule: the draw for the same frames.  The _rng twin draws at the
+ *              absolute frame of every window row with the slot's key instead
+ *   out        (B, hop * samples_per_frame) fp32: the first n * samples_per_frame samples of row b are frames
+ *              [pos[b] - L, pos[b] - L + n) of qvc_infer_batch_ragged on the stream's first min(len[b], pos[b] + n)
+ *              frames (zeros outside [0, len[b])); the rest of the row is written as 0.0
+ *   pos_dev    advanced on the device by the call: pos[b] += n (hence not const)
+ * A slot with n = 0 leaves no trace: ring rows and pos bit for bit as they were, a row of zeros in `out`, its tiles
+ * return at once.  One captured graph of the call replays for any tick pattern: only the contents of n_new_dev,
+ * pos_dev, len_dev, unit_new and noise_new change between replays.  With every n = hop the outputs are bit for bit
+ * qvc_live_step's.  With L = C the concatenated output of a stream is its whole-utterance conversion however the
+ * stream was cut into ticks; with L < C a frame is delivered with between L and L + n - 1 frames of look-ahead, so the
+ * output legitimately depends on the cut.
+ *   state      caller-owned device buffer of qvc_live_tick_state_bytes(), started per slot with
+ *              qvc_live_tick_reset_slot.  Between ticks ring row r of slot b holds frame pos[b] - W + r: the last W
+ *              frames RIGHT-aligned (qvc_live_step keeps W - hop frames left-aligned).  The two states are therefore
+ *              never exchanged: a tick state is never passed to qvc_live_step, a lockstep state never to these calls.
+ *   workspace  qvc_live_tick_workspace_bytes() (more than qvc_live_workspace_bytes())
+ * Errors as qvc_live_step; n_new_dev == NULL: QVC_ERR_BAD_ARG.  The segment rings (qvc_stream_step) keep lockstep. */
+int64_t qvc_live_tick_state_bytes(const qvc_config* cfg, int32_t batch, int32_t hop, int32_t look_ahead);
+int64_t qvc_live_tick_workspace_bytes(const qvc_config* cfg, int32_t batch, int32_t hop, int32_t look_ahead);
+int qvc_live_tick(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes,
+                  const float* unit_new, const float* g, const float* noise_new, float* out,
+                  int32_t batch, int32_t hop, int32_t look_ahead, const int32_t* n_new_dev, int32_t* pos_dev,
+                  const int32_t* len_dev, void* workspace, int64_t workspace_bytes, void* stream);
+int qvc_live_tick_rng(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes,
+                      const float* unit_new, const float* g, const qvc_noise_rng* rng, float* out,
+                      int32_t batch, int32_t hop, int32_t look_ahead, const int32_t* n_new_dev, int32_t* pos_dev,
+                      const int32_t* len_dev, void* workspace, int64_t workspace_bytes, void* stream);
+int qvc_live_tick_reset_slot(const qvc_config* cfg, void* state, int64_t state_bytes, int32_t batch, int32_t hop,
+                             int32_t look_ahead, int32_t slot, int32_t length, int32_t* pos_dev, int32_t* len_dev, void* stream);
+
 /* ---- optional fork/join resources: lets the three independent ResBlocks of an MRF stage
  * (models.py:378-384) run as parallel branches (two auxiliary non-blocking streams + events), so a
  * memory-bound k=3 launch overlaps a compute-bound k=11 launch.  Created/destroyed by the caller

@@ -95,6 +95,9 @@ struct HipBackend {
   int post_tail(const ConvDesc& d, const PostTailArgs& a, int batch, int dtype) { return launch_post_tail(d, a, batch, dtype, stream); }
   int zero(void* p, size_t bytes) { return hipMemsetAsync(p, 0, bytes, stream) == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH; }
   int copy_batch(const CopyDesc* d, int n) { return launch_copy_batch(d, n, stream); }
+  static constexpr bool kLiveTick = true;         // live_tick: the ring update and the delivery driven by device counts
+  int tick_rings(const TickRingsArgs& a) { return launch_tick_rings(a, stream); }
+  int tick_deliver(const TickDeliverArgs& a) { return launch_tick_deliver(a, stream); }
 };
 using Ctx = Path<HipBackend>;
 
@@ -318,6 +321,27 @@ int live_step_api(const qvc_config* cfg, const void* blob_dev, void* state, int6
   HipBackend be(stream);
   const int st = live_step(P, G, static_cast<const char*>(blob_dev), static_cast<char*>(state), static_cast<char*>(workspace), unit_new, g,
                            noise_new, out, batch, pos_dev, len_dev, be, rng ? &rv : nullptr, debug_get(DBG_LIVE_TRIM) != 0);
+  return st != QVC_OK ? st : be.finish();
+}
+
+// qvc_live_tick (noise_new) and qvc_live_tick_rng (rng): exactly one of the two
+int live_tick_api(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
+                  const float* g, const float* noise_new, const qvc_noise_rng* rng, float* out, int32_t batch, int32_t hop,
+                  int32_t look_ahead, const int32_t* n_new_dev, int32_t* pos_dev, const int32_t* len_dev, void* workspace,
+                  int64_t workspace_bytes, void* stream) {
+  NoiseRng rv;
+  const bool draw = rng ? (!noise_new && rng_view(rng, rv)) : noise_new != nullptr;
+  if (!blob_dev || !state || !unit_new || !g || !draw || !out || !n_new_dev || !pos_dev || !len_dev || !workspace || batch <= 0)
+    return QVC_ERR_BAD_ARG;
+  Plan P; LiveGeom G;
+  const int gs = live_plan(cfg, hop, look_ahead, P, G);
+  if (gs != QVC_OK) return gs;
+  if (state_bytes < carve_live_state(P, G, batch).bytes || workspace_bytes < carve_tick_scratch(P, G, batch).bytes) return QVC_ERR_SMALL_BUFFER;
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255) || (reinterpret_cast<uintptr_t>(blob_dev) & 255) || (reinterpret_cast<uintptr_t>(state) & 255))
+    return QVC_ERR_BAD_ARG;
+  HipBackend be(stream);
+  const int st = live_tick(P, G, static_cast<const char*>(blob_dev), static_cast<char*>(state), static_cast<char*>(workspace), unit_new, g,
+                           noise_new, out, batch, n_new_dev, pos_dev, len_dev, be, rng ? &rv : nullptr, debug_get(DBG_LIVE_TRIM) != 0);
   return st != QVC_OK ? st : be.finish();
 }
 
@@ -614,6 +638,41 @@ int qvc_live_reset_slot(const qvc_config* cfg, void* state, int64_t state_bytes,
   ok = ok && hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(pos_dev + slot), 0, 1, st) == hipSuccess;
   ok = ok && hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(len_dev + slot), length, 1, st) == hipSuccess;
   return ok ? QVC_OK : QVC_ERR_LAUNCH;
+}
+
+// The tick state is carved as the lockstep state (one unit ring and one noise ring of W frames per stream); what differs
+// is what the rings hold between calls (right-aligned, qvc_stream.h), so the two are never exchanged.
+int64_t qvc_live_tick_state_bytes(const qvc_config* cfg, int32_t batch, int32_t hop, int32_t look_ahead) {
+  return qvc_live_state_bytes(cfg, batch, hop, look_ahead);
+}
+
+int64_t qvc_live_tick_workspace_bytes(const qvc_config* cfg, int32_t batch, int32_t hop, int32_t look_ahead) {
+  Plan P; LiveGeom G;
+  const int st = batch > 0 ? live_plan(cfg, hop, look_ahead, P, G) : QVC_ERR_BAD_ARG;
+  return st != QVC_OK ? st : carve_tick_scratch(P, G, batch).bytes;
+}
+
+int qvc_live_tick(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
+                  const float* g, const float* noise_new, float* out, int32_t batch, int32_t hop, int32_t look_ahead,
+                  const int32_t* n_new_dev, int32_t* pos_dev, const int32_t* len_dev, void* workspace, int64_t workspace_bytes,
+                  void* stream) {
+  return live_tick_api(cfg, blob_dev, state, state_bytes, unit_new, g, noise_new, nullptr, out, batch, hop, look_ahead, n_new_dev, pos_dev,
+                       len_dev, workspace, workspace_bytes, stream);
+}
+
+int qvc_live_tick_rng(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
+                      const float* g, const qvc_noise_rng* rng, float* out, int32_t batch, int32_t hop, int32_t look_ahead,
+                      const int32_t* n_new_dev, int32_t* pos_dev, const int32_t* len_dev, void* workspace, int64_t workspace_bytes,
+                      void* stream) {
+  if (!rng) return QVC_ERR_BAD_ARG;
+  return live_tick_api(cfg, blob_dev, state, state_bytes, unit_new, g, nullptr, rng, out, batch, hop, look_ahead, n_new_dev, pos_dev,
+                       len_dev, workspace, workspace_bytes, stream);
+}
+
+int qvc_live_tick_reset_slot(const qvc_config* cfg, void* state, int64_t state_bytes, int32_t batch, int32_t hop, int32_t look_ahead,
+                             int32_t slot, int32_t length, int32_t* pos_dev, int32_t* len_dev, void* stream) {
+  // the slot's ring rows zeroed, pos = 0: row r holds frame r - W < 0, which every launch masks -- the invariant holds
+  return qvc_live_reset_slot(cfg, state, state_bytes, batch, hop, look_ahead, slot, length, pos_dev, len_dev, stream);
 }
 
 int qvc_infer_batch_timed(const qvc_config* cfg, const void* blob_dev, const float* unit, const float* g,

@@ -368,6 +368,65 @@ inline LiveScratch carve_live_scratch(const Plan& P, const LiveGeom& G, int B) {
   return X;
 }
 
+// The path over the window held in the rings -- what a step runs between appending the new frames and delivering:
+// the plain form or the three trimmed segments.  `unit` / `noise`: the rings (noise == nullptr: the generator form, rng).
+// pos / lens: buffer row T - hop of a segment over the window's last T rows is absolute frame pos[b].  The window's
+// waveform ends up in X.wave: wave_rows rows per stream, the hop delivered ones from row `first` on.
+template <class Backend>
+int live_window(const Plan& P, const LiveGeom& G, const LiveScratch& X, const char* blob, char* ws, const float* unit, const float* g,
+                const float* noise, int B, const int32_t* pos, const int32_t* lens, Backend& be, const NoiseRng* rng, bool trim,
+                size_t& wave_rows, size_t& first) {
+  const qvc_config& c = P.cfg;
+  const size_t W = (size_t)G.W;
+  int st = QVC_OK;
+  auto ok = [&](int rc) { if (st == QVC_OK && rc != QVC_OK) st = rc; };
+  // one strided copy per hand-off, each a launch of its own
+  auto hand = [&](void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows) {
+    if ((dpitch | spitch | width | rows) >> 32) { ok(QVC_ERR_BAD_ARG); return; }
+    const CopyDesc cd{dst, src, (uint32_t)dpitch, (uint32_t)spitch, (uint32_t)width, (uint32_t)rows};
+    ok(be.copy_batch(&cd, 1));
+  };
+  // a segment over the window's last T rows: its buffer row T - hop is absolute frame pos[b]
+  auto make = [&](int T) {
+    Path<Backend> p{P, blob, ws, carve_workspace(P, B, T), B, T, be};
+    p.lens = lens; p.pos = pos; p.off = T - G.hop;
+    p.wn_wide = false;
+    return p;
+  };
+  float* wave = reinterpret_cast<float*>(ws + X.wave);
+  wave_rows = W; first = (size_t)G.C();
+  if (!trim) {
+    Path<Backend> p = make(G.W);
+    if (!noise && rng) p.rng = *rng;         // (neither: enc_p refuses)
+    p.infer(unit, g, noise, wave);
+    ok(p.status);
+  } else {
+    const size_t zrow = (size_t)c.inter_channels * 4;              // one frame of z
+    const int Tf = G.W - G.He, Td = Tf - G.nf * G.Hf;
+    {   // E: the conditioning table (every segment's workspace keeps it at the same place) and enc_p
+      Path<Backend> p = make(G.W);
+      if (!noise && rng) p.rng = *rng;
+      p.cond_table(g);
+      p.enc_p(unit, noise, p.template wsp<float>(p.W.z));
+      ok(p.status);
+      hand(ws + X.zf, (size_t)Tf * zrow, ws + p.W.z + (size_t)G.He * zrow, W * zrow, (size_t)Tf * zrow, (size_t)B);
+    }
+    {   // F: the flow, in place on its rows
+      Path<Backend> p = make(Tf);
+      p.flow(reinterpret_cast<float*>(ws + X.zf));
+      ok(p.status);
+      hand(ws + X.zd, (size_t)Td * zrow, ws + X.zf + (size_t)(Tf - Td) * zrow, (size_t)Tf * zrow, (size_t)Td * zrow, (size_t)B);
+    }
+    {   // D: the decoder and the tail
+      Path<Backend> p = make(Td);
+      p.dec_trunk_wave(reinterpret_cast<const float*>(ws + X.zd), p.template wsp<float>(p.W.post), wave);
+      ok(p.status);
+    }
+    wave_rows = (size_t)Td; first = (size_t)G.Hdec;
+  }
+  return st;
+}
+
 // One step (G from live_plan).  Backend: as stream_step.
 //   unit_new  (B, unit_channels, hop) fp32: unit frames [pos, pos + hop) of every stream
 //   noise_new (B, inter, hop) fp32:         the N(0,1) draw of models.py:94 for the SAME frames (no noise lag)
@@ -401,48 +460,10 @@ int live_step(const Plan& P, const LiveGeom& G, const char* blob, char* state, c
   add(uring + keep * 4, W * 4, unit_new, h * 4, h * 4, urows);
   if (noise_new) add(nring + keep * 4, W * 4, noise_new, h * 4, h * 4, nrows);
   flush();
-  // a segment over the window's last T rows: its buffer row T - hop is absolute frame pos[b]
-  auto make = [&](int T) {
-    Path<Backend> p{P, blob, ws, carve_workspace(P, B, T), B, T, be};
-    p.lens = lens; p.pos = pos; p.off = T - G.hop;
-    p.wn_wide = false;
-    return p;
-  };
   const float* unit = reinterpret_cast<const float*>(uring);
   const float* noise = noise_new ? reinterpret_cast<const float*>(nring) : nullptr;
-  float* wave = reinterpret_cast<float*>(ws + X.wave);
-  size_t wave_rows = W, first = (size_t)G.C();                     // rows of `wave`, and the first delivered one
-  if (!trim) {
-    Path<Backend> p = make(G.W);
-    if (!noise_new && rng) p.rng = *rng;     // (neither: enc_p refuses)
-    p.infer(unit, g, noise, wave);
-    ok(p.status);
-  } else {
-    const size_t zrow = (size_t)c.inter_channels * 4;              // one frame of z
-    const int Tf = G.W - G.He, Td = Tf - G.nf * G.Hf;
-    {   // E: the conditioning table (every segment's workspace keeps it at the same place) and enc_p
-      Path<Backend> p = make(G.W);
-      if (!noise_new && rng) p.rng = *rng;
-      p.cond_table(g);
-      p.enc_p(unit, noise, p.template wsp<float>(p.W.z));
-      ok(p.status);
-      add(ws + X.zf, (size_t)Tf * zrow, ws + p.W.z + (size_t)G.He * zrow, W * zrow, (size_t)Tf * zrow, (size_t)B);
-      flush();
-    }
-    {   // F: the flow, in place on its rows
-      Path<Backend> p = make(Tf);
-      p.flow(reinterpret_cast<float*>(ws + X.zf));
-      ok(p.status);
-      add(ws + X.zd, (size_t)Td * zrow, ws + X.zf + (size_t)(Tf - Td) * zrow, (size_t)Tf * zrow, (size_t)Td * zrow, (size_t)B);
-      flush();
-    }
-    {   // D: the decoder and the tail
-      Path<Backend> p = make(Td);
-      p.dec_trunk_wave(reinterpret_cast<const float*>(ws + X.zd), p.template wsp<float>(p.W.post), wave);
-      ok(p.status);
-    }
-    wave_rows = (size_t)Td; first = (size_t)G.Hdec;
-  }
+  size_t wave_rows = 0, first = 0;                                 // rows of X.wave, and the first delivered one
+  ok(live_window(P, G, X, blob, ws, unit, g, noise, B, pos, lens, be, rng, trim, wave_rows, first));
   // ---- deliver rows [first, first + hop) and slide the rings by one hop: kept parts out, then back in (they overlap
   //      their destination)
   add(out, h * spf * 4, ws + X.wave + first * spf * 4, wave_rows * spf * 4, h * spf * 4, (size_t)B);
@@ -453,6 +474,90 @@ int live_step(const Plan& P, const LiveGeom& G, const char* blob, char* state, c
   if (noise_new) add(nring, W * 4, ws + X.tmp[1], keep * 4, keep * 4, nrows);
   flush();
   return st;
+}
+
+// ---------------------------------------------------------------- the tick form: per-slot frame counts per step (live_tick)
+// live_step moves every slot by exactly `hop` frames.  A tick lets slot b bring n = clamp(n_new[b], 0, hop) frames, the
+// counts in device memory: a late packet (n = 0), a client catching up, a last chunk shorter than hop.  The windowed
+// step makes that well defined -- a window whose last row is the newest frame is a sequence that ends there, however
+// many frames were appended to get there -- provided the ring is kept RIGHT-aligned:
+//
+//     INVARIANT  between ticks, ring row r of slot b holds frame pos[b] - W + r (the last W frames; live_step's ring
+//                keeps W - hop frames LEFT-aligned between steps).
+//     EXCLUSIVE  the two layouts differ, so a tick state is never passed to live_step, nor a lockstep state to live_tick.
+//
+// A tick is  tick_rings -> the window (live_window, unchanged) -> tick_deliver:
+//   tick_rings    shifts every ring row of a slot left by n and appends its n new frames, in place, and writes the
+//                 position the window's launches see, pos_eff[b] = pos[b] + n - hop: buffer row W - hop is then that
+//                 absolute frame, exactly as live_step's p.off = T - hop assumes, so the segments run unchanged.
+//                 pos_eff is negative early in a stream (first tick with n = 1: 1 - hop); ragged_lo / ragged_len and
+//                 the generator's frame counter only ever use pos - off, which is negative for a young stream in
+//                 live_step too.  A slot with n == 0 gets an empty sequence (len_eff = 0, pos_eff = W: hi = 0 in every
+//                 segment), so its tiles return at once and its ring rows and pos are not touched.
+//   tick_deliver  the delivered rows [first, first + hop) hold the n frames [pos - L, pos - L + n) at their END:
+//                 those go to the front of out[b], zeros behind them, and pos[b] += n.
+// With every n == hop: pos_eff = pos, len_eff = lens and the window's launches and bits are live_step's.
+// Delivered frame f was computed with the frames up to pos + n - 1 in the window: L + n - 1 - (f - (pos - L)) frames of
+// look-ahead, between L and L + n - 1.  With L = C every frame has its whole receptive field whatever n was, so the
+// output does not depend on how the stream was cut into ticks; with L < C it legitimately does.
+// Backend adds:  static constexpr bool kLiveTick = true  with  int tick_rings(const TickRingsArgs&);
+//                int tick_deliver(const TickDeliverArgs&);   -- one that does not say so gets QVC_ERR_BAD_CONFIG.
+template <class B, class = void> constexpr bool live_tick_backend = false;
+template <class B> constexpr bool live_tick_backend<B, std::void_t<decltype(B::kLiveTick)>> = B::kLiveTick;
+
+struct TickScratch {     // live_step's scratch, then the tick's effective positions and lengths
+  LiveScratch live;
+  int64_t pos_eff = 0, len_eff = 0;   // int32 [B] each
+  int64_t bytes = 0;
+};
+
+inline TickScratch carve_tick_scratch(const Plan& P, const LiveGeom& G, int B) {
+  TickScratch X;
+  X.live = carve_live_scratch(P, G, B);
+  int64_t off = X.live.bytes;
+  auto take = [&](int64_t n) { int64_t o = off; off = align_up(off + n, 256); return o; };
+  X.pos_eff = take((int64_t)B * 4);
+  X.len_eff = take((int64_t)B * 4);
+  X.bytes = off;
+  return X;
+}
+
+// One tick (G from live_plan; the state is carved as live_step's, carve_live_state, and holds the right-aligned rings).
+//   unit_new  (B, unit_channels, hop) fp32: columns [0, n) of row b are frames [pos[b], pos[b] + n); the rest is not read
+//   noise_new (B, inter, hop) fp32:         the same rule, the draw for the same frames
+//   out       (B, hop * samples_per_frame): n * spf samples of frames [pos - L, pos - L + n) of the offline conversion
+//                                           of the prefix [0, min(lens, pos + n)), zeros outside [0, lens[b]); then zeros
+//   n_new     (B,) int32 in the backend's memory, clamped to [0, hop] there; pos is advanced by n there too
+template <class Backend>
+int live_tick(const Plan& P, const LiveGeom& G, const char* blob, char* state, char* ws, const float* unit_new, const float* g,
+              const float* noise_new, float* out, int B, const int32_t* n_new, int32_t* pos, const int32_t* lens, Backend& be,
+              const NoiseRng* rng = nullptr, bool trim = true) {
+  if constexpr (live_tick_backend<Backend>) {
+    if (G.status != QVC_OK || G.W < 2) return G.status != QVC_OK ? G.status : QVC_ERR_BAD_ARG;
+    const LiveState S = carve_live_state(P, G, B);
+    const TickScratch X = carve_tick_scratch(P, G, B);
+    int st = QVC_OK;
+    auto ok = [&](int rc) { if (st == QVC_OK && rc != QVC_OK) st = rc; };
+    float* uring = reinterpret_cast<float*>(state + S.unit);
+    float* nring = noise_new ? reinterpret_cast<float*>(state + S.noise) : nullptr;
+    int32_t* pos_eff = reinterpret_cast<int32_t*>(ws + X.pos_eff);
+    int32_t* len_eff = reinterpret_cast<int32_t*>(ws + X.len_eff);
+    TickRingsArgs ra;
+    ra.unit_ring = uring; ra.unit_new = unit_new; ra.noise_ring = nring; ra.noise_new = noise_new;
+    ra.B = B; ra.UC = P.cfg.unit_channels; ra.NC = P.cfg.inter_channels; ra.W = G.W; ra.hop = G.hop;
+    ra.n_new = n_new; ra.pos = pos; ra.lens = lens; ra.pos_eff = pos_eff; ra.len_eff = len_eff;
+    ok(be.tick_rings(ra));
+    size_t wave_rows = 0, first = 0;
+    ok(live_window(P, G, X.live, blob, ws, uring, g, nring, B, pos_eff, len_eff, be, rng, trim, wave_rows, first));
+    TickDeliverArgs da;
+    da.wave = reinterpret_cast<const float*>(ws + X.live.wave); da.out = out;
+    da.B = B; da.rows = (int32_t)wave_rows; da.first = (int32_t)first; da.hop = G.hop; da.spf = samples_per_frame(P);
+    da.n_new = n_new; da.pos = pos;
+    ok(be.tick_deliver(da));
+    return st;
+  } else {
+    return QVC_ERR_BAD_CONFIG;
+  }
 }
 
 }  // namespace qvc

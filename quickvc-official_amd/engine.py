@@ -350,6 +350,45 @@ class QvcEngine:
                                           torch.cuda.current_stream(self.device).cuda_stream)
         L.check(self.lib, st, "qvc_live_reset_slot")
 
+    # ---- the tick form of the windowed step (qvc_live_tick): per-slot frame counts, the counts on the device
+    def live_tick_sizes(self, batch: int, hop: int, look_ahead: int):
+        """(state_bytes, workspace_bytes, context_frames) for `batch` streams that bring AT MOST `hop` frames per tick."""
+        cfg = ctypes.byref(self.cfg)
+        vals = (int(self.lib.qvc_live_tick_state_bytes(cfg, batch, hop, look_ahead)),
+                int(self.lib.qvc_live_tick_workspace_bytes(cfg, batch, hop, look_ahead)),
+                int(self.lib.qvc_live_context_frames(cfg)))
+        for v in vals:
+            if v < 0:
+                L.check(self.lib, v, "qvc_live_tick_*_bytes")
+        return vals
+
+    @_on_device
+    def live_tick(self, state: torch.Tensor, ws: torch.Tensor, unit_new: torch.Tensor, g: torch.Tensor, noise_new: Optional[torch.Tensor],
+                  out: torch.Tensor, n_new: torch.Tensor, pos: torch.Tensor, lens: torch.Tensor, look_ahead: int, rng=None) -> None:
+        """One tick (all tensors fp32 / int32, contiguous, on this device; see include/qvc.h): slot b brings
+        clamp(n_new[b], 0, hop) frames in the first columns of its row of ``unit_new`` (B, unit_channels, hop); `out`
+        receives that many frames from pos - look_ahead on, then zeros; ``pos`` is advanced on the device."""
+        B, _, hop = unit_new.shape
+        if rng is not None and not (torch.is_tensor(rng[1]) and rng[1].device == self.device):
+            raise ValueError("live_tick needs the rng keys as an int64 tensor on the engine's device (slots are rewritten in place)")
+        if n_new.dtype != torch.int32 or n_new.device != self.device or n_new.numel() != B:
+            raise ValueError("live_tick needs n_new as an int32 tensor of one count per slot on the engine's device")
+        noise_new, desc, _ = self._draw(noise_new, rng, B, (B, self.model_config["inter_channels"], hop))
+        fn, draw = (self.lib.qvc_live_tick, noise_new.data_ptr()) if desc is None else (self.lib.qvc_live_tick_rng, ctypes.byref(desc))
+        st = fn(ctypes.byref(self.cfg), self.blob.data_ptr(), state.data_ptr(), state.numel(), unit_new.data_ptr(), g.data_ptr(),
+                draw, out.data_ptr(), B, hop, int(look_ahead), n_new.data_ptr(), pos.data_ptr(), lens.data_ptr(), ws.data_ptr(),
+                ws.numel(), torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib, st, "qvc_live_tick")
+
+    @_on_device
+    def live_tick_reset_slot(self, state: torch.Tensor, batch: int, hop: int, look_ahead: int, slot: int, length: int,
+                             pos: torch.Tensor, lens: torch.Tensor) -> None:
+        """qvc_live_tick_reset_slot: zero slot `slot`'s ring rows, pos[slot] = 0, lens[slot] = length (on the current stream)."""
+        st = self.lib.qvc_live_tick_reset_slot(ctypes.byref(self.cfg), state.data_ptr(), state.numel(), batch, hop, int(look_ahead),
+                                               int(slot), int(length), pos.data_ptr(), lens.data_ptr(),
+                                               torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib, st, "qvc_live_tick_reset_slot")
+
     def _pack_spk(self) -> None:
         if self._spk_blob is None:
             if not self._spk_sd:

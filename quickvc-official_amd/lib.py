@@ -203,6 +203,22 @@ def declare(lib: ctypes.CDLL, prefix: str = "qvc") -> None:
         fn = getattr(lib, prefix + "_live_reset_slot")
         fn.restype = ctypes.c_int
         fn.argtypes = [cfgp, V, L, I, I, I, I, I, V, V, V]
+    # the tick form (qvc_live_tick*: per-slot frame counts per call): the product library only -- the emulation
+    # libraries are frozen before it
+    if hasattr(lib, prefix + "_live_tick"):
+        for name in ("_live_tick_state_bytes", "_live_tick_workspace_bytes"):
+            fn = getattr(lib, prefix + name)
+            fn.restype = L
+            fn.argtypes = [cfgp, I, I, I]
+        fn = getattr(lib, prefix + "_live_tick")
+        fn.restype = ctypes.c_int
+        fn.argtypes = [cfgp, V, V, L, V, V, V, V, I, I, I, V, V, V, V, L, V]
+        fn = getattr(lib, prefix + "_live_tick_rng")
+        fn.restype = ctypes.c_int
+        fn.argtypes = [cfgp, V, V, L, V, V, P(QvcNoiseRng), V, I, I, I, V, V, V, V, L, V]
+        fn = getattr(lib, prefix + "_live_tick_reset_slot")
+        fn.restype = ctypes.c_int
+        fn.argtypes = [cfgp, V, L, I, I, I, I, I, V, V, V]
 
 
 _lib = None

@@ -336,3 +336,72 @@ class LiveConverter(StreamConverter):
 
     def _engine_reset_slot(self, slot: int, length: int) -> None:
         self.engine.live_reset_slot(self._state, self.streams, self.hop, self.look_ahead, slot, length, self._pos, self._len)
+
+
+class TickConverter(LiveConverter):
+    """LiveConverter for streams that tick on their own (qvc_live_tick): per call, slot ``b`` brings ``n_new[b]`` frames,
+    ``0 <= n_new[b] <= hop_frames`` -- nothing when its packet is late, several packets when it catches up, a short last
+    chunk.  ``hop_frames`` is the MOST a slot may bring per tick; it sizes the buffers and the window
+    ``context + look_ahead + hop_frames``.  LiveConverter's lifecycle (``start`` / ``end_slot`` / ``finished`` /
+    ``position`` / ``reset`` / ``end`` / ``set_seed``) and one graph replay per tick; the counts travel in a device
+    tensor the captured call reads, the positions advance on the device by the clamped counts and the host mirror
+    follows them.  A slot that brings nothing leaves no trace: its ring, its position and the other slots' outputs are
+    what they would have been without it.
+
+    ``tick`` returns frames [pos - look_ahead, pos - look_ahead + n) of the offline conversion of the prefix
+    [0, min(length, pos + n)).  With ``look_ahead == context`` the concatenated output is the whole-utterance conversion
+    however the stream was cut into ticks; with less, a frame sees between ``look_ahead`` and ``look_ahead + n - 1``
+    frames of look-ahead, so the output depends on the cut.  ``step`` is the tick in which every slot brings
+    ``hop_frames`` frames: bit for bit LiveConverter's."""
+
+    def _sizes(self):
+        n_state, n_ws, self.context = self.engine.live_tick_sizes(self.streams, self.hop, self.look_ahead)
+        self.window = self.context + self.look_ahead + self.hop
+        self.lag, self.noise_lag = self.look_ahead, 0
+        # the counts of the tick in flight (the captured call holds this tensor's pointer); zeros: the warm-up and capture
+        # ticks of the constructor move nothing
+        self._n = torch.zeros(self.streams, dtype=torch.int32, device=self.engine.device)
+        return n_state, n_ws
+
+    def _one_step(self, rng: bool = False):
+        noise, draw = (None, (self._rng[0], self._keys, self._rng[1])) if rng else (self._noise, None)
+        self.engine.live_tick(self._state, self._ws, self._unit, self._g, noise, self._out, self._n, self._pos, self._len,
+                              self.look_ahead, rng=draw)                  # advances self._pos itself
+
+    def _engine_reset_slot(self, slot: int, length: int) -> None:
+        self.engine.live_tick_reset_slot(self._state, self.streams, self.hop, self.look_ahead, slot, length, self._pos, self._len)
+
+    @torch.no_grad()
+    def tick(self, unit_new: torch.Tensor, n_new, noise_new: Optional[torch.Tensor] = None):
+        """unit_new (S, 256, hop): columns [0, n_new[b]) of row b are frames [pos, pos + n_new[b]) of slot b, the rest is
+        never read; ``n_new``: a sequence of ints or a CPU int32 tensor of length S (clamped to [0, hop] on the device);
+        ``noise_new`` (S, inter, hop): the draw for the same frames, or None for the generator form.
+        -> (out, n): out (S, hop * samples_per_frame) with row b valid in [:n[b] * samples_per_frame] and zero behind it,
+        n the clamped counts."""
+        if noise_new is None and self._rng is None:
+            raise ValueError("tick() without noise_new needs a seed (TickConverter(seed=...) or set_seed)")
+        counts = torch.as_tensor(n_new, dtype=torch.int32, device="cpu").reshape(-1)
+        if counts.numel() != self.streams:
+            raise ValueError(f"{self.streams} slots need {self.streams} counts, got {counts.numel()}")
+        dev = self.engine.device
+        self._stream.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(self._stream):
+            self._unit.copy_(unit_new, non_blocking=True)
+            if noise_new is not None:
+                self._noise.copy_(noise_new, non_blocking=True)
+            self._n.copy_(counts)
+            graph = self._graph if noise_new is not None else self._rng_graph
+            if graph is not None:
+                graph.replay()
+            else:
+                self._one_step(rng=noise_new is None)
+            out = self._out.clone()
+        torch.cuda.current_stream(dev).wait_stream(self._stream)
+        n = [min(max(int(v), 0), self.hop) for v in counts.tolist()]
+        self._pos_host = [p + k for p, k in zip(self._pos_host, n)]
+        return out, n
+
+    @torch.no_grad()
+    def step(self, unit_new: torch.Tensor, noise_new: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The tick in which every slot brings ``hop`` frames (LiveConverter.step's contract and bits)."""
+        return self.tick(unit_new, [self.hop] * self.streams, noise_new)[0]

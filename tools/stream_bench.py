@@ -5,9 +5,15 @@ With --live, also (d) LiveConverter -- the windowed step with a bounded look-ahe
 look-aheads ("C" = the whole context): StreamConverter and the LiveConverters of a hop are timed in alternating rounds
 of one process and the median round is reported; every look-ahead runs in the trimmed form (the default) and in the
 plain form (every stage over the whole window).
-usage: python tools/stream_bench.py [--live L[,L...]] [streams] [hop_frames ...]"""
+With --ticks (and --live L[,L...] for the look-aheads), ONLY (e): per (hop, L) the lockstep LiveConverter.step against
+TickConverter -- the tick form, qvc_live_tick -- with every slot bringing hop frames, with a seeded half of the slots idle
+per tick, and with uniform random counts in [0, hop]; alternating rounds of one process, medians.  The counts of a tick are
+copied into the converter's count tensor on the device in front of every replay (inside the timed region, for all three
+tick rows).
+usage: python tools/stream_bench.py [--live L[,L...]] [--ticks] [streams] [hop_frames ...]"""
 import json
 import os
+import random
 import sys
 
 import torch
@@ -16,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import quickvc_official_amd as q  # noqa: E402
 from quickvc_official_amd.lib import debug_set  # noqa: E402
-from quickvc_official_amd.streaming import ChunkedConverter, LiveConverter, StreamConverter  # noqa: E402
+from quickvc_official_amd.streaming import ChunkedConverter, LiveConverter, StreamConverter, TickConverter  # noqa: E402
 from quickvc_official_amd.synth import make_synthetic_inputs, make_synthetic_state_dict  # noqa: E402
 
 
@@ -60,9 +66,65 @@ def live_rows(model, streams, hop, looks, rounds=5):
     return out
 
 
+def timed_ticks(conv, counts, n=20):
+    """ms per tick of a TickConverter: `counts` (12 + n, streams) int32 on the device, row i = n_new of replay i."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    with torch.cuda.stream(conv._stream):
+        conv._unit.normal_()
+        conv._noise.normal_()
+        conv._g.copy_(torch.nn.functional.normalize(torch.rand_like(conv._g), dim=1))
+        for i in range(12):
+            conv._n.copy_(counts[i])
+            conv._graph.replay()
+        e0.record(conv._stream)
+        for i in range(12, 12 + n):
+            conv._n.copy_(counts[i])
+            conv._graph.replay()
+        e1.record(conv._stream)
+    conv._stream.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+def tick_rows(model, streams, hop, looks, rounds=5, n=20):
+    """ms per step of LiveConverter (lockstep) and of TickConverter under three tick patterns, per look-ahead of `looks`,
+    alternating, median of `rounds`."""
+    context = model.engine().live_sizes(streams, hop, 0)[2]
+    rnd = random.Random(1300 + hop)
+    pats = {"full": [[hop] * streams for _ in range(12 + n)], "half_idle": [], "uniform": []}
+    for _ in range(12 + n):
+        idle = set(rnd.sample(range(streams), streams // 2))
+        pats["half_idle"].append([0 if s in idle else hop for s in range(streams)])
+        pats["uniform"].append([rnd.randint(0, hop) for _s in range(streams)])
+    dev_pats = {k: torch.tensor(v, dtype=torch.int32, device="cuda") for k, v in pats.items()}
+    out = {"context_frames": context,
+           "launches_beside_the_path": {"lockstep_step": "3 copy_batch (append; deliver + rings out; rings back)",
+                                        "tick": "2 (tick_rings, tick_deliver)"},
+           "mean_frames_per_slot_and_tick": {k: sum(map(sum, v[12:])) / (n * streams) for k, v in pats.items()}}
+    for look in looks:
+        L = context if look == "C" else int(look)
+        convs = {"lockstep": LiveConverter(model, streams, hop, L)}
+        for k in pats:
+            convs["tick_" + k] = TickConverter(model, streams, hop, L)
+        ms = {k: [] for k in convs}
+        for _ in range(rounds):
+            for k, conv in convs.items():
+                ms[k].append(timed_replays(conv, n) if k == "lockstep" else timed_ticks(conv, dev_pats[k[5:]], n))
+        row = {"window_frames": convs["lockstep"].window}
+        for k in convs:
+            mid = sorted(ms[k])[len(ms[k]) // 2]
+            row[k] = {"ms_per_step": mid, "ms_rounds": [round(v, 4) for v in ms[k]]}
+        out[f"L{L}"] = row
+        del convs
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     argv = sys.argv[1:]
     looks = None
+    ticks = "--ticks" in argv
+    if ticks:
+        argv.remove("--ticks")
     if "--live" in argv:
         i = argv.index("--live")
         looks = argv[i + 1].split(",")
@@ -73,6 +135,10 @@ def main():
     model.load_state_dict(make_synthetic_state_dict(model, 1234))
     model = model.cuda().eval()
     spf = model.samples_per_frame
+    if ticks:
+        res = {"streams": streams, "ticks": {str(hop): tick_rows(model, streams, hop, looks or ["0", "8", "C"]) for hop in hops}}
+        print(json.dumps(res))
+        return
     # offline cost per frame: the whole batch of `streams` x 320 frames in one call (graph replay)
     eng = model.engine()
     unit, g, noise = make_synthetic_inputs(streams, 320, 256, 192, 256, seed0=500)
