@@ -3,8 +3,7 @@
   libqvc_hip.so      -- the product: gfx950 kernels + C ABI + host packer (hipcc --offload-arch=gfx950)
   libqvc_io.so       -- the product's host-side batch file I/O (g++; include/qvc_io.h)
   oracle/_build/libqvc_emu.so -- TEST-ONLY host emulation of the launch sequence (g++/hipcc host code)
-  oracle/_build/libqvc_emu_live.so -- TEST-ONLY CPU twin of qvc_live_step on the same emulation (tests/emu_live.cpp)
-  oracle/_build/libqvc_emu_tick.so -- TEST-ONLY CPU twin of qvc_live_tick on the same emulation (tests/emu_tick.cpp)
+  oracle/_build/libqvc_emu_twin.so -- TEST-ONLY CPU twin of qvc_live_step / qvc_live_tick on the same emulation (tools/emu_twin.cpp)
 
 hipcc cross-compiles gfx950 without a GPU.  Translation units compile in parallel.
 """
@@ -24,8 +23,7 @@ LIB = os.path.join(PKG, "libqvc_hip.so")
 IO_LIB = os.path.join(PKG, "libqvc_io.so")
 EMU_DIR = os.path.join(ROOT, "oracle", "_build")
 EMU_LIB = os.path.join(EMU_DIR, "libqvc_emu.so")
-EMU_LIVE_LIB = os.path.join(EMU_DIR, "libqvc_emu_live.so")
-EMU_TICK_LIB = os.path.join(EMU_DIR, "libqvc_emu_tick.so")
+EMU_TWIN_LIB = os.path.join(EMU_DIR, "libqvc_emu_twin.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
@@ -110,27 +108,20 @@ def build_emu(force: bool = False) -> str:
     return EMU_LIB
 
 
-def build_emu_live(force: bool = False) -> str:
-    """The CPU twin of qvc_live_step (tests only): tests/emu_live.cpp includes the frozen oracle/qvc_emu.cpp and adds
-    qvc_emu_live_step on its backend -- a library of its own, the emulation library stays as it was."""
+def build_emu_twin(force: bool = False) -> str:
+    """The CPU twin of qvc_live_step and qvc_live_tick (tests only): tools/emu_twin.cpp includes the frozen
+    oracle/qvc_emu.cpp, derives a backend with host versions of the tick's ring update and delivery from its EmuBackend
+    and adds qvc_emu_live_step / qvc_emu_live_tick -- a library of its own, the emulation library stays as it was."""
     os.makedirs(EMU_DIR, exist_ok=True)
-    srcs = [os.path.join(ROOT, "tests", "emu_live.cpp"), os.path.join(CSRC, "qvc_pack.cpp")]
+    srcs = [os.path.join(ROOT, "tools", "emu_twin.cpp"), os.path.join(CSRC, "qvc_pack.cpp")]
     deps = srcs + [os.path.join(ROOT, "oracle", "qvc_emu.cpp")] + [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(ROOT, "include", "qvc.h")]
-    if force or not _newer(EMU_LIVE_LIB, deps):
-        _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", EMU_LIVE_LIB] + srcs)
-    return EMU_LIVE_LIB
+    if force or not _newer(EMU_TWIN_LIB, deps):
+        _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", EMU_TWIN_LIB] + srcs)
+    return EMU_TWIN_LIB
 
 
-def build_emu_tick(force: bool = False) -> str:
-    """The CPU twin of qvc_live_tick (tests only): tests/emu_tick.cpp includes the frozen oracle/qvc_emu.cpp, derives a
-    backend with host versions of the tick's ring update and delivery from its EmuBackend and adds qvc_emu_live_tick --
-    a library of its own, as build_emu_live's."""
-    os.makedirs(EMU_DIR, exist_ok=True)
-    srcs = [os.path.join(ROOT, "tests", "emu_tick.cpp"), os.path.join(CSRC, "qvc_pack.cpp")]
-    deps = srcs + [os.path.join(ROOT, "oracle", "qvc_emu.cpp")] + [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(ROOT, "include", "qvc.h")]
-    if force or not _newer(EMU_TICK_LIB, deps):
-        _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", EMU_TICK_LIB] + srcs)
-    return EMU_TICK_LIB
+# the twins were two libraries once; a caller of either earlier builder gets the one library, which exports both sets
+build_emu_live = build_emu_tick = build_emu_twin
 
 
 if __name__ == "__main__":
@@ -139,5 +130,4 @@ if __name__ == "__main__":
     print(build_hip(force, variant="sat"))
     print(build_io(force))
     print(build_emu(force))
-    print(build_emu_live(force))
-    print(build_emu_tick(force))
+    print(build_emu_twin(force))

@@ -285,64 +285,75 @@ int infer_fanout(const qvc_config* cfg, const void* blob_dev, const float* unit,
   });
 }
 
-// qvc_stream_step (noise_new) and qvc_stream_step_rng (rng): exactly one of the two
+// What every streaming step / tick entry point does (qvc_stream_step, qvc_live_step, qvc_live_tick and their _rng twins:
+// exactly one of noise_new / rng): the draw, the host checks of qvc_stream.h (pointers and batch, then `need` -- the plan
+// and the bytes the call needs --, then the two sizes), the alignments, and `step` on the caller's stream.
+template <class NeedFn, class StepFn>
+int run_stream(bool ptrs_ok, const float* noise_new, const qvc_noise_rng* rng, const void* blob_dev, void* state, int64_t state_bytes,
+               void* workspace, int64_t workspace_bytes, int32_t batch, void* stream, NeedFn need, StepFn step) {
+  NoiseRng rv;
+  const bool draw = rng ? (!noise_new && rng_view(rng, rv)) : noise_new != nullptr;
+  const int st = stream_checks(ptrs_ok && draw && blob_dev && state && workspace, batch, state_bytes, workspace_bytes, need);
+  if (st != QVC_OK) return st;
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255) || (reinterpret_cast<uintptr_t>(blob_dev) & 255) || (reinterpret_cast<uintptr_t>(state) & 255))
+    return QVC_ERR_BAD_ARG;
+  HipBackend be(stream);
+  const int rc = step(be, rng ? &rv : nullptr);
+  return rc != QVC_OK ? rc : be.finish();
+}
+
 int stream_step_api(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
                     const float* g, const float* noise_new, const qvc_noise_rng* rng, float* out, int32_t batch, int32_t hop,
                     const int32_t* pos_dev, const int32_t* len_dev, void* workspace, int64_t workspace_bytes, void* stream) {
-  NoiseRng rv;
-  const bool draw = rng ? (!noise_new && rng_view(rng, rv)) : noise_new != nullptr;
-  if (!blob_dev || !state || !unit_new || !g || !draw || !out || !pos_dev || !len_dev || !workspace || batch <= 0) return QVC_ERR_BAD_ARG;
   Plan P; StreamGeom G;
-  const int gs = stream_plan(cfg, hop, P, G);
-  if (gs != QVC_OK) return gs;
-  if (state_bytes < carve_stream_state(P, G, batch).bytes || workspace_bytes < carve_stream_scratch(P, G, batch).bytes) return QVC_ERR_SMALL_BUFFER;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255) || (reinterpret_cast<uintptr_t>(blob_dev) & 255) || (reinterpret_cast<uintptr_t>(state) & 255))
-    return QVC_ERR_BAD_ARG;
-  HipBackend be(stream);
-  const int st = stream_step(P, static_cast<const char*>(blob_dev), static_cast<char*>(state), static_cast<char*>(workspace), unit_new, g,
-                             noise_new, out, batch, hop, pos_dev, len_dev, be, rng ? &rv : nullptr);
-  return st != QVC_OK ? st : be.finish();
+  return run_stream(unit_new && g && out && pos_dev && len_dev, noise_new, rng, blob_dev, state, state_bytes, workspace, workspace_bytes, batch, stream,
+    [&](StreamBytes& b) {
+      const int gs = stream_plan(cfg, hop, P, G);
+      if (gs == QVC_OK) b = {carve_stream_state(P, G, batch).bytes, carve_stream_scratch(P, G, batch).bytes};
+      return gs;
+    },
+    [&](HipBackend& be, const NoiseRng* rv) {
+      return stream_step(P, static_cast<const char*>(blob_dev), static_cast<char*>(state), static_cast<char*>(workspace), unit_new, g,
+                         noise_new, out, batch, hop, pos_dev, len_dev, be, rv);
+    });
 }
 
-// qvc_live_step (noise_new) and qvc_live_step_rng (rng): exactly one of the two
-int live_step_api(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
+// qvc_live_step (tick == false: no n_new_dev, pos_dev is only read) and qvc_live_tick (pos_dev is the caller's int32_t*)
+int live_step_api(bool tick, const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
                   const float* g, const float* noise_new, const qvc_noise_rng* rng, float* out, int32_t batch, int32_t hop,
-                  int32_t look_ahead, const int32_t* pos_dev, const int32_t* len_dev, void* workspace, int64_t workspace_bytes,
-                  void* stream) {
-  NoiseRng rv;
-  const bool draw = rng ? (!noise_new && rng_view(rng, rv)) : noise_new != nullptr;
-  if (!blob_dev || !state || !unit_new || !g || !draw || !out || !pos_dev || !len_dev || !workspace || batch <= 0) return QVC_ERR_BAD_ARG;
-  Plan P; LiveGeom G;
-  const int gs = live_plan(cfg, hop, look_ahead, P, G);
-  if (gs != QVC_OK) return gs;
-  if (state_bytes < carve_live_state(P, G, batch).bytes || workspace_bytes < carve_live_scratch(P, G, batch).bytes) return QVC_ERR_SMALL_BUFFER;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255) || (reinterpret_cast<uintptr_t>(blob_dev) & 255) || (reinterpret_cast<uintptr_t>(state) & 255))
-    return QVC_ERR_BAD_ARG;
-  HipBackend be(stream);
-  const int st = live_step(P, G, static_cast<const char*>(blob_dev), static_cast<char*>(state), static_cast<char*>(workspace), unit_new, g,
-                           noise_new, out, batch, pos_dev, len_dev, be, rng ? &rv : nullptr, debug_get(DBG_LIVE_TRIM) != 0);
-  return st != QVC_OK ? st : be.finish();
-}
-
-// qvc_live_tick (noise_new) and qvc_live_tick_rng (rng): exactly one of the two
-int live_tick_api(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
-                  const float* g, const float* noise_new, const qvc_noise_rng* rng, float* out, int32_t batch, int32_t hop,
-                  int32_t look_ahead, const int32_t* n_new_dev, int32_t* pos_dev, const int32_t* len_dev, void* workspace,
+                  int32_t look_ahead, const int32_t* n_new_dev, const int32_t* pos_dev, const int32_t* len_dev, void* workspace,
                   int64_t workspace_bytes, void* stream) {
-  NoiseRng rv;
-  const bool draw = rng ? (!noise_new && rng_view(rng, rv)) : noise_new != nullptr;
-  if (!blob_dev || !state || !unit_new || !g || !draw || !out || !n_new_dev || !pos_dev || !len_dev || !workspace || batch <= 0)
-    return QVC_ERR_BAD_ARG;
   Plan P; LiveGeom G;
-  const int gs = live_plan(cfg, hop, look_ahead, P, G);
-  if (gs != QVC_OK) return gs;
-  if (state_bytes < carve_live_state(P, G, batch).bytes || workspace_bytes < carve_tick_scratch(P, G, batch).bytes) return QVC_ERR_SMALL_BUFFER;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255) || (reinterpret_cast<uintptr_t>(blob_dev) & 255) || (reinterpret_cast<uintptr_t>(state) & 255))
-    return QVC_ERR_BAD_ARG;
-  HipBackend be(stream);
-  const int st = live_tick(P, G, static_cast<const char*>(blob_dev), static_cast<char*>(state), static_cast<char*>(workspace), unit_new, g,
-                           noise_new, out, batch, n_new_dev, pos_dev, len_dev, be, rng ? &rv : nullptr, debug_get(DBG_LIVE_TRIM) != 0);
-  return st != QVC_OK ? st : be.finish();
+  return run_stream(unit_new && g && out && (n_new_dev || !tick) && pos_dev && len_dev, noise_new, rng, blob_dev, state, state_bytes, workspace,
+                    workspace_bytes, batch, stream,
+    [&](StreamBytes& b) {
+      const int gs = live_plan(cfg, hop, look_ahead, P, G);
+      if (gs == QVC_OK) b = {carve_live_state(P, G, batch).bytes, carve_live_scratch(P, G, batch, tick).bytes};
+      return gs;
+    },
+    [&](HipBackend& be, const NoiseRng* rv) {
+      const bool trim = debug_get(DBG_LIVE_TRIM) != 0;
+      const char* blob = static_cast<const char*>(blob_dev);
+      char* st = static_cast<char*>(state);
+      char* ws = static_cast<char*>(workspace);
+      return tick ? live_tick(P, G, blob, st, ws, unit_new, g, noise_new, out, batch, n_new_dev, const_cast<int32_t*>(pos_dev), len_dev, be, rv, trim)
+                  : live_step(P, G, blob, st, ws, unit_new, g, noise_new, out, batch, pos_dev, len_dev, be, rv, trim);
+    });
+}
+
+// What the three *_reset_slot entry points do: reset_slot of qvc_stream.h with memsets on the caller's stream, then
+// pos[slot] = 0 and lens[slot] = length there too (no host buffer involved).
+template <class RingsFn>
+int reset_slot_api(void* state, int64_t state_bytes, int32_t batch, int32_t slot, int32_t length, int32_t* pos_dev, int32_t* len_dev,
+                   void* stream, RingsFn rings) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  bool ok = true;
+  const int rc = reset_slot(state, state_bytes, batch, slot, length, pos_dev, len_dev, rings,
+                            [&](char* p, size_t n) { ok = ok && hipMemsetAsync(p, 0, n, st) == hipSuccess; });
+  if (rc != QVC_OK) return rc;
+  ok = ok && hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(pos_dev + slot), 0, 1, st) == hipSuccess;
+  ok = ok && hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(len_dev + slot), length, 1, st) == hipSuccess;
+  return ok ? QVC_OK : QVC_ERR_LAUNCH;
 }
 
 }  // namespace
@@ -562,27 +573,12 @@ int qvc_stream_step_rng(const qvc_config* cfg, const void* blob_dev, void* state
 
 int qvc_stream_reset_slot(const qvc_config* cfg, void* state, int64_t state_bytes, int32_t batch, int32_t hop, int32_t slot,
                           int32_t length, int32_t* pos_dev, int32_t* len_dev, void* stream) {
-  if (!state || !pos_dev || !len_dev || batch <= 0 || slot < 0 || slot >= batch || length < 0) return QVC_ERR_BAD_ARG;
-  Plan P; StreamGeom G;
-  const int gs = stream_plan(cfg, hop, P, G);
-  if (gs != QVC_OK) return gs;
-  const StreamState S = carve_stream_state(P, G, batch);
-  if (state_bytes < S.bytes) return QVC_ERR_SMALL_BUFFER;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(state);
-  const qvc_config& c = P.cfg;
-  bool ok = true;
-  // every ring is batch-major, so a stream's rows are one contiguous range per ring
-  auto zero = [&](int64_t ring, int64_t per_stream) {
-    ok = ok && hipMemsetAsync(base + ring + (int64_t)slot * per_stream, 0, (size_t)per_stream, st) == hipSuccess;
-  };
-  zero(S.unit, (int64_t)c.unit_channels * (2 * G.He + G.hop) * 4);
-  for (int k = 0; k < G.nf; ++k) zero(S.zf[k], (int64_t)(2 * G.Hf + G.hop) * c.inter_channels * 4);
-  zero(S.zd, (int64_t)(2 * G.Hd1 + G.hop) * c.inter_channels * 4);
-  for (int j = 0; j < 3; ++j) zero(S.s0[j], (int64_t)(2 * G.Hd2 + G.hop) * G.r0 * P.stages[0].ch * 2);
-  ok = ok && hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(pos_dev + slot), 0, 1, st) == hipSuccess;
-  ok = ok && hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(len_dev + slot), length, 1, st) == hipSuccess;   // no host buffer involved
-  return ok ? QVC_OK : QVC_ERR_LAUNCH;
+  return reset_slot_api(state, state_bytes, batch, slot, length, pos_dev, len_dev, stream, [&](Rings& R) {
+    Plan P; StreamGeom G;
+    const int gs = stream_plan(cfg, hop, P, G);
+    if (gs == QVC_OK) R = stream_rings(P, G, batch);
+    return gs;
+  });
 }
 
 int32_t qvc_live_context_frames(const qvc_config* cfg) {
@@ -606,7 +602,7 @@ int64_t qvc_live_workspace_bytes(const qvc_config* cfg, int32_t batch, int32_t h
 int qvc_live_step(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
                   const float* g, const float* noise_new, float* out, int32_t batch, int32_t hop, int32_t look_ahead,
                   const int32_t* pos_dev, const int32_t* len_dev, void* workspace, int64_t workspace_bytes, void* stream) {
-  return live_step_api(cfg, blob_dev, state, state_bytes, unit_new, g, noise_new, nullptr, out, batch, hop, look_ahead, pos_dev, len_dev,
+  return live_step_api(false, cfg, blob_dev, state, state_bytes, unit_new, g, noise_new, nullptr, out, batch, hop, look_ahead, nullptr, pos_dev, len_dev,
                        workspace, workspace_bytes, stream);
 }
 
@@ -614,30 +610,18 @@ int qvc_live_step_rng(const qvc_config* cfg, const void* blob_dev, void* state, 
                       const float* g, const qvc_noise_rng* rng, float* out, int32_t batch, int32_t hop, int32_t look_ahead,
                       const int32_t* pos_dev, const int32_t* len_dev, void* workspace, int64_t workspace_bytes, void* stream) {
   if (!rng) return QVC_ERR_BAD_ARG;
-  return live_step_api(cfg, blob_dev, state, state_bytes, unit_new, g, nullptr, rng, out, batch, hop, look_ahead, pos_dev, len_dev,
+  return live_step_api(false, cfg, blob_dev, state, state_bytes, unit_new, g, nullptr, rng, out, batch, hop, look_ahead, nullptr, pos_dev, len_dev,
                        workspace, workspace_bytes, stream);
 }
 
 int qvc_live_reset_slot(const qvc_config* cfg, void* state, int64_t state_bytes, int32_t batch, int32_t hop, int32_t look_ahead,
                         int32_t slot, int32_t length, int32_t* pos_dev, int32_t* len_dev, void* stream) {
-  if (!state || !pos_dev || !len_dev || batch <= 0 || slot < 0 || slot >= batch || length < 0) return QVC_ERR_BAD_ARG;
-  Plan P; LiveGeom G;
-  const int gs = live_plan(cfg, hop, look_ahead, P, G);
-  if (gs != QVC_OK) return gs;
-  const LiveState S = carve_live_state(P, G, batch);
-  if (state_bytes < S.bytes) return QVC_ERR_SMALL_BUFFER;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(state);
-  bool ok = true;
-  // both rings are batch-major, so a stream's rows are one contiguous range per ring
-  auto zero = [&](int64_t ring, int64_t per_stream) {
-    ok = ok && hipMemsetAsync(base + ring + (int64_t)slot * per_stream, 0, (size_t)per_stream, st) == hipSuccess;
-  };
-  zero(S.unit, (int64_t)P.cfg.unit_channels * G.W * 4);
-  zero(S.noise, (int64_t)P.cfg.inter_channels * G.W * 4);
-  ok = ok && hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(pos_dev + slot), 0, 1, st) == hipSuccess;
-  ok = ok && hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(len_dev + slot), length, 1, st) == hipSuccess;
-  return ok ? QVC_OK : QVC_ERR_LAUNCH;
+  return reset_slot_api(state, state_bytes, batch, slot, length, pos_dev, len_dev, stream, [&](Rings& R) {
+    Plan P; LiveGeom G;
+    const int gs = live_plan(cfg, hop, look_ahead, P, G);
+    if (gs == QVC_OK) R = live_rings(P, G, batch);
+    return gs;
+  });
 }
 
 // The tick state is carved as the lockstep state (one unit ring and one noise ring of W frames per stream); what differs
@@ -649,14 +633,14 @@ int64_t qvc_live_tick_state_bytes(const qvc_config* cfg, int32_t batch, int32_t 
 int64_t qvc_live_tick_workspace_bytes(const qvc_config* cfg, int32_t batch, int32_t hop, int32_t look_ahead) {
   Plan P; LiveGeom G;
   const int st = batch > 0 ? live_plan(cfg, hop, look_ahead, P, G) : QVC_ERR_BAD_ARG;
-  return st != QVC_OK ? st : carve_tick_scratch(P, G, batch).bytes;
+  return st != QVC_OK ? st : carve_live_scratch(P, G, batch, true).bytes;
 }
 
 int qvc_live_tick(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
                   const float* g, const float* noise_new, float* out, int32_t batch, int32_t hop, int32_t look_ahead,
                   const int32_t* n_new_dev, int32_t* pos_dev, const int32_t* len_dev, void* workspace, int64_t workspace_bytes,
                   void* stream) {
-  return live_tick_api(cfg, blob_dev, state, state_bytes, unit_new, g, noise_new, nullptr, out, batch, hop, look_ahead, n_new_dev, pos_dev,
+  return live_step_api(true, cfg, blob_dev, state, state_bytes, unit_new, g, noise_new, nullptr, out, batch, hop, look_ahead, n_new_dev, pos_dev,
                        len_dev, workspace, workspace_bytes, stream);
 }
 
@@ -665,7 +649,7 @@ int qvc_live_tick_rng(const qvc_config* cfg, const void* blob_dev, void* state, 
                       const int32_t* n_new_dev, int32_t* pos_dev, const int32_t* len_dev, void* workspace, int64_t workspace_bytes,
                       void* stream) {
   if (!rng) return QVC_ERR_BAD_ARG;
-  return live_tick_api(cfg, blob_dev, state, state_bytes, unit_new, g, nullptr, rng, out, batch, hop, look_ahead, n_new_dev, pos_dev,
+  return live_step_api(true, cfg, blob_dev, state, state_bytes, unit_new, g, nullptr, rng, out, batch, hop, look_ahead, n_new_dev, pos_dev,
                        len_dev, workspace, workspace_bytes, stream);
 }
 

@@ -25,6 +25,11 @@ inline int pair_dtype(const qvc_config& c) { return c.operand_dtype; }          
 inline int pair_weight_dtype(const qvc_config& c) { return c.operand_dtype == QVC_BF16X ? QVC_BF16 : c.operand_dtype; }
 
 inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+// Carves a buffer into 256-byte aligned pieces: take(n) is the offset of the next n bytes, `off` the size so far.
+struct Carver {
+  int64_t off = 0;
+  int64_t take(int64_t n) { int64_t o = off; off = align_up(off + n, 256); return o; }
+};
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 enum EpiKind : int32_t { EPI_STD = 0, EPI_GAU = 1, EPI_RESSKIP = 2,
@@ -409,28 +414,27 @@ struct Workspace {
 inline Workspace carve_workspace(const Plan& P, int B, int T) {
   Workspace W;
   const qvc_config& c = P.cfg;
-  int64_t off = 0;
-  auto take = [&](int64_t n) { int64_t o = off; off = align_up(off + n, 256); return o; };
+  Carver cv;
   const int64_t BT = (int64_t)B * T;
-  W.bb = take((int64_t)B * std::max(P.cond_rows, c.enc_layers * 2 * c.hidden_channels) * 4);   // enc_q's table too
-  W.xw = take(BT * c.hidden_channels * 4);
-  W.xw2 = take(BT * c.hidden_channels * 4);
-  W.oacc = take(BT * c.hidden_channels * 4);
-  W.acts = take(BT * c.hidden_channels * 2);
-  W.stats = take(BT * 2 * c.inter_channels * 4);
-  W.z = take(BT * c.inter_channels * 4);
-  W.c0 = take(BT * c.upsample_initial_channel * 2);
+  W.bb = cv.take((int64_t)B * std::max(P.cond_rows, c.enc_layers * 2 * c.hidden_channels) * 4);   // enc_q's table too
+  W.xw = cv.take(BT * c.hidden_channels * 4);
+  W.xw2 = cv.take(BT * c.hidden_channels * 4);
+  W.oacc = cv.take(BT * c.hidden_channels * 4);
+  W.acts = cv.take(BT * c.hidden_channels * 2);
+  W.stats = cv.take(BT * 2 * c.inter_channels * 4);
+  W.z = cv.take(BT * c.inter_channels * 4);
+  W.c0 = cv.take(BT * c.upsample_initial_channel * 2);
   int64_t t = T;
   for (size_t i = 0; i < P.stages.size(); ++i) {
     t *= P.stages[i].rate;
     int64_t n = (int64_t)B * t * P.stages[i].ch;
-    W.u.push_back(take(n * 2));
+    W.u.push_back(cv.take(n * 2));
     W.ra.emplace_back(); W.rb.emplace_back();
-    for (int j = 0; j < c.n_resblocks; ++j) { W.ra.back().push_back(take(n * 2)); W.rb.back().push_back(take(n * 2)); }
-    W.xt.push_back(take(n * 2 * c.n_resblocks));
+    for (int j = 0; j < c.n_resblocks; ++j) { W.ra.back().push_back(cv.take(n * 2)); W.rb.back().push_back(cv.take(n * 2)); }
+    W.xt.push_back(cv.take(n * 2 * c.n_resblocks));
   }
-  W.post = take((int64_t)B * (t + 1) * P.post_channels * 4);
-  W.bytes = off;
+  W.post = cv.take((int64_t)B * (t + 1) * P.post_channels * 4);
+  W.bytes = cv.off;
   return W;
 }
 
@@ -555,14 +559,13 @@ struct SpkWorkspace {
 
 inline SpkWorkspace carve_spk_workspace(const SpkPlan& S, int U, int F) {
   SpkWorkspace W;
-  int64_t off = 0;
-  auto take = [&](int64_t n) { int64_t o = off; off = align_up(off + n, 256); return o; };
+  Carver cv;
   const int64_t P = (int64_t)U * spk_partials(F), St = spk_steps(F);
-  W.xp0 = take((int64_t)U * F * 4 * S.H * 4);
-  W.xp = take(P * St * 4 * S.H * 4);
-  W.hseq = take(align_up(P, kSpkCols) * St * S.HP * 2);
-  W.hfin = take(P * S.H * 4);
-  W.bytes = off;
+  W.xp0 = cv.take((int64_t)U * F * 4 * S.H * 4);
+  W.xp = cv.take(P * St * 4 * S.H * 4);
+  W.hseq = cv.take(align_up(P, kSpkCols) * St * S.HP * 2);
+  W.hfin = cv.take(P * S.H * 4);
+  W.bytes = cv.off;
   return W;
 }
 
@@ -570,16 +573,15 @@ inline SpkWorkspace carve_spk_workspace(const SpkPlan& S, int U, int F) {
 // spk_steps(F) steps) followed by the device-built partial map.  A row of 0 frames has no partial.
 inline SpkWorkspace carve_spk_ragged_workspace(const SpkPlan& S, int U, int F) {
   SpkWorkspace W = carve_spk_workspace(S, U, F);
-  int64_t off = W.bytes;
-  auto take = [&](int64_t n) { int64_t o = off; off = align_up(off + n, 256); return o; };
+  Carver cv{W.bytes};
   const int64_t P = (int64_t)U * spk_partials(F);
-  W.flen = take((int64_t)U * 4);
-  W.poff = take(((int64_t)U + 1) * 4);
-  W.prow = take(P * 4);
-  W.pstart = take(P * 4);
-  W.psteps = take(P * 4);
-  W.phdr = take(2 * 4);
-  W.bytes = off;
+  W.flen = cv.take((int64_t)U * 4);
+  W.poff = cv.take(((int64_t)U + 1) * 4);
+  W.prow = cv.take(P * 4);
+  W.pstart = cv.take(P * 4);
+  W.psteps = cv.take(P * 4);
+  W.phdr = cv.take(2 * 4);
+  W.bytes = cv.off;
   return W;
 }
 

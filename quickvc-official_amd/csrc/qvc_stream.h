@@ -20,10 +20,123 @@
 // Inside a segment the fused kernels keep their layers' state on chip, so there are no per-layer caches to carry.
 // Sequence starts and ends inside a window are exact: every kernel masks its input rows by the absolute position
 // of the window (Ragged: pos / lens), i.e. each conv zero-pads at the sequence's own ends.
+//
+// Three drivers share this file: stream_step (the segment rings above), live_step (one window over the whole path,
+// below) and live_tick (live_step with per-slot frame counts).  What they share is stated once:
+//   Rings         the ring table of a driver (stream_rings / live_rings): where every ring lies in the state and its
+//                 geometry.  The state size, the slide buffers of the scratch, the slide loops and the per-slot reset
+//                 (reset_slot, slot_range) all read the table, so a ring is added or resized in ONE place.
+//   CopyQueue     the copy-descriptor queue in front of the backend's copy_batch (all data movement of a step).
+//   Segments      the factory of a step's Path segments.
+//   stream_checks the pure-host checks of an entry point (the C ABI's scaffold in qvc_api.hip and the CPU twin call it).
 #pragma once
 #include "qvc_path.h"
 
 namespace qvc {
+
+// One-sided reach of a ResBlock stack in its own frames: the worst over the blocks of sum over pairs of (k-1)/2 * (d + 1).
+inline int mrf_reach(const qvc_config& c) {
+  int worst = 0;
+  for (int j = 0; j < c.n_resblocks; ++j) {
+    int s = 0;
+    for (int q = 0; q < 3; ++q) s += (c.resblock_kernel_sizes[j] - 1) / 2 * (c.resblock_dilations[j][q] + 1);
+    worst = std::max(worst, s);
+  }
+  return worst;
+}
+
+// A ring of the state buffer, batch-major: `rows` rows per stream of keep + hopb bytes each.  A step appends hopb bytes
+// behind the first `keep` of every row and then slides the row left by hopb.
+struct Ring { int64_t off, rows, keep, hopb; };
+
+struct Rings {          // a driver's rings in the order they lie in the state; bytes = the state's size
+  Ring r[21] = {};      // stream_step: unit, zf[0..16), zd, s0[0..3)
+  int n = 0;
+  Carver cv;
+  void add(int B, int64_t rows, int64_t keep, int64_t hopb) { r[n++] = Ring{cv.take(B * rows * (keep + hopb)), rows, keep, hopb}; }
+  int64_t bytes() const { return cv.off; }
+  // the slide buffers of a step's scratch, one per ring: that ring's kept part
+  void carve_tmp(Carver& x, int B, int64_t* tmp) const { for (int i = 0; i < n; ++i) tmp[i] = x.take(B * r[i].rows * r[i].keep); }
+};
+
+// Every ring is batch-major, so a stream's rows are one contiguous range per ring.
+struct ByteRange { int64_t off, bytes; };
+inline ByteRange slot_range(const Ring& r, int slot) {
+  const int64_t per = r.rows * (r.keep + r.hopb);
+  return ByteRange{r.off + slot * per, per};
+}
+
+// Starts a new stream in `slot` on the host side: the checks of every *_reset_slot entry point in their order, then
+// zero(p, n) for the slot's range of every ring.  rings(R) -> status fills the driver's table.
+template <class RingsFn, class Zero>
+int reset_slot(void* state, int64_t state_bytes, int batch, int slot, int length, const void* pos, const void* lens, RingsFn rings, Zero zero) {
+  if (!state || !pos || !lens || batch <= 0 || slot < 0 || slot >= batch || length < 0) return QVC_ERR_BAD_ARG;
+  Rings R;
+  const int gs = rings(R);
+  if (gs != QVC_OK) return gs;
+  if (state_bytes < R.bytes()) return QVC_ERR_SMALL_BUFFER;
+  for (int i = 0; i < R.n; ++i) {
+    const ByteRange s = slot_range(R.r[i], slot);
+    zero(static_cast<char*>(state) + s.off, (size_t)s.bytes);
+  }
+  return QVC_OK;
+}
+
+// The pure-host checks of a step / tick entry point, in the order the status codes are pinned to: pointers and batch,
+// the plan (need(b) -> status fills the bytes the call needs), the two buffer sizes.
+struct StreamBytes { int64_t state = 0, ws = 0; };
+template <class NeedFn>
+int stream_checks(bool ptrs_ok, int batch, int64_t state_bytes, int64_t ws_bytes, NeedFn need) {
+  if (!ptrs_ok || batch <= 0) return QVC_ERR_BAD_ARG;
+  StreamBytes b;
+  const int gs = need(b);
+  if (gs != QVC_OK) return gs;
+  return state_bytes < b.state || ws_bytes < b.ws ? QVC_ERR_SMALL_BUFFER : QVC_OK;
+}
+
+// The queue in front of the backend's  int copy_batch(const CopyDesc* d, int n)  -- n independent strided copies / zero
+// fills in one launch (qvc_kernels.h).  The descriptors between two flushes run as ONE launch and must be independent
+// of each other; st is the first error.
+template <class Backend>
+struct CopyQueue {
+  Backend& be;
+  int st = QVC_OK;
+  CopyDesc cd[kCopyBatchMax];
+  int n = 0;
+  explicit CopyQueue(Backend& b) : be(b) {}
+  void ok(int rc) { if (st == QVC_OK && rc != QVC_OK) st = rc; }
+  void flush() { if (n) ok(be.copy_batch(cd, n)); n = 0; }
+  // queue a strided copy (src == nullptr: zero fill)
+  void add(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows) {
+    if (n == kCopyBatchMax) flush();
+    if ((dpitch | spitch | width | rows) >> 32) { ok(QVC_ERR_BAD_ARG); return; }
+    cd[n++] = CopyDesc{dst, src, (uint32_t)dpitch, (uint32_t)spitch, (uint32_t)width, (uint32_t)rows};
+  }
+  // a ring's new bytes of this step behind its kept ones; then, for the first `count` rings of R, the kept parts out to
+  // the slide buffers / back in, slid by one hop (out and back are two launches: a kept part and its destination overlap)
+  void append(char* state, const Ring& r, int B, const void* fresh) {
+    add(state + r.off + r.keep, (size_t)(r.keep + r.hopb), fresh, (size_t)r.hopb, (size_t)r.hopb, (size_t)(B * r.rows));
+  }
+  void slide_out(char* state, char* ws, const Rings& R, const int64_t* tmp, int count, int B) {
+    for (int i = 0; i < count; ++i) add(ws + tmp[i], (size_t)R.r[i].keep, state + R.r[i].off + R.r[i].hopb, (size_t)(R.r[i].keep + R.r[i].hopb), (size_t)R.r[i].keep, (size_t)(B * R.r[i].rows));
+  }
+  void slide_back(char* state, char* ws, const Rings& R, const int64_t* tmp, int count, int B) {
+    for (int i = 0; i < count; ++i) add(state + R.r[i].off, (size_t)(R.r[i].keep + R.r[i].hopb), ws + tmp[i], (size_t)R.r[i].keep, (size_t)R.r[i].keep, (size_t)(B * R.r[i].rows));
+  }
+};
+
+// A step's segments: make(T, lag_before) is a Path over the last T rows of a window whose newest `hop` rows are this
+// step's frames -- buffer row lag_before + T - hop is absolute frame pos[b].
+template <class Backend>
+struct Segments {
+  const Plan& P; const char* blob; char* ws; int B, hop; const int32_t* pos; const int32_t* lens; Backend& be;
+  Path<Backend> make(int T, int lag_before = 0) const {
+    Path<Backend> p{P, blob, ws, carve_workspace(P, B, T), B, T, be};
+    p.lens = lens; p.pos = pos; p.off = lag_before + (T - hop);
+    p.wn_wide = false;
+    return p;
+  }
+};
 
 struct StreamGeom {
   int32_t status = QVC_OK;
@@ -44,15 +157,7 @@ inline StreamGeom stream_geom(const Plan& P, int hop) {
   G.hop = hop; G.nf = c.n_flows; G.r0 = c.upsample_rates[0];
   G.He = c.enc_layers * K2;
   G.Hf = c.flow_layers * K2;
-  auto mrf = [&]() {   // one-sided reach of a ResBlock stack in its own frames: sum over pairs of (k-1)/2 * (d + 1)
-    int worst = 0;
-    for (int j = 0; j < c.n_resblocks; ++j) {
-      int s = 0;
-      for (int q = 0; q < 3; ++q) s += (c.resblock_kernel_sizes[j] - 1) / 2 * (c.resblock_dilations[j][q] + 1);
-      worst = std::max(worst, s);
-    }
-    return worst;
-  }();
+  const int mrf = mrf_reach(c);
   const int taps0 = P.stages[0].up.taps, taps1 = P.stages[1].up.taps;
   const int r1 = c.upsample_rates[1];
   G.Hd1 = 3 + taps0 + ceil_div(mrf, G.r0) + 1;                               // conv_pre (k 7), ups[0], MRF 0, margin
@@ -69,24 +174,36 @@ inline int stream_plan(const qvc_config* cfg, int hop, Plan& P, StreamGeom& G) {
   return G.status;
 }
 
-struct StreamState {     // byte offsets into the caller-owned state buffer
-  int64_t unit = 0;      // fp32 (B, unit_channels, 2*He + hop), the reference's (B, C, T) layout
-  int64_t zf[16] = {};   // fp32 [B][2*Hf + hop][C]: z in front of coupling layer k
-  int64_t zd = 0;        // fp32 [B][2*Hd1 + hop][C]: z after the flow
-  int64_t s0[3] = {};    // operand type [B][(2*Hd2 + hop) * r0][ch0]: stage-0 ResBlock outputs
+// The segment rings: each keeps 2*H frames and takes hop new ones per step.
+//   unit    fp32 (B, unit_channels, 2*He + hop), the reference's (B, C, T) layout
+//   zf[k]   fp32 [B][2*Hf + hop][C]: z in front of coupling layer k
+//   zd      fp32 [B][2*Hd1 + hop][C]: z after the flow
+//   s0[j]   operand type [B][(2*Hd2 + hop) * r0][ch0]: stage-0 ResBlock outputs
+inline Rings stream_rings(const Plan& P, const StreamGeom& G, int B) {
+  Rings R;
+  const int64_t h = G.hop, zrow = (int64_t)P.cfg.inter_channels * 4, srow = (int64_t)G.r0 * P.stages[0].ch * 2;
+  R.add(B, P.cfg.unit_channels, 2 * G.He * 4, h * 4);
+  for (int k = 0; k < G.nf; ++k) R.add(B, 1, 2 * G.Hf * zrow, h * zrow);
+  R.add(B, 1, 2 * G.Hd1 * zrow, h * zrow);
+  for (int j = 0; j < 3; ++j) R.add(B, 1, 2 * G.Hd2 * srow, h * srow);
+  return R;
+}
+
+struct StreamState {     // the ring table and, by name, the byte offsets of its rings in the caller-owned state buffer
+  Rings rings;
+  int64_t unit = 0, zf[16] = {}, zd = 0, s0[3] = {};
   int64_t bytes = 0;
 };
 
 inline StreamState carve_stream_state(const Plan& P, const StreamGeom& G, int B) {
   StreamState S;
-  const qvc_config& c = P.cfg;
-  int64_t off = 0;
-  auto take = [&](int64_t n) { int64_t o = off; off = align_up(off + n, 256); return o; };
-  S.unit = take((int64_t)B * c.unit_channels * (2 * G.He + G.hop) * 4);
-  for (int k = 0; k < G.nf; ++k) S.zf[k] = take((int64_t)B * (2 * G.Hf + G.hop) * c.inter_channels * 4);
-  S.zd = take((int64_t)B * (2 * G.Hd1 + G.hop) * c.inter_channels * 4);
-  for (int j = 0; j < 3; ++j) S.s0[j] = take((int64_t)B * (2 * G.Hd2 + G.hop) * G.r0 * P.stages[0].ch * 2);
-  S.bytes = off;
+  S.rings = stream_rings(P, G, B);
+  const Ring* r = S.rings.r;
+  S.unit = (r++)->off;
+  for (int k = 0; k < G.nf; ++k) S.zf[k] = (r++)->off;
+  S.zd = (r++)->off;
+  for (int j = 0; j < 3; ++j) S.s0[j] = (r++)->off;
+  S.bytes = S.rings.bytes();
   return S;
 }
 
@@ -96,7 +213,7 @@ struct StreamScratch {   // carved from the END of the step's workspace, after t
   int64_t zwork[2] = {};    // fp32 [B][2*Hf + hop][C]: the coupling layer updates z in place on a copy of its ring
                             // (two of them: layer k's result feeds the copy for layer k+1 in the same launch)
   int64_t wave = 0;         // fp32 (B, spf * (2*Hd2 + hop))
-  int64_t tmp[21] = {};     // slide buffers, one per ring (unit, zf[0..nf), zd, s0[0..3)): that ring's kept part
+  int64_t tmp[21] = {};     // slide buffers, one per ring of the table
   int64_t bytes = 0;
 };
 
@@ -106,23 +223,17 @@ inline StreamScratch carve_stream_scratch(const Plan& P, const StreamGeom& G, in
   StreamScratch X;
   const qvc_config& c = P.cfg;
   X.path_bytes = carve_workspace(P, B, G.max_window()).bytes;
-  int64_t off = X.path_bytes;
-  auto take = [&](int64_t n) { int64_t o = off; off = align_up(off + n, 256); return o; };
-  X.noise = take((int64_t)B * c.inter_channels * (2 * G.He + G.hop) * 4);
-  for (int k = 0; k < 2; ++k) X.zwork[k] = take((int64_t)B * (2 * G.Hf + G.hop) * c.inter_channels * 4);
-  X.wave = take((int64_t)B * samples_per_frame(P) * (2 * G.Hd2 + G.hop) * 4);
-  int r = 0;
-  X.tmp[r++] = take((int64_t)B * c.unit_channels * 2 * G.He * 4);
-  for (int k = 0; k < G.nf; ++k) X.tmp[r++] = take((int64_t)B * 2 * G.Hf * c.inter_channels * 4);
-  X.tmp[r++] = take((int64_t)B * 2 * G.Hd1 * c.inter_channels * 4);
-  for (int j = 0; j < 3; ++j) X.tmp[r++] = take((int64_t)B * 2 * G.Hd2 * G.r0 * P.stages[0].ch * 2);
-  X.bytes = off;
+  Carver cv{X.path_bytes};
+  X.noise = cv.take((int64_t)B * c.inter_channels * (2 * G.He + G.hop) * 4);
+  for (int k = 0; k < 2; ++k) X.zwork[k] = cv.take((int64_t)B * (2 * G.Hf + G.hop) * c.inter_channels * 4);
+  X.wave = cv.take((int64_t)B * samples_per_frame(P) * (2 * G.Hd2 + G.hop) * 4);
+  stream_rings(P, G, B).carve_tmp(cv, B, X.tmp);
+  X.bytes = cv.off;
   return X;
 }
 
-// One step.  Backend adds:  int copy_batch(const CopyDesc* d, int n)  -- n independent strided copies / zero fills in
-// one launch (qvc_kernels.h).  All data movement of a step goes through it: 10 launches where one memcpy per
-// hand-off / slide would be ~35.
+// One step.  All data movement of a step goes through the backend's copy_batch (CopyQueue): 5 + n_flows launches (9 at
+// the shipped config) where one memcpy per hand-off / slide would be ~35.
 //   unit_new  (B, unit_channels, hop) fp32: unit frames [pos, pos + hop) of every stream
 //   noise_new (B, inter, hop) fp32:         the N(0,1) draw of models.py:94 for frames [pos - He, pos - He + hop)
 //                                           (the frames enc_p finishes in this step)
@@ -140,32 +251,12 @@ int stream_step(const Plan& P, const char* blob, char* state, char* ws, const fl
   const StreamState S = carve_stream_state(P, G, B);
   const StreamScratch X = carve_stream_scratch(P, G, B);
   const qvc_config& c = P.cfg;
-  const int C = c.inter_channels, UC = c.unit_channels;
+  const int C = c.inter_channels;
   const int h = hop, He = G.He, Hf = G.Hf, Hd1 = G.Hd1, Hd2 = G.Hd2;
-  int st = QVC_OK;
-  auto ok = [&](int rc) { if (st == QVC_OK && rc != QVC_OK) st = rc; };
-  CopyDesc cd[kCopyBatchMax];
-  int ncd = 0;
-  auto flush = [&]() { if (ncd) ok(be.copy_batch(cd, ncd)); ncd = 0; };
-  // queue a strided copy (src == nullptr: zero fill); the descriptors between two flushes run as ONE launch and must be
-  // independent of each other
-  auto add = [&](void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows) {
-    if (ncd == kCopyBatchMax) flush();
-    if ((dpitch | spitch | width | rows) >> 32) { ok(QVC_ERR_BAD_ARG); return; }
-    cd[ncd++] = CopyDesc{dst, src, (uint32_t)dpitch, (uint32_t)spitch, (uint32_t)width, (uint32_t)rows};
-  };
-  // the rings slide at the END of the step, all of them in two launches (out to the scratch, back in: the kept part and
-  // its destination overlap).  A ring is read by exactly one segment per step, so nothing needs it slid earlier.
-  struct Slide { char* ring; size_t rows, keep, hopb; };
-  Slide slides[21];
-  int nslide = 0;
-  auto slide = [&](char* ring, size_t rows, size_t keep, size_t hopb) { slides[nslide++] = Slide{ring, rows, keep, hopb}; };
-  auto make = [&](int T, int lag_before) {
-    Path<Backend> p{P, blob, ws, carve_workspace(P, B, T), B, T, be};
-    p.lens = lens; p.pos = pos; p.off = lag_before + (T - h);      // buffer row `off` is absolute frame pos[b]
-    p.wn_wide = false;
-    return p;
-  };
+  CopyQueue<Backend> q(be);
+  const Segments<Backend> seg{P, blob, ws, B, h, pos, lens, be};
+  // the rings slide at the END of the step, all of them in two launches.  A ring is read by exactly one segment per
+  // step, so nothing needs it slid earlier.
   const size_t zrow = (size_t)C * 4;                               // one frame of z
   const int Tf = 2 * Hf + h;
   // hand the central hop frames of a segment's result (`src`, frame pitch zrow, `srcT` frames per stream) to coupling
@@ -173,89 +264,82 @@ int stream_step(const Plan& P, const char* blob, char* state, char* ws, const fl
   auto feed_flow = [&](int k, const char* src, int srcT) {
     char* ring = state + S.zf[k];
     char* zw = ws + X.zwork[k & 1];
-    add(ring + (size_t)2 * Hf * zrow, (size_t)Tf * zrow, src, (size_t)srcT * zrow, (size_t)h * zrow, (size_t)B);
-    add(zw, (size_t)Tf * zrow, ring, (size_t)Tf * zrow, (size_t)2 * Hf * zrow, (size_t)B);
-    add(zw + (size_t)2 * Hf * zrow, (size_t)Tf * zrow, src, (size_t)srcT * zrow, (size_t)h * zrow, (size_t)B);
-    flush();
+    q.add(ring + (size_t)2 * Hf * zrow, (size_t)Tf * zrow, src, (size_t)srcT * zrow, (size_t)h * zrow, (size_t)B);
+    q.add(zw, (size_t)Tf * zrow, ring, (size_t)Tf * zrow, (size_t)2 * Hf * zrow, (size_t)B);
+    q.add(zw + (size_t)2 * Hf * zrow, (size_t)Tf * zrow, src, (size_t)srcT * zrow, (size_t)h * zrow, (size_t)B);
+    q.flush();
+  };
+  // ... or, behind the last coupling layer (or enc_p without a flow), into the tail of the decoder's ring
+  auto feed_dec = [&](const char* src, int srcT) {
+    q.add(state + S.zd + (size_t)2 * Hd1 * zrow, (size_t)(2 * Hd1 + h) * zrow, src, (size_t)srcT * zrow, (size_t)h * zrow, (size_t)B);
+    q.flush();
   };
 
   {   // the conditioning table (cond rows x g) once per step: every segment's workspace keeps it at the same place
-    Path<Backend> p = make(Tf, 0);
+    Path<Backend> p = seg.make(Tf);
     p.cond_table(g);
-    ok(p.status);
+    q.ok(p.status);
   }
   // ---- E: enc_p over the unit ring
   {
     const int T = 2 * He + h;
     char* ring = state + S.unit;
     char* nz = ws + X.noise;                                       // zeros either side of the step's noise
-    add(ring + (size_t)2 * He * 4, (size_t)T * 4, unit_new, (size_t)h * 4, (size_t)h * 4, (size_t)B * UC);
+    q.append(state, S.rings.r[0], B, unit_new);
     if (noise_new) {
-      add(nz, (size_t)T * 4, nullptr, 0, (size_t)He * 4, (size_t)B * C);
-      add(nz + (size_t)He * 4, (size_t)T * 4, noise_new, (size_t)h * 4, (size_t)h * 4, (size_t)B * C);
-      add(nz + (size_t)(He + h) * 4, (size_t)T * 4, nullptr, 0, (size_t)He * 4, (size_t)B * C);
+      q.add(nz, (size_t)T * 4, nullptr, 0, (size_t)He * 4, (size_t)B * C);
+      q.add(nz + (size_t)He * 4, (size_t)T * 4, noise_new, (size_t)h * 4, (size_t)h * 4, (size_t)B * C);
+      q.add(nz + (size_t)(He + h) * 4, (size_t)T * 4, nullptr, 0, (size_t)He * 4, (size_t)B * C);
     }
-    flush();
-    Path<Backend> p = make(T, 0);
+    q.flush();
+    Path<Backend> p = seg.make(T);
     if (!noise_new && rng) p.rng = *rng;     // (neither: enc_p refuses)
     p.enc_p(reinterpret_cast<const float*>(ring), noise_new ? reinterpret_cast<const float*>(nz) : nullptr, p.template wsp<float>(p.W.z));
-    ok(p.status);
+    q.ok(p.status);
     if (G.nf > 0) feed_flow(0, ws + p.W.z + (size_t)He * zrow, T);
-    else {
-      add(state + S.zd + (size_t)2 * Hd1 * zrow, (size_t)(2 * Hd1 + h) * zrow, ws + p.W.z + (size_t)He * zrow, (size_t)T * zrow, (size_t)h * zrow, (size_t)B);
-      flush();
-    }
-    slide(ring, (size_t)B * UC, (size_t)2 * He * 4, (size_t)h * 4);
+    else feed_dec(ws + p.W.z + (size_t)He * zrow, T);
   }
   // ---- F_k: one coupling layer per segment, in place on a copy of its ring (its edge rows come out wrong and
   //      must not be written back: the ring has to keep the untouched values for the next step's context)
   for (int k = 0; k < G.nf; ++k) {
     char* zw = ws + X.zwork[k & 1];
-    Path<Backend> p = make(Tf, He + k * Hf);
+    Path<Backend> p = seg.make(Tf, He + k * Hf);
     p.flow_step(P.flow[(size_t)k], reinterpret_cast<float*>(zw), -1.f);
-    ok(p.status);
+    q.ok(p.status);
     if (k + 1 < G.nf) feed_flow(k + 1, zw + (size_t)Hf * zrow, Tf);
-    else {
-      add(state + S.zd + (size_t)2 * Hd1 * zrow, (size_t)(2 * Hd1 + h) * zrow, zw + (size_t)Hf * zrow, (size_t)Tf * zrow, (size_t)h * zrow, (size_t)B);
-      flush();
-    }
-    slide(state + S.zf[k], (size_t)B, (size_t)2 * Hf * zrow, (size_t)h * zrow);
+    else feed_dec(zw + (size_t)Hf * zrow, Tf);
   }
   // ---- D1: conv_pre + stage 0; its three ResBlock outputs feed the stage-0 rings
   const int ch0 = P.stages[0].ch, r0 = G.r0;
   {
     const int T = 2 * Hd1 + h;
-    char* ring = state + S.zd;
-    Path<Backend> p = make(T, He + G.nf * Hf);
-    p.dec_front(reinterpret_cast<const float*>(ring));
-    ok(p.status);
+    Path<Backend> p = seg.make(T, He + G.nf * Hf);
+    p.dec_front(reinterpret_cast<const float*>(state + S.zd));
+    q.ok(p.status);
     const size_t row = (size_t)ch0 * 2;
     for (int j = 0; j < 3; ++j) {
       const int jj = j < c.n_resblocks ? j : 0;
-      add(state + S.s0[j] + (size_t)2 * Hd2 * r0 * row, (size_t)(2 * Hd2 + h) * r0 * row,
-          ws + p.W.ra[0][(size_t)jj] + (size_t)Hd1 * r0 * row, (size_t)T * r0 * row, (size_t)h * r0 * row, (size_t)B);
+      q.add(state + S.s0[j] + (size_t)2 * Hd2 * r0 * row, (size_t)(2 * Hd2 + h) * r0 * row,
+            ws + p.W.ra[0][(size_t)jj] + (size_t)Hd1 * r0 * row, (size_t)T * r0 * row, (size_t)h * r0 * row, (size_t)B);
     }
-    flush();
-    slide(ring, (size_t)B, (size_t)2 * Hd1 * zrow, (size_t)h * zrow);
+    q.flush();
   }
   // ---- D2: remaining stages + conv_post + iSTFT / band synthesis; the central hop frames are the step's output
   {
     const int T = 2 * Hd2 + h;
     const int spf = samples_per_frame(P);
-    Path<Backend> p = make(T, He + G.nf * Hf + Hd1);
+    Path<Backend> p = seg.make(T, He + G.nf * Hf + Hd1);
     for (int j = 0; j < 3; ++j) p.s0_override[j] = state + S.s0[j];
     p.dec_back_wave(p.template wsp<float>(p.W.post), reinterpret_cast<float*>(ws + X.wave));
-    ok(p.status);
-    add(out, (size_t)h * spf * 4, ws + X.wave + (size_t)Hd2 * spf * 4, (size_t)T * spf * 4, (size_t)h * spf * 4, (size_t)B);
-    const size_t row = (size_t)ch0 * 2;
-    for (int j = 0; j < 3; ++j) slide(state + S.s0[j], (size_t)B, (size_t)2 * Hd2 * r0 * row, (size_t)h * r0 * row);
+    q.ok(p.status);
+    q.add(out, (size_t)h * spf * 4, ws + X.wave + (size_t)Hd2 * spf * 4, (size_t)T * spf * 4, (size_t)h * spf * 4, (size_t)B);
   }
   // ---- slide every ring by one hop: kept parts out (in the launch that also delivers the output), then back in
-  for (int r = 0; r < nslide; ++r) add(ws + X.tmp[r], slides[r].keep, slides[r].ring + slides[r].hopb, slides[r].keep + slides[r].hopb, slides[r].keep, slides[r].rows);
-  flush();
-  for (int r = 0; r < nslide; ++r) add(slides[r].ring, slides[r].keep + slides[r].hopb, ws + X.tmp[r], slides[r].keep, slides[r].keep, slides[r].rows);
-  flush();
-  return st;
+  q.slide_out(state, ws, S.rings, X.tmp, S.rings.n, B);
+  q.flush();
+  q.slide_back(state, ws, S.rings, X.tmp, S.rings.n, B);
+  q.flush();
+  return q.st;
 }
 
 // ---------------------------------------------------------------- windowed step with a bounded look-ahead (live_step)
@@ -294,6 +378,8 @@ struct LiveGeom {
   int32_t He = 0, Hf = 0, nf = 0, Hdec = 0;
   int32_t hop = 0, L = 0, W = 0;                   // set by live_plan
   int C() const { return He + nf * Hf + Hdec; }
+  // what live_step / live_tick refuse: a geometry live_plan refused, or one it never saw
+  int usable() const { return status != QVC_OK ? status : W < 2 ? QVC_ERR_BAD_ARG : QVC_OK; }
 };
 
 inline LiveGeom live_geom(const Plan& P) {
@@ -302,12 +388,7 @@ inline LiveGeom live_geom(const Plan& P) {
   const qvc_config& c = P.cfg;
   const int K2 = (c.wn_kernel_size - 1) / 2;
   G.He = c.enc_layers * K2; G.Hf = c.flow_layers * K2; G.nf = c.n_flows;
-  int mrf = 0;               // one-sided reach of a ResBlock stack in its own frames (as in stream_geom)
-  for (int j = 0; j < c.n_resblocks; ++j) {
-    int s = 0;
-    for (int q = 0; q < 3; ++q) s += (c.resblock_kernel_sizes[j] - 1) / 2 * (c.resblock_dilations[j][q] + 1);
-    mrf = std::max(mrf, s);
-  }
+  const int mrf = mrf_reach(c);
   int r = mrf + 8;
   for (int i = c.n_ups - 1; i >= 0; --i) {
     r = P.stages[(size_t)i].up.taps + ceil_div(r, c.upsample_rates[i]) + 1;
@@ -329,19 +410,28 @@ inline int live_plan(const qvc_config* cfg, int hop, int look_ahead, Plan& P, Li
   return QVC_OK;
 }
 
-struct LiveState {       // byte offsets into the caller-owned state buffer
-  int64_t unit = 0;      // fp32 (B, unit_channels, W), the reference's (B, C, T) layout
-  int64_t noise = 0;     // fp32 (B, inter_channels, W): the noise of the same frames (pointer form only)
+// The window's rings, live_step's and live_tick's alike (what they hold between calls differs: see live_tick):
+//   unit    fp32 (B, unit_channels, W), the reference's (B, C, T) layout
+//   noise   fp32 (B, inter_channels, W): the noise of the same frames (pointer form only)
+inline Rings live_rings(const Plan& P, const LiveGeom& G, int B) {
+  Rings R;
+  const int64_t keep = (int64_t)(G.W - G.hop) * 4, hopb = (int64_t)G.hop * 4;
+  R.add(B, P.cfg.unit_channels, keep, hopb);
+  R.add(B, P.cfg.inter_channels, keep, hopb);
+  return R;
+}
+
+struct LiveState {       // the ring table; unit / noise: the byte offsets of its two rings in the caller-owned state buffer
+  Rings rings;
+  int64_t unit = 0, noise = 0;
   int64_t bytes = 0;
 };
 
 inline LiveState carve_live_state(const Plan& P, const LiveGeom& G, int B) {
   LiveState S;
-  int64_t off = 0;
-  auto take = [&](int64_t n) { int64_t o = off; off = align_up(off + n, 256); return o; };
-  S.unit = take((int64_t)B * P.cfg.unit_channels * G.W * 4);
-  S.noise = take((int64_t)B * P.cfg.inter_channels * G.W * 4);
-  S.bytes = off;
+  S.rings = live_rings(P, G, B);
+  S.unit = S.rings.r[0].off; S.noise = S.rings.r[1].off;
+  S.bytes = S.rings.bytes();
   return S;
 }
 
@@ -351,20 +441,20 @@ struct LiveScratch {     // carved from the END of the step's workspace, after t
   int64_t zd = 0;           // fp32 [B][W - He - nf * Hf][C]: z handed to the decoder (trimmed form)
   int64_t wave = 0;         // fp32 (B, spf * W): the window's waveform (trimmed form: of the decoder's rows)
   int64_t tmp[2] = {};      // slide buffers: the kept W - hop frames of the unit / noise ring
+  int64_t pos_eff = 0, len_eff = 0;   // int32 [B] each: a tick's effective positions and lengths (tick = true only)
   int64_t bytes = 0;
 };
 
-inline LiveScratch carve_live_scratch(const Plan& P, const LiveGeom& G, int B) {
+inline LiveScratch carve_live_scratch(const Plan& P, const LiveGeom& G, int B, bool tick = false) {
   LiveScratch X;
   X.path_bytes = carve_workspace(P, B, G.W).bytes;
-  int64_t off = X.path_bytes;
-  auto take = [&](int64_t n) { int64_t o = off; off = align_up(off + n, 256); return o; };
-  X.zf = take((int64_t)B * (G.W - G.He) * P.cfg.inter_channels * 4);
-  X.zd = take((int64_t)B * (G.W - G.He - G.nf * G.Hf) * P.cfg.inter_channels * 4);
-  X.wave = take((int64_t)B * samples_per_frame(P) * G.W * 4);
-  X.tmp[0] = take((int64_t)B * P.cfg.unit_channels * (G.W - G.hop) * 4);
-  X.tmp[1] = take((int64_t)B * P.cfg.inter_channels * (G.W - G.hop) * 4);
-  X.bytes = off;
+  Carver cv{X.path_bytes};
+  X.zf = cv.take((int64_t)B * (G.W - G.He) * P.cfg.inter_channels * 4);
+  X.zd = cv.take((int64_t)B * (G.W - G.He - G.nf * G.Hf) * P.cfg.inter_channels * 4);
+  X.wave = cv.take((int64_t)B * samples_per_frame(P) * G.W * 4);
+  live_rings(P, G, B).carve_tmp(cv, B, X.tmp);
+  if (tick) { X.pos_eff = cv.take((int64_t)B * 4); X.len_eff = cv.take((int64_t)B * 4); }
+  X.bytes = cv.off;
   return X;
 }
 
@@ -378,56 +468,46 @@ int live_window(const Plan& P, const LiveGeom& G, const LiveScratch& X, const ch
                 size_t& wave_rows, size_t& first) {
   const qvc_config& c = P.cfg;
   const size_t W = (size_t)G.W;
-  int st = QVC_OK;
-  auto ok = [&](int rc) { if (st == QVC_OK && rc != QVC_OK) st = rc; };
-  // one strided copy per hand-off, each a launch of its own
-  auto hand = [&](void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows) {
-    if ((dpitch | spitch | width | rows) >> 32) { ok(QVC_ERR_BAD_ARG); return; }
-    const CopyDesc cd{dst, src, (uint32_t)dpitch, (uint32_t)spitch, (uint32_t)width, (uint32_t)rows};
-    ok(be.copy_batch(&cd, 1));
-  };
-  // a segment over the window's last T rows: its buffer row T - hop is absolute frame pos[b]
-  auto make = [&](int T) {
-    Path<Backend> p{P, blob, ws, carve_workspace(P, B, T), B, T, be};
-    p.lens = lens; p.pos = pos; p.off = T - G.hop;
-    p.wn_wide = false;
-    return p;
-  };
+  CopyQueue<Backend> q(be);                  // one strided copy per hand-off, each a launch of its own
+  const Segments<Backend> seg{P, blob, ws, B, G.hop, pos, lens, be};
   float* wave = reinterpret_cast<float*>(ws + X.wave);
   wave_rows = W; first = (size_t)G.C();
   if (!trim) {
-    Path<Backend> p = make(G.W);
+    Path<Backend> p = seg.make(G.W);
     if (!noise && rng) p.rng = *rng;         // (neither: enc_p refuses)
     p.infer(unit, g, noise, wave);
-    ok(p.status);
+    q.ok(p.status);
   } else {
     const size_t zrow = (size_t)c.inter_channels * 4;              // one frame of z
     const int Tf = G.W - G.He, Td = Tf - G.nf * G.Hf;
     {   // E: the conditioning table (every segment's workspace keeps it at the same place) and enc_p
-      Path<Backend> p = make(G.W);
+      Path<Backend> p = seg.make(G.W);
       if (!noise && rng) p.rng = *rng;
       p.cond_table(g);
       p.enc_p(unit, noise, p.template wsp<float>(p.W.z));
-      ok(p.status);
-      hand(ws + X.zf, (size_t)Tf * zrow, ws + p.W.z + (size_t)G.He * zrow, W * zrow, (size_t)Tf * zrow, (size_t)B);
+      q.ok(p.status);
+      q.add(ws + X.zf, (size_t)Tf * zrow, ws + p.W.z + (size_t)G.He * zrow, W * zrow, (size_t)Tf * zrow, (size_t)B);
+      q.flush();
     }
     {   // F: the flow, in place on its rows
-      Path<Backend> p = make(Tf);
+      Path<Backend> p = seg.make(Tf);
       p.flow(reinterpret_cast<float*>(ws + X.zf));
-      ok(p.status);
-      hand(ws + X.zd, (size_t)Td * zrow, ws + X.zf + (size_t)(Tf - Td) * zrow, (size_t)Tf * zrow, (size_t)Td * zrow, (size_t)B);
+      q.ok(p.status);
+      q.add(ws + X.zd, (size_t)Td * zrow, ws + X.zf + (size_t)(Tf - Td) * zrow, (size_t)Tf * zrow, (size_t)Td * zrow, (size_t)B);
+      q.flush();
     }
     {   // D: the decoder and the tail
-      Path<Backend> p = make(Td);
+      Path<Backend> p = seg.make(Td);
       p.dec_trunk_wave(reinterpret_cast<const float*>(ws + X.zd), p.template wsp<float>(p.W.post), wave);
-      ok(p.status);
+      q.ok(p.status);
     }
     wave_rows = (size_t)Td; first = (size_t)G.Hdec;
   }
-  return st;
+  return q.st;
 }
 
-// One step (G from live_plan).  Backend: as stream_step.
+// One step (G from live_plan).  Backend: as stream_step.  The rings are kept LEFT-aligned between steps: the W - hop
+// kept frames in front, slid by copy_batch.
 //   unit_new  (B, unit_channels, hop) fp32: unit frames [pos, pos + hop) of every stream
 //   noise_new (B, inter, hop) fp32:         the N(0,1) draw of models.py:94 for the SAME frames (no noise lag)
 //   out       (B, hop * samples_per_frame): waveform of frames [pos - L, pos - L + hop); zeros where that is outside
@@ -438,42 +518,27 @@ template <class Backend>
 int live_step(const Plan& P, const LiveGeom& G, const char* blob, char* state, char* ws, const float* unit_new, const float* g,
               const float* noise_new, float* out, int B, const int32_t* pos, const int32_t* lens, Backend& be,
               const NoiseRng* rng = nullptr, bool trim = true) {
-  if (G.status != QVC_OK || G.W < 2) return G.status != QVC_OK ? G.status : QVC_ERR_BAD_ARG;
+  if (G.usable() != QVC_OK) return G.usable();
   const LiveState S = carve_live_state(P, G, B);
   const LiveScratch X = carve_live_scratch(P, G, B);
-  const qvc_config& c = P.cfg;
-  const size_t W = (size_t)G.W, h = (size_t)G.hop, keep = W - h;
-  const size_t spf = (size_t)samples_per_frame(P);
-  int st = QVC_OK;
-  auto ok = [&](int rc) { if (st == QVC_OK && rc != QVC_OK) st = rc; };
-  CopyDesc cd[kCopyBatchMax];
-  int ncd = 0;
-  auto flush = [&]() { if (ncd) ok(be.copy_batch(cd, ncd)); ncd = 0; };
-  auto add = [&](void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows) {
-    if ((dpitch | spitch | width | rows) >> 32) { ok(QVC_ERR_BAD_ARG); return; }
-    cd[ncd++] = CopyDesc{dst, src, (uint32_t)dpitch, (uint32_t)spitch, (uint32_t)width, (uint32_t)rows};
-  };
-  char* uring = state + S.unit;
-  char* nring = state + S.noise;
-  const size_t urows = (size_t)B * c.unit_channels, nrows = (size_t)B * c.inter_channels;
+  const size_t h = (size_t)G.hop, spf = (size_t)samples_per_frame(P);
+  const int nrings = noise_new ? 2 : 1;                            // the generator form leaves the noise ring alone
+  CopyQueue<Backend> q(be);
   // ---- append the new frames behind the kept ones
-  add(uring + keep * 4, W * 4, unit_new, h * 4, h * 4, urows);
-  if (noise_new) add(nring + keep * 4, W * 4, noise_new, h * 4, h * 4, nrows);
-  flush();
-  const float* unit = reinterpret_cast<const float*>(uring);
-  const float* noise = noise_new ? reinterpret_cast<const float*>(nring) : nullptr;
+  q.append(state, S.rings.r[0], B, unit_new);
+  if (noise_new) q.append(state, S.rings.r[1], B, noise_new);
+  q.flush();
+  const float* unit = reinterpret_cast<const float*>(state + S.unit);
+  const float* noise = noise_new ? reinterpret_cast<const float*>(state + S.noise) : nullptr;
   size_t wave_rows = 0, first = 0;                                 // rows of X.wave, and the first delivered one
-  ok(live_window(P, G, X, blob, ws, unit, g, noise, B, pos, lens, be, rng, trim, wave_rows, first));
-  // ---- deliver rows [first, first + hop) and slide the rings by one hop: kept parts out, then back in (they overlap
-  //      their destination)
-  add(out, h * spf * 4, ws + X.wave + first * spf * 4, wave_rows * spf * 4, h * spf * 4, (size_t)B);
-  add(ws + X.tmp[0], keep * 4, uring + h * 4, W * 4, keep * 4, urows);
-  if (noise_new) add(ws + X.tmp[1], keep * 4, nring + h * 4, W * 4, keep * 4, nrows);
-  flush();
-  add(uring, W * 4, ws + X.tmp[0], keep * 4, keep * 4, urows);
-  if (noise_new) add(nring, W * 4, ws + X.tmp[1], keep * 4, keep * 4, nrows);
-  flush();
-  return st;
+  q.ok(live_window(P, G, X, blob, ws, unit, g, noise, B, pos, lens, be, rng, trim, wave_rows, first));
+  // ---- deliver rows [first, first + hop) and slide the rings by one hop: kept parts out, then back in
+  q.add(out, h * spf * 4, ws + X.wave + first * spf * 4, wave_rows * spf * 4, h * spf * 4, (size_t)B);
+  q.slide_out(state, ws, S.rings, X.tmp, nrings, B);
+  q.flush();
+  q.slide_back(state, ws, S.rings, X.tmp, nrings, B);
+  q.flush();
+  return q.st;
 }
 
 // ---------------------------------------------------------------- the tick form: per-slot frame counts per step (live_tick)
@@ -489,7 +554,7 @@ int live_step(const Plan& P, const LiveGeom& G, const char* blob, char* state, c
 // A tick is  tick_rings -> the window (live_window, unchanged) -> tick_deliver:
 //   tick_rings    shifts every ring row of a slot left by n and appends its n new frames, in place, and writes the
 //                 position the window's launches see, pos_eff[b] = pos[b] + n - hop: buffer row W - hop is then that
-//                 absolute frame, exactly as live_step's p.off = T - hop assumes, so the segments run unchanged.
+//                 absolute frame, exactly as live_step's segments assume, so they run unchanged.
 //                 pos_eff is negative early in a stream (first tick with n = 1: 1 - hop); ragged_lo / ragged_len and
 //                 the generator's frame counter only ever use pos - off, which is negative for a young stream in
 //                 live_step too.  A slot with n == 0 gets an empty sequence (len_eff = 0, pos_eff = W: hi = 0 in every
@@ -505,24 +570,8 @@ int live_step(const Plan& P, const LiveGeom& G, const char* blob, char* state, c
 template <class B, class = void> constexpr bool live_tick_backend = false;
 template <class B> constexpr bool live_tick_backend<B, std::void_t<decltype(B::kLiveTick)>> = B::kLiveTick;
 
-struct TickScratch {     // live_step's scratch, then the tick's effective positions and lengths
-  LiveScratch live;
-  int64_t pos_eff = 0, len_eff = 0;   // int32 [B] each
-  int64_t bytes = 0;
-};
-
-inline TickScratch carve_tick_scratch(const Plan& P, const LiveGeom& G, int B) {
-  TickScratch X;
-  X.live = carve_live_scratch(P, G, B);
-  int64_t off = X.live.bytes;
-  auto take = [&](int64_t n) { int64_t o = off; off = align_up(off + n, 256); return o; };
-  X.pos_eff = take((int64_t)B * 4);
-  X.len_eff = take((int64_t)B * 4);
-  X.bytes = off;
-  return X;
-}
-
-// One tick (G from live_plan; the state is carved as live_step's, carve_live_state, and holds the right-aligned rings).
+// One tick (G from live_plan; state and scratch are carved as live_step's, the scratch with tick = true; the state holds
+// the right-aligned rings).
 //   unit_new  (B, unit_channels, hop) fp32: columns [0, n) of row b are frames [pos[b], pos[b] + n); the rest is not read
 //   noise_new (B, inter, hop) fp32:         the same rule, the draw for the same frames
 //   out       (B, hop * samples_per_frame): n * spf samples of frames [pos - L, pos - L + n) of the offline conversion
@@ -533,9 +582,9 @@ int live_tick(const Plan& P, const LiveGeom& G, const char* blob, char* state, c
               const float* noise_new, float* out, int B, const int32_t* n_new, int32_t* pos, const int32_t* lens, Backend& be,
               const NoiseRng* rng = nullptr, bool trim = true) {
   if constexpr (live_tick_backend<Backend>) {
-    if (G.status != QVC_OK || G.W < 2) return G.status != QVC_OK ? G.status : QVC_ERR_BAD_ARG;
+    if (G.usable() != QVC_OK) return G.usable();
     const LiveState S = carve_live_state(P, G, B);
-    const TickScratch X = carve_tick_scratch(P, G, B);
+    const LiveScratch X = carve_live_scratch(P, G, B, true);
     int st = QVC_OK;
     auto ok = [&](int rc) { if (st == QVC_OK && rc != QVC_OK) st = rc; };
     float* uring = reinterpret_cast<float*>(state + S.unit);
@@ -548,9 +597,9 @@ int live_tick(const Plan& P, const LiveGeom& G, const char* blob, char* state, c
     ra.n_new = n_new; ra.pos = pos; ra.lens = lens; ra.pos_eff = pos_eff; ra.len_eff = len_eff;
     ok(be.tick_rings(ra));
     size_t wave_rows = 0, first = 0;
-    ok(live_window(P, G, X.live, blob, ws, uring, g, nring, B, pos_eff, len_eff, be, rng, trim, wave_rows, first));
+    ok(live_window(P, G, X, blob, ws, uring, g, nring, B, pos_eff, len_eff, be, rng, trim, wave_rows, first));
     TickDeliverArgs da;
-    da.wave = reinterpret_cast<const float*>(ws + X.live.wave); da.out = out;
+    da.wave = reinterpret_cast<const float*>(ws + X.wave); da.out = out;
     da.B = B; da.rows = (int32_t)wave_rows; da.first = (int32_t)first; da.hop = G.hop; da.spf = samples_per_frame(P);
     da.n_new = n_new; da.pos = pos;
     ok(be.tick_deliver(da));

@@ -268,17 +268,41 @@ class QvcEngine:
         L.check(self.lib, st, "qvc_infer_fanout_ragged")
         return out
 
-    # ---- streaming (qvc_stream_step): sizes, lags and one step; the state / workspace tensors belong to the caller
-    def stream_sizes(self, batch: int, hop: int):
-        """(state_bytes, workspace_bytes, lag_frames, noise_lag_frames) for `batch` streams fed `hop` frames per step."""
-        vals = (int(self.lib.qvc_stream_state_bytes(ctypes.byref(self.cfg), batch, hop)),
-                int(self.lib.qvc_stream_workspace_bytes(ctypes.byref(self.cfg), batch, hop)),
-                int(self.lib.qvc_stream_lag_frames(ctypes.byref(self.cfg))),
-                int(self.lib.qvc_stream_noise_lag_frames(ctypes.byref(self.cfg))))
+    # ---- streaming: the segment rings (qvc_stream_*), the windowed step with a bounded look-ahead (qvc_live_*: every
+    #      decoder, the lag is the caller's choice) and its tick form (qvc_live_tick*: per-slot frame counts on the
+    #      device).  Sizes, one step and the per-slot reset of each; the state / workspace tensors belong to the caller.
+    def _stream_sizes(self, form: str, queries, *args):
+        """The values of lib.qvc_<query>(cfg, ...) -- the byte queries with ``args``, the frame queries without."""
+        cfg = ctypes.byref(self.cfg)
+        vals = tuple(int(getattr(self.lib, "qvc_" + q)(cfg, *(args if q.endswith("_bytes") else ()))) for q in queries)
         for v in vals:
             if v < 0:
-                L.check(self.lib, v, "qvc_stream_*_bytes")
+                L.check(self.lib, v, f"qvc_{form}_*_bytes")
         return vals
+
+    def _stream_call(self, form: str, state, ws, unit_new, g, noise_new, out, geom, ptrs, rng) -> None:
+        """qvc_<form> / qvc_<form>_rng: ``geom`` the integers behind the batch (hop, look_ahead), ``ptrs`` the int32 device
+        tensors in front of the workspace (n_new, pos, lens)."""
+        B = unit_new.shape[0]
+        if rng is not None and not (torch.is_tensor(rng[1]) and rng[1].device == self.device):
+            raise ValueError(f"{form} needs the rng keys as an int64 tensor on the engine's device (slots are rewritten in place)")
+        noise_new, desc, _ = self._draw(noise_new, rng, B, (B, self.model_config["inter_channels"], unit_new.shape[2]))
+        fn, draw = (getattr(self.lib, "qvc_" + form), noise_new.data_ptr()) if desc is None else (getattr(self.lib, f"qvc_{form}_rng"), ctypes.byref(desc))
+        st = fn(ctypes.byref(self.cfg), self.blob.data_ptr(), state.data_ptr(), state.numel(), unit_new.data_ptr(), g.data_ptr(),
+                draw, out.data_ptr(), B, *geom, *(t.data_ptr() for t in ptrs), ws.data_ptr(), ws.numel(),
+                torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib, st, "qvc_" + form)
+
+    def _stream_reset_slot(self, form: str, state, batch, geom, slot, length, pos, lens) -> None:
+        st = getattr(self.lib, f"qvc_{form}_reset_slot")(ctypes.byref(self.cfg), state.data_ptr(), state.numel(), batch, *geom, int(slot),
+                                                         int(length), pos.data_ptr(), lens.data_ptr(),
+                                                         torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib, st, f"qvc_{form}_reset_slot")
+
+    def stream_sizes(self, batch: int, hop: int):
+        """(state_bytes, workspace_bytes, lag_frames, noise_lag_frames) for `batch` streams fed `hop` frames per step."""
+        return self._stream_sizes("stream", ("stream_state_bytes", "stream_workspace_bytes", "stream_lag_frames", "stream_noise_lag_frames"),
+                                  batch, hop)
 
     @_on_device
     def stream_step(self, state: torch.Tensor, ws: torch.Tensor, unit_new: torch.Tensor, g: torch.Tensor, noise_new: Optional[torch.Tensor],
@@ -287,43 +311,18 @@ class QvcEngine:
         ``rng``: with ``noise_new=None``, ``(seed, keys, scale)`` with ``keys`` an int64 tensor of one key per slot ON THIS
         DEVICE (qvc_stream_step_rng): the caller writes keys[slot] when it admits a stream; a captured step holds the
         array's pointer, so the tensor must outlive the graph."""
-        B, _, hop = unit_new.shape
-        if rng is not None and not (torch.is_tensor(rng[1]) and rng[1].device == self.device):
-            raise ValueError("stream_step needs the rng keys as an int64 tensor on the engine's device (slots are rewritten in place)")
-        noise_new, desc, _ = self._draw(noise_new, rng, B, (B, self.model_config["inter_channels"], hop))
-        if desc is None:
-            st = self.lib.qvc_stream_step(ctypes.byref(self.cfg), self.blob.data_ptr(), state.data_ptr(), state.numel(),
-                                          unit_new.data_ptr(), g.data_ptr(), noise_new.data_ptr(), out.data_ptr(), B, hop,
-                                          pos.data_ptr(), lens.data_ptr(), ws.data_ptr(), ws.numel(),
-                                          torch.cuda.current_stream(self.device).cuda_stream)
-        else:
-            st = self.lib.qvc_stream_step_rng(ctypes.byref(self.cfg), self.blob.data_ptr(), state.data_ptr(), state.numel(),
-                                              unit_new.data_ptr(), g.data_ptr(), ctypes.byref(desc), out.data_ptr(), B, hop,
-                                              pos.data_ptr(), lens.data_ptr(), ws.data_ptr(), ws.numel(),
-                                              torch.cuda.current_stream(self.device).cuda_stream)
-        L.check(self.lib, st, "qvc_stream_step")
+        self._stream_call("stream_step", state, ws, unit_new, g, noise_new, out, (unit_new.shape[2],), (pos, lens), rng)
 
     @_on_device
     def stream_reset_slot(self, state: torch.Tensor, batch: int, hop: int, slot: int, length: int, pos: torch.Tensor,
                           lens: torch.Tensor) -> None:
         """qvc_stream_reset_slot: zero slot `slot`'s ring rows, pos[slot] = 0, lens[slot] = length (on the current stream)."""
-        st = self.lib.qvc_stream_reset_slot(ctypes.byref(self.cfg), state.data_ptr(), state.numel(), batch, hop, int(slot),
-                                            int(length), pos.data_ptr(), lens.data_ptr(),
-                                            torch.cuda.current_stream(self.device).cuda_stream)
-        L.check(self.lib, st, "qvc_stream_reset_slot")
+        self._stream_reset_slot("stream", state, batch, (hop,), slot, length, pos, lens)
 
-    # ---- windowed streaming with a bounded look-ahead (qvc_live_step): every decoder, the lag is the caller's choice
     def live_sizes(self, batch: int, hop: int, look_ahead: int):
         """(state_bytes, workspace_bytes, context_frames) for `batch` streams fed `hop` frames per step whose output lags
         the input by `look_ahead` frames (0 <= look_ahead <= context_frames); the window is context + look_ahead + hop."""
-        cfg = ctypes.byref(self.cfg)
-        vals = (int(self.lib.qvc_live_state_bytes(cfg, batch, hop, look_ahead)),
-                int(self.lib.qvc_live_workspace_bytes(cfg, batch, hop, look_ahead)),
-                int(self.lib.qvc_live_context_frames(cfg)))
-        for v in vals:
-            if v < 0:
-                L.check(self.lib, v, "qvc_live_*_bytes")
-        return vals
+        return self._stream_sizes("live", ("live_state_bytes", "live_workspace_bytes", "live_context_frames"), batch, hop, look_ahead)
 
     @_on_device
     def live_step(self, state: torch.Tensor, ws: torch.Tensor, unit_new: torch.Tensor, g: torch.Tensor, noise_new: Optional[torch.Tensor],
@@ -331,36 +330,18 @@ class QvcEngine:
         """One hop for every stream (all tensors fp32 / int32, contiguous, on this device; see include/qvc.h): `out`
         receives frames [pos - look_ahead, ... + hop) of the conversion of each stream's prefix.  ``noise_new``: the draw
         for the frames of ``unit_new``; ``rng``: as stream_step."""
-        B, _, hop = unit_new.shape
-        if rng is not None and not (torch.is_tensor(rng[1]) and rng[1].device == self.device):
-            raise ValueError("live_step needs the rng keys as an int64 tensor on the engine's device (slots are rewritten in place)")
-        noise_new, desc, _ = self._draw(noise_new, rng, B, (B, self.model_config["inter_channels"], hop))
-        fn, draw = (self.lib.qvc_live_step, noise_new.data_ptr()) if desc is None else (self.lib.qvc_live_step_rng, ctypes.byref(desc))
-        st = fn(ctypes.byref(self.cfg), self.blob.data_ptr(), state.data_ptr(), state.numel(), unit_new.data_ptr(), g.data_ptr(),
-                draw, out.data_ptr(), B, hop, int(look_ahead), pos.data_ptr(), lens.data_ptr(), ws.data_ptr(), ws.numel(),
-                torch.cuda.current_stream(self.device).cuda_stream)
-        L.check(self.lib, st, "qvc_live_step")
+        self._stream_call("live_step", state, ws, unit_new, g, noise_new, out, (unit_new.shape[2], int(look_ahead)), (pos, lens), rng)
 
     @_on_device
     def live_reset_slot(self, state: torch.Tensor, batch: int, hop: int, look_ahead: int, slot: int, length: int, pos: torch.Tensor,
                         lens: torch.Tensor) -> None:
         """qvc_live_reset_slot: zero slot `slot`'s ring rows, pos[slot] = 0, lens[slot] = length (on the current stream)."""
-        st = self.lib.qvc_live_reset_slot(ctypes.byref(self.cfg), state.data_ptr(), state.numel(), batch, hop, int(look_ahead), int(slot),
-                                          int(length), pos.data_ptr(), lens.data_ptr(),
-                                          torch.cuda.current_stream(self.device).cuda_stream)
-        L.check(self.lib, st, "qvc_live_reset_slot")
+        self._stream_reset_slot("live", state, batch, (hop, int(look_ahead)), slot, length, pos, lens)
 
-    # ---- the tick form of the windowed step (qvc_live_tick): per-slot frame counts, the counts on the device
     def live_tick_sizes(self, batch: int, hop: int, look_ahead: int):
         """(state_bytes, workspace_bytes, context_frames) for `batch` streams that bring AT MOST `hop` frames per tick."""
-        cfg = ctypes.byref(self.cfg)
-        vals = (int(self.lib.qvc_live_tick_state_bytes(cfg, batch, hop, look_ahead)),
-                int(self.lib.qvc_live_tick_workspace_bytes(cfg, batch, hop, look_ahead)),
-                int(self.lib.qvc_live_context_frames(cfg)))
-        for v in vals:
-            if v < 0:
-                L.check(self.lib, v, "qvc_live_tick_*_bytes")
-        return vals
+        return self._stream_sizes("live_tick", ("live_tick_state_bytes", "live_tick_workspace_bytes", "live_context_frames"),
+                                  batch, hop, look_ahead)
 
     @_on_device
     def live_tick(self, state: torch.Tensor, ws: torch.Tensor, unit_new: torch.Tensor, g: torch.Tensor, noise_new: Optional[torch.Tensor],
@@ -368,26 +349,15 @@ class QvcEngine:
         """One tick (all tensors fp32 / int32, contiguous, on this device; see include/qvc.h): slot b brings
         clamp(n_new[b], 0, hop) frames in the first columns of its row of ``unit_new`` (B, unit_channels, hop); `out`
         receives that many frames from pos - look_ahead on, then zeros; ``pos`` is advanced on the device."""
-        B, _, hop = unit_new.shape
-        if rng is not None and not (torch.is_tensor(rng[1]) and rng[1].device == self.device):
-            raise ValueError("live_tick needs the rng keys as an int64 tensor on the engine's device (slots are rewritten in place)")
-        if n_new.dtype != torch.int32 or n_new.device != self.device or n_new.numel() != B:
+        if n_new.dtype != torch.int32 or n_new.device != self.device or n_new.numel() != unit_new.shape[0]:
             raise ValueError("live_tick needs n_new as an int32 tensor of one count per slot on the engine's device")
-        noise_new, desc, _ = self._draw(noise_new, rng, B, (B, self.model_config["inter_channels"], hop))
-        fn, draw = (self.lib.qvc_live_tick, noise_new.data_ptr()) if desc is None else (self.lib.qvc_live_tick_rng, ctypes.byref(desc))
-        st = fn(ctypes.byref(self.cfg), self.blob.data_ptr(), state.data_ptr(), state.numel(), unit_new.data_ptr(), g.data_ptr(),
-                draw, out.data_ptr(), B, hop, int(look_ahead), n_new.data_ptr(), pos.data_ptr(), lens.data_ptr(), ws.data_ptr(),
-                ws.numel(), torch.cuda.current_stream(self.device).cuda_stream)
-        L.check(self.lib, st, "qvc_live_tick")
+        self._stream_call("live_tick", state, ws, unit_new, g, noise_new, out, (unit_new.shape[2], int(look_ahead)), (n_new, pos, lens), rng)
 
     @_on_device
     def live_tick_reset_slot(self, state: torch.Tensor, batch: int, hop: int, look_ahead: int, slot: int, length: int,
                              pos: torch.Tensor, lens: torch.Tensor) -> None:
         """qvc_live_tick_reset_slot: zero slot `slot`'s ring rows, pos[slot] = 0, lens[slot] = length (on the current stream)."""
-        st = self.lib.qvc_live_tick_reset_slot(ctypes.byref(self.cfg), state.data_ptr(), state.numel(), batch, hop, int(look_ahead),
-                                               int(slot), int(length), pos.data_ptr(), lens.data_ptr(),
-                                               torch.cuda.current_stream(self.device).cuda_stream)
-        L.check(self.lib, st, "qvc_live_tick_reset_slot")
+        self._stream_reset_slot("live_tick", state, batch, (hop, int(look_ahead)), slot, length, pos, lens)
 
     def _pack_spk(self) -> None:
         if self._spk_blob is None:

@@ -84,18 +84,6 @@ def declare(lib: ctypes.CDLL, prefix: str = "qvc") -> None:
         lib.qvc_infer_batch_ragged.argtypes = [cfgp, V, V, V, V, V, I, I, V, V, L, V]
         lib.qvc_infer_batch_ragged_fm.restype = ctypes.c_int
         lib.qvc_infer_batch_ragged_fm.argtypes = [cfgp, V, V, V, V, V, I, I, V, V, L, V]
-        lib.qvc_stream_state_bytes.restype = L
-        lib.qvc_stream_state_bytes.argtypes = [cfgp, I, I]
-        lib.qvc_stream_workspace_bytes.restype = L
-        lib.qvc_stream_workspace_bytes.argtypes = [cfgp, I, I]
-        lib.qvc_stream_lag_frames.restype = I
-        lib.qvc_stream_lag_frames.argtypes = [cfgp]
-        lib.qvc_stream_noise_lag_frames.restype = I
-        lib.qvc_stream_noise_lag_frames.argtypes = [cfgp]
-        lib.qvc_stream_step.restype = ctypes.c_int
-        lib.qvc_stream_step.argtypes = [cfgp, V, V, L, V, V, V, V, I, I, V, V, V, L, V]
-        lib.qvc_stream_reset_slot.restype = ctypes.c_int
-        lib.qvc_stream_reset_slot.argtypes = [cfgp, V, L, I, I, I, I, V, V, V]
         lib.qvc_aux_create.restype = ctypes.c_int
         lib.qvc_aux_create.argtypes = [P(V)]
         lib.qvc_aux_destroy.restype = ctypes.c_int
@@ -179,46 +167,33 @@ def declare(lib: ctypes.CDLL, prefix: str = "qvc") -> None:
             fn = getattr(lib, prefix + name)
             fn.restype = ctypes.c_int
             fn.argtypes = [cfgp, V, V, V, V, V, rngp, V, I, I, I, V, L, V]
-        fn = getattr(lib, prefix + "_stream_step_rng")
-        fn.restype = ctypes.c_int
-        fn.argtypes = [cfgp, V, V, L, V, V, rngp, V, I, I, V, V, V, L, V]
         fn = getattr(lib, prefix + "_noise_fill")
         fn.restype = ctypes.c_int
         fn.argtypes = [ctypes.c_uint64, V, ctypes.c_float, I, I, I, I, V, V]
-    # the windowed step with a bounded look-ahead (qvc_live_*): only on a library that has it, as above
-    if hasattr(lib, prefix + "_live_step"):
-        fn = getattr(lib, prefix + "_live_context_frames")
-        fn.restype = I
-        fn.argtypes = [cfgp]
-        for name in ("_live_state_bytes", "_live_workspace_bytes"):
-            fn = getattr(lib, prefix + name)
+    # the windowed step with a bounded look-ahead (qvc_live_*) and its tick form (qvc_live_tick*: per-slot frame counts
+    # per call): only on a library that has them, as above -- the emulation libraries are frozen before both.
+    # With the segment rings (qvc_stream_*) one table: (the step, the stem of its size queries and reset, the integers
+    # behind the batch -- hop[, look_ahead] --, the int32 device arrays in front of the workspace).  A step is (cfg, blob,
+    # state, state_bytes, unit_new, g, noise_new | rng, out, batch, integers..., arrays..., workspace, workspace_bytes, stream).
+    for step, stem, ints, arrays in (("_stream_step", "_stream", 1, 2), ("_live_step", "_live", 2, 2), ("_live_tick", "_live_tick", 2, 3)):
+        if not hasattr(lib, prefix + stem + "_state_bytes"):
+            continue
+        for name in ("_state_bytes", "_workspace_bytes"):
+            fn = getattr(lib, prefix + stem + name)
             fn.restype = L
-            fn.argtypes = [cfgp, I, I, I]
-        fn = getattr(lib, prefix + "_live_step")
-        fn.restype = ctypes.c_int
-        fn.argtypes = [cfgp, V, V, L, V, V, V, V, I, I, I, V, V, V, L, V]
-        fn = getattr(lib, prefix + "_live_step_rng")
-        fn.restype = ctypes.c_int
-        fn.argtypes = [cfgp, V, V, L, V, V, P(QvcNoiseRng), V, I, I, I, V, V, V, L, V]
-        fn = getattr(lib, prefix + "_live_reset_slot")
-        fn.restype = ctypes.c_int
-        fn.argtypes = [cfgp, V, L, I, I, I, I, I, V, V, V]
-    # the tick form (qvc_live_tick*: per-slot frame counts per call): the product library only -- the emulation
-    # libraries are frozen before it
-    if hasattr(lib, prefix + "_live_tick"):
-        for name in ("_live_tick_state_bytes", "_live_tick_workspace_bytes"):
+            fn.argtypes = [cfgp, I] + [I] * ints
+        for name, draw in ((step, V), (step + "_rng", P(QvcNoiseRng))):
             fn = getattr(lib, prefix + name)
-            fn.restype = L
-            fn.argtypes = [cfgp, I, I, I]
-        fn = getattr(lib, prefix + "_live_tick")
+            fn.restype = ctypes.c_int
+            fn.argtypes = [cfgp, V, V, L, V, V, draw, V, I] + [I] * ints + [V] * arrays + [V, L, V]
+        fn = getattr(lib, prefix + stem + "_reset_slot")
         fn.restype = ctypes.c_int
-        fn.argtypes = [cfgp, V, V, L, V, V, V, V, I, I, I, V, V, V, V, L, V]
-        fn = getattr(lib, prefix + "_live_tick_rng")
-        fn.restype = ctypes.c_int
-        fn.argtypes = [cfgp, V, V, L, V, V, P(QvcNoiseRng), V, I, I, I, V, V, V, V, L, V]
-        fn = getattr(lib, prefix + "_live_tick_reset_slot")
-        fn.restype = ctypes.c_int
-        fn.argtypes = [cfgp, V, L, I, I, I, I, I, V, V, V]
+        fn.argtypes = [cfgp, V, L, I] + [I] * ints + [I, I, V, V, V]
+    for name in ("_stream_lag_frames", "_stream_noise_lag_frames", "_live_context_frames"):
+        if hasattr(lib, prefix + name):
+            fn = getattr(lib, prefix + name)
+            fn.restype = I
+            fn.argtypes = [cfgp]
 
 
 _lib = None

@@ -247,12 +247,22 @@ class StreamConverter:
         ``noise_new=None``: the generator form (needs a seed: the constructor's, ``set_seed`` or ``convert(seed=...)``)."""
         if noise_new is None and self._rng is None:
             raise ValueError("step() without noise_new needs a seed (StreamConverter(seed=...) or set_seed)")
+        out = self._issue(unit_new, noise_new)
+        self._pos_host = [p + self.hop for p in self._pos_host]
+        return out
+
+    def _issue(self, unit_new: torch.Tensor, noise_new: Optional[torch.Tensor], counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One step / tick on the side stream, ordered after the caller's stream and in front of its next work: the inputs
+        (``counts``: a tick's, into ``self._n``) copied in, the captured graph replayed (or the call issued directly), a
+        copy of the output."""
         dev = self.engine.device
         self._stream.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(self._stream):
             self._unit.copy_(unit_new, non_blocking=True)
             if noise_new is not None:
                 self._noise.copy_(noise_new, non_blocking=True)
+            if counts is not None:
+                self._n.copy_(counts)
             graph = self._graph if noise_new is not None else self._rng_graph
             if graph is not None:
                 graph.replay()
@@ -260,7 +270,6 @@ class StreamConverter:
                 self._one_step(rng=noise_new is None)
             out = self._out.clone()
         torch.cuda.current_stream(dev).wait_stream(self._stream)
-        self._pos_host = [p + self.hop for p in self._pos_host]
         return out
 
     @torch.no_grad()
@@ -383,20 +392,7 @@ class TickConverter(LiveConverter):
         counts = torch.as_tensor(n_new, dtype=torch.int32, device="cpu").reshape(-1)
         if counts.numel() != self.streams:
             raise ValueError(f"{self.streams} slots need {self.streams} counts, got {counts.numel()}")
-        dev = self.engine.device
-        self._stream.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(self._stream):
-            self._unit.copy_(unit_new, non_blocking=True)
-            if noise_new is not None:
-                self._noise.copy_(noise_new, non_blocking=True)
-            self._n.copy_(counts)
-            graph = self._graph if noise_new is not None else self._rng_graph
-            if graph is not None:
-                graph.replay()
-            else:
-                self._one_step(rng=noise_new is None)
-            out = self._out.clone()
-        torch.cuda.current_stream(dev).wait_stream(self._stream)
+        out = self._issue(unit_new, noise_new, counts)
         n = [min(max(int(v), 0), self.hop) for v in counts.tolist()]
         self._pos_host = [p + k for p, k in zip(self._pos_host, n)]
         return out, n

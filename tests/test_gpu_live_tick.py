@@ -24,67 +24,17 @@ import config_space as CS
 import memguard as M
 import tick_patterns as TP
 from helpers import load_case, regenerate, snr_db
+import live_common as LC
+from live_common import NAN, SEED, _Model, _debug_switches_at_defaults, _keys, dev, lib  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-DEBUG_DEFAULTS = {"post_tail": 1, "post_tail_nf": 4, "pair_wide_launch": 1, "pair_cm4": 1, "conv_cl": 1, "wn_chunk": 0,
-                  "pair_chain3": 0, "wn_kernel": 0, "launch_stop": -1, "live_trim": 1}
-NAN = float("nan")
-SEED = 0x5EED1234ABCD
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from quickvc_official_amd import lib as L
-    l = L.load_library()                       # raises if the HIP library is missing: no fallback
-    assert l.qvc_device_check() == 0
-    return l
-
-
-@pytest.fixture(autouse=True)
-def _debug_switches_at_defaults():
-    from quickvc_official_amd import lib as L
-    for k, v in DEBUG_DEFAULTS.items():
-        L.debug_set(k, v)
-    yield
-    for k, v in DEBUG_DEFAULTS.items():
-        L.debug_set(k, v)
-
-
-class _Model:
-    """What the converters need of a model, for configurations SynthesizerTrn's constructor cannot name (the WaveNet keys)."""
-
-    def __init__(self, mc, sd, dev, dtype="f16"):
-        from quickvc_official_amd.engine import QvcEngine
-        self.model_config = dict(mc, operand_dtype=dtype)
-        self._engine = QvcEngine(self.model_config, sd, dev)
-        self.samples_per_frame = self._engine.samples_per_frame
-
-    def engine(self):
-        return self._engine
-
-
-@functools.lru_cache(maxsize=None)
 def _row_model(name, wn=None, dtype="f16"):
-    """(model, C) of a row of the configuration space; wn = (enc_layers, flow_layers, n_flows): the row with that WaveNet
-    geometry (kernel 5) and weights from wn_state_dict -- a short WaveNet keeps the window small."""
-    cfg, mc, sd = CS.problem(name)
-    if wn is not None:
-        keys = dict(wn_kernel_size=5, enc_layers=wn[0], flow_layers=wn[1], n_flows=wn[2])
-        cfg, mc = dict(cfg, **keys), dict(mc, **keys)
-        sd = CS.wn_state_dict(dict(sd), cfg)
-    model = _Model(mc, sd, torch.device("cuda:0"), dtype)
-    return model, model.engine().live_tick_sizes(1, 1, 0)[2]
+    return LC._row_model(name, wn, dtype, sizes="live_tick_sizes")
 
 
-def _keys(n):
-    return [0x9E3779B97F4A7C15 * (i + 1) & 0xFFFFFFFFFFFFFFFF for i in range(n)]
+def _prefix_rows(eng, unit_b, g_b, noise_b, key, prefixes):
+    return LC._prefix_rows(eng, unit_b, g_b, noise_b, key, prefixes, min_frames=2)
 
 
 def _tick_inputs(unit, noise, at, n, lens, S, hop):
@@ -120,16 +70,6 @@ def _tick_all(conv, unit, g, noise, lens, count_of, keys=None):
         assert k < 600
     assert conv._pos.tolist() == [conv.position(s) for s in range(S)], "the device positions and the host mirror disagree"
     return ticks
-
-
-def _prefix_rows(eng, unit_b, g_b, noise_b, key, prefixes):
-    """The conversions of the prefixes of ONE stream, as rows of one ragged call -> (len(prefixes), 1, max * spf)."""
-    R, t = len(prefixes), max(max(prefixes), 2)
-    frames = torch.tensor(prefixes, dtype=torch.int32)
-    u, gg = unit_b[None, :, :t].expand(R, -1, -1).contiguous(), g_b[None].expand(R, -1).contiguous()
-    if noise_b is None:
-        return eng.infer_batch_ragged(u, gg, None, frames, rng=(SEED, [key] * R, 1.0)).clone()
-    return eng.infer_batch_ragged(u, gg, noise_b[None, :, :t].expand(R, -1, -1).contiguous(), frames).clone()
 
 
 def _slot_ticks(ticks, slot):

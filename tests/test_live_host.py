@@ -1,6 +1,6 @@
 """CPU tests (no GPU) of the windowed streaming step with a bounded look-ahead (include/qvc.h: qvc_live_*;
 csrc/qvc_stream.h: live_step): the C ABI's surface, sizes, error codes and the bound C on the receptive field, and --
-through the CPU twin of the driver (tests/emu_live.cpp: live_step on the frozen emulation's backend) -- the two
+through the CPU twin of the driver (tools/emu_twin.cpp: live_step on the frozen emulation's backend) -- the two
 properties that define it:
 
   P1  a step's output is frames [pos - L, pos - L + hop) of the OFFLINE conversion of the stream's first
@@ -19,41 +19,21 @@ import ctypes
 import functools
 import os
 import re
-import sys
 
 import pytest
 import torch
 
 import config_space as CS
 from helpers import ROOT, snr_db
+from live_common import NAN, _aligned, _context, _spf, built, twin_library  # noqa: F401
 
-NAN = float("nan")
 NEW = ("qvc_live_context_frames", "qvc_live_state_bytes", "qvc_live_workspace_bytes", "qvc_live_step", "qvc_live_step_rng",
        "qvc_live_reset_slot")
 
 
 @pytest.fixture(scope="module")
-def built():
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as ge
-    ge.build()
-    from quickvc_official_amd import lib as L
-    return L.load_library()
-
-
-@pytest.fixture(scope="module")
 def twin(built):
-    """oracle/_build/libqvc_emu_live.so: qvc_emu_live_step / qvc_emu_live_reset_slot."""
-    import importlib
-    from quickvc_official_amd import lib as L
-    lib = ctypes.CDLL(importlib.import_module("quickvc_official_amd.build").build_emu_live())
-    P, I, Lg, V = ctypes.POINTER, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
-    lib.qvc_emu_live_step.restype = ctypes.c_int
-    lib.qvc_emu_live_step.argtypes = [P(L.QvcConfig), V, V, Lg, V, V, V, V, I, I, I, V, V, V, Lg]
-    lib.qvc_emu_live_reset_slot.restype = ctypes.c_int
-    lib.qvc_emu_live_reset_slot.argtypes = [P(L.QvcConfig), V, Lg, I, I, I, I, I, V, V]
-    lib.qvc_emu_live_trim.restype = None
-    lib.qvc_emu_live_trim.argtypes = [I]
+    lib = twin_library()
     yield lib
     lib.qvc_emu_live_trim(1)
 
@@ -68,10 +48,6 @@ def _named_configs():
     for row in ("one_up8", "istft_ups3", "istft_ups4"):
         out[row] = L.make_config(CS.problem(row)[1])
     return out
-
-
-def _context(built, cfg):
-    return int(built.qvc_live_context_frames(ctypes.byref(cfg)))
 
 
 def test_exports_and_abi(built):
@@ -162,12 +138,6 @@ def test_error_codes(built):
 
 
 # ---------------------------------------------------------------- the CPU twin
-def _aligned(n, fill):
-    raw = torch.full((n + 256,), fill, dtype=torch.uint8)
-    shift = (-raw.data_ptr()) % 256
-    return raw, raw[shift:shift + n]
-
-
 def _twin_stream(built, twin, mc, sd, unit, g, noise, lens, hop, L_, dtype="f16", trim=True):
     """Streams `lens[b]` frames of every row through qvc_emu_live_step until all have flushed.  State, workspace and the
     output chunk start from NaN bytes; every slot is started by qvc_emu_live_reset_slot; the frames of unit_new /
@@ -206,13 +176,6 @@ def _twin_stream(built, twin, mc, sd, unit, g, noise, lens, hop, L_, dtype="f16"
         steps.append((s, chunk))
         s += hop
     return steps
-
-
-def _spf(cfg):
-    n = int(cfg.hop) * int(cfg.subbands)
-    for i in range(int(cfg.n_ups)):
-        n *= int(cfg.upsample_rates[i])
-    return n
 
 
 def _check_against(steps, want_of_step, lens, hop, L_, spf):

@@ -1,13 +1,13 @@
 """CPU tests (no GPU) of the tick form of the windowed step (include/qvc.h: qvc_live_tick*; csrc/qvc_stream.h:
 live_tick): per call, slot b brings n = clamp(n_new[b], 0, hop) frames.  The C ABI's surface, sizes and error codes on
-the product library, and -- through the CPU twin of the driver (tests/emu_tick.cpp: live_tick on a backend derived from
+the product library, and -- through the CPU twin of the driver (tools/emu_twin.cpp: live_tick on a backend derived from
 the frozen emulation's, with host versions of the ring update and the delivery) -- the properties that define it:
 
   T1  the first n * spf samples of a tick's row are frames [pos - L, pos - L + n) of the OFFLINE conversion of the
       stream's first min(len, pos + n) frames, zeros outside [0, len); the rest of the row is 0.0; pos += n; a slot with
       n = 0 leaves no trace;
   T2  with L = C the concatenated output is the whole-utterance conversion however the stream was cut into ticks;
-  T3  with every n = hop the outputs are bit for bit qvc_live_step's (tests/emu_live.cpp's twin).
+  T3  with every n = hop the outputs are bit for bit qvc_live_step's (the same twin).
 
 The references are the emulation's own offline results and the comparison is bit equality (the SNR is printed first).
 The twin covers the band-synthesis decoders and the pointer form of the noise only, as the emulation.
@@ -16,7 +16,6 @@ import ctypes
 import functools
 import os
 import re
-import sys
 
 import pytest
 import torch
@@ -24,52 +23,22 @@ import torch
 import config_space as CS
 import tick_patterns as TP
 from helpers import ROOT, snr_db
+from live_common import NAN, _aligned, _context, _spf, built, twin_library  # noqa: F401
 
-NAN = float("nan")
 NEW = ("qvc_live_tick_state_bytes", "qvc_live_tick_workspace_bytes", "qvc_live_tick", "qvc_live_tick_rng", "qvc_live_tick_reset_slot")
 
 
 @pytest.fixture(scope="module")
-def built():
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as ge
-    ge.build()
-    from quickvc_official_amd import lib as L
-    return L.load_library()
-
-
-@pytest.fixture(scope="module")
 def twin(built):
-    """oracle/_build/libqvc_emu_tick.so: qvc_emu_live_tick / _reset_slot / _ring / _trim."""
-    import importlib
-    from quickvc_official_amd import lib as L
-    lib = ctypes.CDLL(importlib.import_module("quickvc_official_amd.build").build_emu_tick())
-    P, I, Lg, V = ctypes.POINTER, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
-    lib.qvc_emu_live_tick.restype = ctypes.c_int
-    lib.qvc_emu_live_tick.argtypes = [P(L.QvcConfig), V, V, Lg, V, V, V, V, I, I, I, V, V, V, V, Lg]
-    lib.qvc_emu_live_tick_reset_slot.restype = ctypes.c_int
-    lib.qvc_emu_live_tick_reset_slot.argtypes = [P(L.QvcConfig), V, Lg, I, I, I, I, I, V, V]
-    lib.qvc_emu_live_tick_ring.restype = ctypes.c_int
-    lib.qvc_emu_live_tick_ring.argtypes = [P(L.QvcConfig), I, I, I, I, I, P(Lg), P(Lg)]
-    lib.qvc_emu_live_tick_trim.restype = None
-    lib.qvc_emu_live_tick_trim.argtypes = [I]
+    lib = twin_library()
     yield lib
     lib.qvc_emu_live_tick_trim(1)
 
 
 @pytest.fixture(scope="module")
 def lockstep(built):
-    """oracle/_build/libqvc_emu_live.so: the twin of qvc_live_step (T3's other side)."""
-    import importlib
-    from quickvc_official_amd import lib as L
-    lib = ctypes.CDLL(importlib.import_module("quickvc_official_amd.build").build_emu_live())
-    P, I, Lg, V = ctypes.POINTER, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
-    lib.qvc_emu_live_step.restype = ctypes.c_int
-    lib.qvc_emu_live_step.argtypes = [P(L.QvcConfig), V, V, Lg, V, V, V, V, I, I, I, V, V, V, Lg]
-    lib.qvc_emu_live_reset_slot.restype = ctypes.c_int
-    lib.qvc_emu_live_reset_slot.argtypes = [P(L.QvcConfig), V, Lg, I, I, I, I, I, V, V]
-    lib.qvc_emu_live_trim.restype = None
-    lib.qvc_emu_live_trim.argtypes = [I]
+    """The twin of qvc_live_step (T3's other side): the same library."""
+    lib = twin_library()
     yield lib
     lib.qvc_emu_live_trim(1)
 
@@ -86,17 +55,6 @@ def _mini():
 def _cfg_of(mc, dtype="f16"):
     from quickvc_official_amd import lib as L
     return L.make_config(dict(mc, operand_dtype=dtype))
-
-
-def _context(built, cfg):
-    return int(built.qvc_live_context_frames(ctypes.byref(cfg)))
-
-
-def _spf(cfg):
-    n = int(cfg.hop) * int(cfg.subbands)
-    for i in range(int(cfg.n_ups)):
-        n *= int(cfg.upsample_rates[i])
-    return n
 
 
 # ---------------------------------------------------------------- surface
@@ -181,12 +139,6 @@ def test_error_codes(built):
 
 
 # ---------------------------------------------------------------- the CPU twin
-def _aligned(n, fill):
-    raw = torch.full((n + 256,), fill, dtype=torch.uint8)
-    shift = (-raw.data_ptr()) % 256
-    return raw, raw[shift:shift + n]
-
-
 def _ring_ranges(twin, p, B, hop, L_):
     """[slot][which] -> (offset, bytes) of the slot's unit / noise ring in the state."""
     out = []
