@@ -357,7 +357,8 @@ int qvc_live_reset_slot(const qvc_config* cfg, void* state, int64_t state_bytes,
  *              frames RIGHT-aligned (qvc_live_step keeps W - hop frames left-aligned).  The two states are therefore
  *              never exchanged: a tick state is never passed to qvc_live_step, a lockstep state never to these calls.
  *   workspace  qvc_live_tick_workspace_bytes() (more than qvc_live_workspace_bytes())
- * Errors as qvc_live_step; n_new_dev == NULL: QVC_ERR_BAD_ARG.  The segment rings (qvc_stream_step) keep lockstep. */
+ * Errors as qvc_live_step; n_new_dev == NULL: QVC_ERR_BAD_ARG.  The segment rings have a tick form of their own:
+ * qvc_stream_tick, below. */
 int64_t qvc_live_tick_state_bytes(const qvc_config* cfg, int32_t batch, int32_t hop, int32_t look_ahead);
 int64_t qvc_live_tick_workspace_bytes(const qvc_config* cfg, int32_t batch, int32_t hop, int32_t look_ahead);
 int qvc_live_tick(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes,
@@ -370,6 +371,44 @@ int qvc_live_tick_rng(const qvc_config* cfg, const void* blob_dev, void* state, 
                       const int32_t* len_dev, void* workspace, int64_t workspace_bytes, void* stream);
 int qvc_live_tick_reset_slot(const qvc_config* cfg, void* state, int64_t state_bytes, int32_t batch, int32_t hop,
                              int32_t look_ahead, int32_t slot, int32_t length, int32_t* pos_dev, int32_t* len_dev, void* stream);
+
+/* ---- the tick form of the segment rings: per-slot frame counts per call ------------------------------------------------
+ * qvc_stream_step moves every slot by exactly `hop` frames, so one late packet stalls every other stream of the batch.  In
+ * a tick slot b brings n = clamp(n_new_dev[b], 0, hop) frames.  The counts live in device memory, are read and clamped
+ * there and never on the host; `hop` is the MOST a slot may bring and sizes every buffer and launch.
+ *   unit_new   (B, unit_channels, hop) fp32: columns [0, n) of row b are frames [pos[b], pos[b] + n); columns [n, hop) --
+ *              the whole row of a slot with n = 0 -- are never read
+ *   noise_new  (B, inter_channels, hop) fp32, the same rule: the draw for frames [pos[b] - noise_lag, pos[b] - noise_lag
+ *              + n), noise_lag = qvc_stream_noise_lag_frames().  The _rng twin draws at the absolute frame with the
+ *              slot's key instead
+ *   out        (B, hop * samples_per_frame) fp32: the first n * samples_per_frame samples of row b are frames
+ *              [pos[b] - lag, pos[b] - lag + n) of the stream's whole-utterance conversion (qvc_infer_batch_ragged with the
+ *              same g and the same noise or (seed, key)), zeros outside [0, len[b]); the rest of the row is written as 0.0
+ *   pos_dev    advanced on the device by the call: pos[b] += n (hence not const)
+ * A slot with n = 0 leaves no trace: its rows of every ring and its pos bit for bit as they were, a row of zeros in
+ * `out`, its workgroups return at once.  One captured graph of the call replays for any tick pattern: only the contents
+ * of n_new_dev, pos_dev, len_dev, unit_new and noise_new change between replays.
+ * With every n = hop, `out` is bit for bit qvc_stream_step's, and so is every ring byte a later call can read (the kept
+ * 2*H frames of every ring; the hop frames behind them are rewritten before they are read and may differ).
+ * The segment rings are exact, so a stream's concatenated output is its whole-utterance conversion HOWEVER the stream
+ * was cut into ticks -- stronger than qvc_live_tick, which has that at L = C only.
+ *   state      the state of qvc_stream_step: qvc_stream_state_bytes(), started per slot with qvc_stream_reset_slot (or
+ *              zeroed with pos = 0).  Both calls leave the rings in the same layout, so a server may switch between
+ *              qvc_stream_step and qvc_stream_tick on one state at any call.
+ *   workspace  qvc_stream_tick_workspace_bytes() (more than qvc_stream_workspace_bytes())
+ * Errors as qvc_stream_step's, in the same order; n_new_dev == NULL: QVC_ERR_BAD_ARG.  The configurations
+ * qvc_stream_step refuses (the single-band decoder, decoders without exactly two up-samplers) get QVC_ERR_BAD_CONFIG
+ * here too, from the size query as well.  Asynchronous, allocation-free, capturable on one stream.
+ * csrc/qvc_stream.h (stream_tick) has the details. */
+int64_t qvc_stream_tick_workspace_bytes(const qvc_config* cfg, int32_t batch, int32_t hop);
+int qvc_stream_tick(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes,
+                    const float* unit_new, const float* g, const float* noise_new, float* out,
+                    int32_t batch, int32_t hop, const int32_t* n_new_dev, int32_t* pos_dev, const int32_t* len_dev,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+int qvc_stream_tick_rng(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes,
+                        const float* unit_new, const float* g, const qvc_noise_rng* rng, float* out,
+                        int32_t batch, int32_t hop, const int32_t* n_new_dev, int32_t* pos_dev, const int32_t* len_dev,
+                        void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- optional fork/join resources: lets the three independent ResBlocks of an MRF stage
  * (models.py:378-384) run as parallel branches (two auxiliary non-blocking streams + events), so a

@@ -3,7 +3,7 @@
   libqvc_hip.so      -- the product: gfx950 kernels + C ABI + host packer (hipcc --offload-arch=gfx950)
   libqvc_io.so       -- the product's host-side batch file I/O (g++; include/qvc_io.h)
   oracle/_build/libqvc_emu.so -- TEST-ONLY host emulation of the launch sequence (g++/hipcc host code)
-  oracle/_build/libqvc_emu_twin.so -- TEST-ONLY CPU twin of qvc_live_step / qvc_live_tick on the same emulation (tools/emu_twin.cpp)
+  oracle/_build/libqvc_emu_twin.so -- TEST-ONLY CPU twin of qvc_live_step / qvc_live_tick / qvc_stream_tick on the same emulation (tools/emu_twin.cpp)
 
 hipcc cross-compiles gfx950 without a GPU.  Translation units compile in parallel.
 """
@@ -111,7 +111,7 @@ def build_emu(force: bool = False) -> str:
 def build_emu_twin(force: bool = False) -> str:
     """The CPU twin of qvc_live_step and qvc_live_tick (tests only): tools/emu_twin.cpp includes the frozen
     oracle/qvc_emu.cpp, derives a backend with host versions of the tick's ring update and delivery from its EmuBackend
-    and adds qvc_emu_live_step / qvc_emu_live_tick -- a library of its own, the emulation library stays as it was."""
+    and adds qvc_emu_live_step / qvc_emu_live_tick / qvc_emu_stream_tick -- a library of its own, the emulation library stays as it was."""
     os.makedirs(EMU_DIR, exist_ok=True)
     srcs = [os.path.join(ROOT, "tools", "emu_twin.cpp"), os.path.join(CSRC, "qvc_pack.cpp")]
     deps = srcs + [os.path.join(ROOT, "oracle", "qvc_emu.cpp")] + [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(ROOT, "include", "qvc.h")]

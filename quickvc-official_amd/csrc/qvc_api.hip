@@ -98,6 +98,8 @@ struct HipBackend {
   static constexpr bool kLiveTick = true;         // live_tick: the ring update and the delivery driven by device counts
   int tick_rings(const TickRingsArgs& a) { return launch_tick_rings(a, stream); }
   int tick_deliver(const TickDeliverArgs& a) { return launch_tick_deliver(a, stream); }
+  static constexpr bool kStreamTick = true;       // stream_tick: copy_batch's job with the bytes per slot taken from device counts
+  int copy_counted(const CountedHead& h, const CountedDesc* d, int n) { return launch_copy_counted(h, d, n, stream); }
 };
 using Ctx = Path<HipBackend>;
 
@@ -315,6 +317,24 @@ int stream_step_api(const qvc_config* cfg, const void* blob_dev, void* state, in
     [&](HipBackend& be, const NoiseRng* rv) {
       return stream_step(P, static_cast<const char*>(blob_dev), static_cast<char*>(state), static_cast<char*>(workspace), unit_new, g,
                          noise_new, out, batch, hop, pos_dev, len_dev, be, rv);
+    });
+}
+
+// qvc_stream_tick: stream_step_api's checks plus n_new_dev, the tick's scratch, and pos_dev as the caller's int32_t*
+int stream_tick_api(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
+                    const float* g, const float* noise_new, const qvc_noise_rng* rng, float* out, int32_t batch, int32_t hop,
+                    const int32_t* n_new_dev, int32_t* pos_dev, const int32_t* len_dev, void* workspace, int64_t workspace_bytes, void* stream) {
+  Plan P; StreamGeom G;
+  return run_stream(unit_new && g && out && n_new_dev && pos_dev && len_dev, noise_new, rng, blob_dev, state, state_bytes, workspace, workspace_bytes,
+                    batch, stream,
+    [&](StreamBytes& b) {
+      const int gs = stream_plan(cfg, hop, P, G);
+      if (gs == QVC_OK) b = {carve_stream_state(P, G, batch).bytes, carve_stream_scratch(P, G, batch, true).bytes};
+      return gs;
+    },
+    [&](HipBackend& be, const NoiseRng* rv) {
+      return stream_tick(P, static_cast<const char*>(blob_dev), static_cast<char*>(state), static_cast<char*>(workspace), unit_new, g,
+                         noise_new, out, batch, hop, n_new_dev, pos_dev, len_dev, be, rv);
     });
 }
 
@@ -579,6 +599,27 @@ int qvc_stream_reset_slot(const qvc_config* cfg, void* state, int64_t state_byte
     if (gs == QVC_OK) R = stream_rings(P, G, batch);
     return gs;
   });
+}
+
+int64_t qvc_stream_tick_workspace_bytes(const qvc_config* cfg, int32_t batch, int32_t hop) {
+  Plan P; StreamGeom G;
+  const int st = batch > 0 ? stream_plan(cfg, hop, P, G) : QVC_ERR_BAD_ARG;
+  return st != QVC_OK ? st : carve_stream_scratch(P, G, batch, true).bytes;
+}
+
+int qvc_stream_tick(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
+                    const float* g, const float* noise_new, float* out, int32_t batch, int32_t hop, const int32_t* n_new_dev,
+                    int32_t* pos_dev, const int32_t* len_dev, void* workspace, int64_t workspace_bytes, void* stream) {
+  return stream_tick_api(cfg, blob_dev, state, state_bytes, unit_new, g, noise_new, nullptr, out, batch, hop, n_new_dev, pos_dev, len_dev,
+                         workspace, workspace_bytes, stream);
+}
+
+int qvc_stream_tick_rng(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
+                        const float* g, const qvc_noise_rng* rng, float* out, int32_t batch, int32_t hop, const int32_t* n_new_dev,
+                        int32_t* pos_dev, const int32_t* len_dev, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!rng) return QVC_ERR_BAD_ARG;
+  return stream_tick_api(cfg, blob_dev, state, state_bytes, unit_new, g, nullptr, rng, out, batch, hop, n_new_dev, pos_dev, len_dev,
+                         workspace, workspace_bytes, stream);
 }
 
 int32_t qvc_live_context_frames(const qvc_config* cfg) {

@@ -469,6 +469,41 @@ struct TickDeliverArgs {
 };
 int launch_tick_rings(const TickRingsArgs& a, void* stream);
 int launch_tick_deliver(const TickDeliverArgs& a, void* stream);
+
+// ---- the tick form of the segment rings (qvc_stream.h: stream_tick): copy_batch's job -- several independent strided
+//      copies / zero fills in ONE launch -- with what moves per slot decided on the device by n = tick_count(n_new, slot,
+//      hop).  A descriptor covers `slots` slots of `rows` rows each; slot s starts s * rows * dpitch bytes into dst and
+//      s * rows * spitch bytes into src.  Of every row of a slot it writes `width` bytes:
+//          [0, fixed + n * unit)      copied from the slot's source row, read from byte n * shift on
+//          [fixed + n * unit, width)  zeros
+//      (src == nullptr: fixed = unit = shift = 0, a zero fill).  A slot with n == 0 is not touched at all -- neither read
+//      nor written -- unless the descriptor says kCountedIdleZero: then its `width` bytes are zeros and src is not read.
+//      All sizes in bytes, multiples of 4, fixed + hop * unit <= width <= dpitch; the widest read of a source row,
+//      hop * shift + fixed + hop * unit, is the caller's to keep inside the row.  As with copy_batch, nothing a launch
+//      writes may overlap what the same launch reads or writes.
+struct CountedDesc {
+  void* dst;
+  const void* src;
+  uint32_t dpitch, spitch;
+  uint32_t fixed, unit, shift, width;
+  uint32_t rows;          // per slot
+  uint32_t flags;
+};
+constexpr uint32_t kCountedIdleZero = 1u;
+// What the launch shares: the counts and, by its first workgroup, the two pieces of per-slot bookkeeping of a tick.
+//   pos_eff / len_eff (with pos and lens; all four or none): what the segments' launches see in this tick --
+//       n > 0: pos[b], lens[b];   n == 0: idle_pos, 0 -- an empty sequence in every segment (idle_pos >= every segment's
+//       Ragged::off), so an idle slot's tiles return at once
+//   pos_add: pos_add[b] += n (nothing else in the same launch may read it)
+struct CountedHead {
+  const int32_t* n_new = nullptr;
+  int32_t slots = 0, hop = 0;
+  const int32_t* pos = nullptr; const int32_t* lens = nullptr;
+  int32_t* pos_eff = nullptr; int32_t* len_eff = nullptr;
+  int32_t idle_pos = 0;
+  int32_t* pos_add = nullptr;
+};
+int launch_copy_counted(const CountedHead& h, const CountedDesc* d, int n, void* stream);
 int launch_sample(const SampleArgs& a, void* stream);
 int launch_sample_rows(const SampleRowsArgs& a, void* stream);
 // (rows, channels, frames) fp32 in the reference's layout, frames [frame0, frame0 + frames): the tensor the draw sites would compute

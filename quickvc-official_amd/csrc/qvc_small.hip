@@ -536,6 +536,103 @@ int launch_tick_deliver(const TickDeliverArgs& a, void* stream) {
   return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
 }
 
+// ------------------------------------------------------------------ count-aware batched copies (qvc_stream.h: stream_tick)
+// copy_batch_kernel's job with the bytes per slot taken from n_new on the device.  A workgroup serves one chunk of ONE
+// slot of one descriptor, so n is uniform in it: the early return of an idle slot and the choice of the vector width
+// are not divergent.  A descriptor whose addresses, pitches, fixed part and width are multiples of 16 (wide) moves 16
+// bytes per lane whenever n * unit and n * shift are too -- the frame-major rings always, the (B, C, T) unit ring when
+// n % 4 == 0 -- and otherwise covers the same chunk with 4-byte elements in four passes: its shift is then 4-byte aligned
+// only.  Every copy goes ring -> scratch or scratch -> ring, never in place, so no pass ordering is needed.
+struct CopyCountedArgs {
+  CountedDesc d[kCopyBatchMax];
+  uint32_t first[kCopyBatchMax + 1];   // first workgroup of descriptor i; first[n] = grid size
+  uint32_t chunks[kCopyBatchMax];      // workgroups per slot
+  uint32_t wide[kCopyBatchMax];        // 1: sized in 16-byte elements (see above), 0: in 4-byte elements
+  int32_t n;
+  CountedHead h;
+};
+
+template <typename V>
+__device__ inline void counted_span(const CountedDesc& d, uint32_t slot, uint32_t chunk, uint32_t passes, uint32_t n, bool zero_only) {
+  const uint32_t wv = d.width / (uint32_t)sizeof(V);
+  const uint32_t total = wv * d.rows;
+  const uint32_t valid = zero_only ? 0u : d.fixed + n * d.unit;                // bytes of a row that come from src
+  char* dst = static_cast<char*>(d.dst) + (size_t)slot * d.rows * d.dpitch;
+  const char* src = static_cast<const char*>(d.src) + (size_t)slot * d.rows * d.spitch + (size_t)n * d.shift;
+  for (uint32_t p = 0; p < passes; ++p) {
+    const uint32_t e0 = (chunk * passes + p) * (256u * kCopyPerThread) + threadIdx.x;
+    V v[kCopyPerThread];
+    uint32_t off[kCopyPerThread];
+#pragma unroll
+    for (int k = 0; k < kCopyPerThread; ++k) {
+      const uint32_t e = e0 + (uint32_t)k * 256u;
+      const uint32_t row = e / wv, col = (e - row * wv) * (uint32_t)sizeof(V);
+      off[k] = e < total ? row * d.dpitch + col : 0xffffffffu;
+      v[k] = V{};
+      if (e < total && col < valid) v[k] = *reinterpret_cast<const V*>(src + (size_t)row * d.spitch + col);
+    }
+#pragma unroll
+    for (int k = 0; k < kCopyPerThread; ++k)
+      if (off[k] != 0xffffffffu) *reinterpret_cast<V*>(dst + off[k]) = v[k];
+  }
+}
+
+__global__ __launch_bounds__(256) void copy_counted_kernel(const CopyCountedArgs a) {
+  if (blockIdx.x == 0) {       // the tick's bookkeeping: nothing else in this launch reads what it writes
+    for (int b = (int)threadIdx.x; b < a.h.slots; b += 256) {
+      const int nb = tick_count(a.h.n_new, b, a.h.hop);
+      if (a.h.pos_eff) {
+        a.h.pos_eff[b] = nb > 0 ? a.h.pos[b] : a.h.idle_pos;
+        a.h.len_eff[b] = nb > 0 ? a.h.lens[b] : 0;
+      }
+      if (a.h.pos_add && nb > 0) a.h.pos_add[b] += nb;
+    }
+  }
+  int i = 0;
+  while (i + 1 < a.n && blockIdx.x >= a.first[i + 1]) ++i;    // <= 12 descriptors: a scalar scan
+  const uint32_t wg = blockIdx.x - a.first[i];
+  const uint32_t slot = wg / a.chunks[i], chunk = wg - slot * a.chunks[i];
+  const uint32_t n = (uint32_t)tick_count(a.h.n_new, (int)slot, a.h.hop);
+  const bool idle_zero = (a.d[i].flags & kCountedIdleZero) != 0;
+  if (n == 0 && !idle_zero) return;
+  if (a.wide[i] && !((n * a.d[i].unit | n * a.d[i].shift) & 15u)) counted_span<uint4>(a.d[i], slot, chunk, 1, n, n == 0);
+  else counted_span<uint32_t>(a.d[i], slot, chunk, a.wide[i] ? 4u : 1u, n, n == 0);
+}
+
+int launch_copy_counted(const CountedHead& h, const CountedDesc* d, int n, void* stream) {
+  if (n <= 0) return QVC_OK;
+  if (!d || n > kCopyBatchMax || !h.n_new || h.slots < 1 || h.hop < 1) return QVC_ERR_BAD_ARG;
+  if ((h.pos_eff != nullptr) != (h.len_eff != nullptr) || (h.pos_eff && (!h.pos || !h.lens))) return QVC_ERR_BAD_ARG;
+  CopyCountedArgs a{};
+  a.h = h;
+  a.n = 0;
+  uint64_t wgs = 0;
+  for (int i = 0; i < n; ++i) {
+    const CountedDesc& c = d[i];
+    const uint32_t sizes = c.width | c.dpitch | c.spitch | c.fixed | c.unit | c.shift;
+    const uintptr_t addrs = reinterpret_cast<uintptr_t>(c.dst) | reinterpret_cast<uintptr_t>(c.src);
+    if (!c.dst || (sizes & 3u) || (addrs & 3u)) return QVC_ERR_BAD_ARG;
+    if (!c.src && (c.fixed | c.unit | c.shift)) return QVC_ERR_BAD_ARG;
+    if ((uint64_t)c.fixed + (uint64_t)h.hop * c.unit > c.width || c.width > c.dpitch) return QVC_ERR_BAD_ARG;
+    if (c.src && (uint64_t)h.hop * c.shift + c.fixed + (uint64_t)h.hop * c.unit > c.spitch) return QVC_ERR_BAD_ARG;
+    if (c.width == 0 || c.rows == 0) continue;
+    // a slot's rows are whole multiples of 16 bytes apart when the pitches are, so one test serves every slot
+    const bool wide = !(((c.width | c.dpitch | c.spitch | c.fixed) & 15u) || (addrs & 15u));
+    const uint64_t total = (uint64_t)(c.width / (wide ? 16u : 4u)) * c.rows;      // elements per slot
+    // 32-bit element and in-slot offset arithmetic in the kernel (the 4-byte passes of a wide descriptor: 4 * total)
+    if (total * 4 >= (1ull << 31) || (uint64_t)c.rows * c.dpitch >= (1ull << 32) || (uint64_t)c.rows * c.spitch >= (1ull << 32)) return QVC_ERR_BAD_ARG;
+    a.d[a.n] = c; a.wide[a.n] = wide ? 1u : 0u; a.first[a.n] = (uint32_t)wgs;
+    a.chunks[a.n] = (uint32_t)((total + 256u * kCopyPerThread - 1) / (256u * kCopyPerThread));
+    wgs += (uint64_t)a.chunks[a.n] * (uint32_t)h.slots;
+    if (wgs >= (1ull << 31)) return QVC_ERR_BAD_ARG;
+    ++a.n;
+  }
+  if (a.n == 0) return h.pos_eff || h.pos_add ? QVC_ERR_BAD_ARG : QVC_OK;     // bookkeeping rides on a copy: none to ride on
+  a.first[a.n] = (uint32_t)wgs;
+  hipLaunchKernelGGL(copy_counted_kernel, dim3((unsigned)wgs), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
+}
+
 // ------------------------------------------------------------------ conv dispatcher
 int launch_conv(const ConvDesc& d, ConvArgs a, int batch, int epi, int dtype, void* stream, int* nf_out) {
   conv_geometry(a, d);

@@ -21,12 +21,14 @@
 // Sequence starts and ends inside a window are exact: every kernel masks its input rows by the absolute position
 // of the window (Ragged: pos / lens), i.e. each conv zero-pads at the sequence's own ends.
 //
-// Three drivers share this file: stream_step (the segment rings above), live_step (one window over the whole path,
-// below) and live_tick (live_step with per-slot frame counts).  What they share is stated once:
+// Four drivers share this file: stream_step (the segment rings above), stream_tick (stream_step with per-slot frame
+// counts, on the same state), live_step (one window over the whole path, below) and live_tick (live_step with per-slot
+// frame counts).  What they share is stated once:
 //   Rings         the ring table of a driver (stream_rings / live_rings): where every ring lies in the state and its
 //                 geometry.  The state size, the slide buffers of the scratch, the slide loops and the per-slot reset
 //                 (reset_slot, slot_range) all read the table, so a ring is added or resized in ONE place.
-//   CopyQueue     the copy-descriptor queue in front of the backend's copy_batch (all data movement of a step).
+//   CopyQueue     the copy-descriptor queue in front of the backend's copy_batch (all data movement of a step);
+//                 CountedQueue: its sibling in front of copy_counted (all data movement of a stream_tick).
 //   Segments      the factory of a step's Path segments.
 //   stream_checks the pure-host checks of an entry point (the C ABI's scaffold in qvc_api.hip and the CPU twin call it).
 #pragma once
@@ -214,12 +216,13 @@ struct StreamScratch {   // carved from the END of the step's workspace, after t
                             // (two of them: layer k's result feeds the copy for layer k+1 in the same launch)
   int64_t wave = 0;         // fp32 (B, spf * (2*Hd2 + hop))
   int64_t tmp[21] = {};     // slide buffers, one per ring of the table
+  int64_t pos_eff = 0, len_eff = 0;   // int32 [B] each: a tick's effective positions and lengths (tick = true only)
   int64_t bytes = 0;
 };
 
 inline int samples_per_frame(const Plan& P) { return P.total_up * P.cfg.hop * P.cfg.subbands; }
 
-inline StreamScratch carve_stream_scratch(const Plan& P, const StreamGeom& G, int B) {
+inline StreamScratch carve_stream_scratch(const Plan& P, const StreamGeom& G, int B, bool tick = false) {
   StreamScratch X;
   const qvc_config& c = P.cfg;
   X.path_bytes = carve_workspace(P, B, G.max_window()).bytes;
@@ -228,6 +231,7 @@ inline StreamScratch carve_stream_scratch(const Plan& P, const StreamGeom& G, in
   for (int k = 0; k < 2; ++k) X.zwork[k] = cv.take((int64_t)B * (2 * G.Hf + G.hop) * c.inter_channels * 4);
   X.wave = cv.take((int64_t)B * samples_per_frame(P) * (2 * G.Hd2 + G.hop) * 4);
   stream_rings(P, G, B).carve_tmp(cv, B, X.tmp);
+  if (tick) { X.pos_eff = cv.take((int64_t)B * 4); X.len_eff = cv.take((int64_t)B * 4); }
   X.bytes = cv.off;
   return X;
 }
@@ -340,6 +344,185 @@ int stream_step(const Plan& P, const char* blob, char* state, char* ws, const fl
   q.slide_back(state, ws, S.rings, X.tmp, S.rings.n, B);
   q.flush();
   return q.st;
+}
+
+// ---------------------------------------------------------------- the tick form of the segment rings (stream_tick)
+// stream_step moves every slot by exactly `hop` frames.  A tick lets slot b bring n = clamp(n_new[b], 0, hop) frames, the
+// counts in device memory (a late packet, a client catching up, a short last chunk), on the SAME state:
+//
+//     INVARIANT  between calls every ring is left-aligned, exactly as stream_step leaves it: row r of a ring whose
+//                segment runs at lag_before holds frame pos[b] - lag_before - 2*H + r, for r in [0, 2*H).
+//     SHARED     stream_step keeps that invariant too, so a server may switch between the two calls on one state.
+//
+// A tick writes a slot's n new frames behind the kept 2*H, zero-fills rows [2*H + n, 2*H + hop) and runs every segment
+// over its usual window of 2*H + hop rows with the usual pos.  Row H + i of a segment's result depends on window rows
+// <= 2*H + i only, so rows [H, H + n) are exact; the rows behind them are computed from zeros -- finite, whatever the
+// scratch held -- and never handed on.  A hand-off appends those n rows (and the zero fill) to the next ring, the slides
+// move a slot's kept part by n rows, the delivery takes the FIRST n of the hop central rows, and pos[b] += n.  A
+// sequence is never shortened through lens to skip the unused rows: a conv zero-pads at a sequence end, which would
+// change the rows within H of it.  The one legitimate empty sequence is an idle slot's: with n == 0 the segments see
+// len_eff = 0 and pos_eff >= every segment's off, so its tiles return at once, and no copy touches its rings, its scratch
+// rows or its pos; only its row of `out` is written (zeros).
+// With every n == hop: pos_eff = pos, len_eff = lens, every copy moves what stream_step's moves, and out and the bytes
+// of the rings a later call can read are stream_step's bit for bit.
+// All data movement is the backend's copy_counted (qvc_kernels.h: CountedDesc / CountedHead), queued as CopyQueue
+// queues copy_batch: the same 5 + n_flows launches as a step.
+// Backend adds:  static constexpr bool kStreamTick = true  with  int copy_counted(const CountedHead&, const CountedDesc*, int n);
+//                -- one that does not say so gets QVC_ERR_BAD_CONFIG.
+template <class B, class = void> constexpr bool stream_tick_backend = false;
+template <class B> constexpr bool stream_tick_backend<B, std::void_t<decltype(B::kStreamTick)>> = B::kStreamTick;
+
+// CopyQueue's counted sibling.  `head` carries the counts; book() adds the tick's bookkeeping to the NEXT launch.
+template <class Backend>
+struct CountedQueue {
+  Backend& be;
+  CountedHead head;                  // n_new, slots, hop: every launch; the rest is set by book() and cleared by flush()
+  int st = QVC_OK;
+  CountedDesc cd[kCopyBatchMax];
+  int n = 0;
+  CountedQueue(Backend& b, const int32_t* n_new, int B, int hop) : be(b) { head.n_new = n_new; head.slots = B; head.hop = hop; }
+  void ok(int rc) { if (st == QVC_OK && rc != QVC_OK) st = rc; }
+  void flush() {
+    if (n) ok(be.copy_counted(head, cd, n));
+    n = 0;
+    head.pos = head.lens = nullptr; head.pos_eff = head.len_eff = head.pos_add = nullptr;
+  }
+  // per slot `rows` rows: `fixed + n * unit` bytes from src (read from byte n * shift of the row on), zeros up to width
+  void add(void* dst, size_t dpitch, const void* src, size_t spitch, size_t fixed, size_t unit, size_t shift, size_t width, size_t rows,
+           uint32_t flags = 0) {
+    if (n == kCopyBatchMax) flush();
+    if ((dpitch | spitch | fixed | unit | shift | width | rows) >> 32) { ok(QVC_ERR_BAD_ARG); return; }
+    cd[n++] = CountedDesc{dst, src, (uint32_t)dpitch, (uint32_t)spitch, (uint32_t)fixed, (uint32_t)unit, (uint32_t)shift, (uint32_t)width,
+                          (uint32_t)rows, flags};
+  }
+  // n frames of `frame` bytes each from the front of a source row, then zeros up to hop frames
+  void fresh(void* dst, size_t dpitch, const void* src, size_t spitch, size_t frame, size_t rows, uint32_t flags = 0) {
+    add(dst, dpitch, src, spitch, 0, frame, 0, (size_t)head.hop * frame, rows, flags);
+  }
+  // a ring's new frames of this tick behind its kept ones (one frame of a ring row: hopb / hop bytes)
+  void append(char* state, const Ring& r, const void* src) {
+    fresh(state + r.off + r.keep, (size_t)(r.keep + r.hopb), src, (size_t)r.hopb, (size_t)(r.hopb / head.hop), (size_t)r.rows);
+  }
+  // the kept parts out to the slide buffers -- from n frames into the row on -- and back in (two launches, as CopyQueue's)
+  void slide_out(char* state, char* ws, const Rings& R, const int64_t* tmp) {
+    for (int i = 0; i < R.n; ++i) add(ws + tmp[i], (size_t)R.r[i].keep, state + R.r[i].off, (size_t)(R.r[i].keep + R.r[i].hopb), (size_t)R.r[i].keep, 0,
+                                      (size_t)(R.r[i].hopb / head.hop), (size_t)R.r[i].keep, (size_t)R.r[i].rows);
+  }
+  void slide_back(char* state, char* ws, const Rings& R, const int64_t* tmp) {
+    for (int i = 0; i < R.n; ++i) add(state + R.r[i].off, (size_t)(R.r[i].keep + R.r[i].hopb), ws + tmp[i], (size_t)R.r[i].keep, (size_t)R.r[i].keep, 0, 0,
+                                      (size_t)R.r[i].keep, (size_t)R.r[i].rows);
+  }
+};
+
+// One tick.  State as stream_step's; scratch carved with tick = true.  Arguments as stream_step's, except:
+//   unit_new  columns [0, n) of row b are frames [pos[b], pos[b] + n); columns [n, hop) are never read
+//   noise_new the same rule: the draw for frames [pos - He, pos - He + n)
+//   out       the first n * spf samples of row b: frames [pos - lag, pos - lag + n), zeros outside [0, lens[b]); then zeros
+//   n_new     (B,) int32 in the backend's memory, clamped to [0, hop] there; pos is advanced by n there too
+template <class Backend>
+int stream_tick(const Plan& P, const char* blob, char* state, char* ws, const float* unit_new, const float* g,
+                const float* noise_new, float* out, int B, int hop, const int32_t* n_new, int32_t* pos, const int32_t* lens,
+                Backend& be, const NoiseRng* rng = nullptr) {
+  if constexpr (stream_tick_backend<Backend>) {
+    const StreamGeom G = stream_geom(P, hop);
+    if (G.status != QVC_OK) return G.status;
+    const StreamState S = carve_stream_state(P, G, B);
+    const StreamScratch X = carve_stream_scratch(P, G, B, true);
+    const qvc_config& c = P.cfg;
+    const int C = c.inter_channels;
+    const int h = hop, He = G.He, Hf = G.Hf, Hd1 = G.Hd1, Hd2 = G.Hd2;
+    int32_t* pos_eff = reinterpret_cast<int32_t*>(ws + X.pos_eff);
+    int32_t* len_eff = reinterpret_cast<int32_t*>(ws + X.len_eff);
+    CountedQueue<Backend> q(be, n_new, B, h);
+    const Segments<Backend> seg{P, blob, ws, B, h, pos_eff, len_eff, be};
+    const size_t zrow = (size_t)C * 4;                               // one frame of z
+    const int Tf = 2 * Hf + h;
+    // a segment's central rows (from `src` on, frame pitch zrow, `srcT` frames per stream) to coupling layer k: the n
+    // exact ones into its ring's tail AND -- together with the ring's kept part -- into the work copy the layer updates
+    auto feed_flow = [&](int k, const char* src, int srcT) {
+      char* ring = state + S.zf[k];
+      char* zw = ws + X.zwork[k & 1];
+      q.fresh(ring + (size_t)2 * Hf * zrow, (size_t)Tf * zrow, src, (size_t)srcT * zrow, zrow, 1);
+      q.add(zw, (size_t)Tf * zrow, ring, (size_t)Tf * zrow, (size_t)2 * Hf * zrow, 0, 0, (size_t)2 * Hf * zrow, 1);
+      q.fresh(zw + (size_t)2 * Hf * zrow, (size_t)Tf * zrow, src, (size_t)srcT * zrow, zrow, 1);
+      q.flush();
+    };
+    auto feed_dec = [&](const char* src, int srcT) {
+      q.fresh(state + S.zd + (size_t)2 * Hd1 * zrow, (size_t)(2 * Hd1 + h) * zrow, src, (size_t)srcT * zrow, zrow, 1);
+      q.flush();
+    };
+
+    {   // the conditioning table, as stream_step
+      Path<Backend> p = seg.make(Tf);
+      p.cond_table(g);
+      q.ok(p.status);
+    }
+    // ---- E: enc_p over the unit ring.  The launch that appends also writes pos_eff / len_eff, in front of every
+    //      launch that reads them (the conditioning table reads neither).
+    {
+      const int T = 2 * He + h;
+      char* ring = state + S.unit;
+      char* nz = ws + X.noise;                                       // zeros either side of the tick's noise
+      q.head.pos = pos; q.head.lens = lens; q.head.pos_eff = pos_eff; q.head.len_eff = len_eff;
+      q.head.idle_pos = G.lag() + G.max_window();
+      q.append(state, S.rings.r[0], unit_new);
+      if (noise_new) {
+        q.add(nz, (size_t)T * 4, nullptr, 0, 0, 0, 0, (size_t)He * 4, (size_t)C);
+        q.add(nz + (size_t)He * 4, (size_t)T * 4, noise_new, (size_t)h * 4, 0, 4, 0, (size_t)(h + He) * 4, (size_t)C);
+      }
+      q.flush();
+      Path<Backend> p = seg.make(T);
+      if (!noise_new && rng) p.rng = *rng;     // (neither: enc_p refuses)
+      p.enc_p(reinterpret_cast<const float*>(ring), noise_new ? reinterpret_cast<const float*>(nz) : nullptr, p.template wsp<float>(p.W.z));
+      q.ok(p.status);
+      if (G.nf > 0) feed_flow(0, ws + p.W.z + (size_t)He * zrow, T);
+      else feed_dec(ws + p.W.z + (size_t)He * zrow, T);
+    }
+    // ---- F_k: one coupling layer per segment, in place on a copy of its ring
+    for (int k = 0; k < G.nf; ++k) {
+      char* zw = ws + X.zwork[k & 1];
+      Path<Backend> p = seg.make(Tf, He + k * Hf);
+      p.flow_step(P.flow[(size_t)k], reinterpret_cast<float*>(zw), -1.f);
+      q.ok(p.status);
+      if (k + 1 < G.nf) feed_flow(k + 1, zw + (size_t)Hf * zrow, Tf);
+      else feed_dec(zw + (size_t)Hf * zrow, Tf);
+    }
+    // ---- D1: conv_pre + stage 0; its three ResBlock outputs feed the stage-0 rings
+    const int ch0 = P.stages[0].ch, r0 = G.r0;
+    {
+      const int T = 2 * Hd1 + h;
+      Path<Backend> p = seg.make(T, He + G.nf * Hf);
+      p.dec_front(reinterpret_cast<const float*>(state + S.zd));
+      q.ok(p.status);
+      const size_t row = (size_t)ch0 * 2;
+      for (int j = 0; j < 3; ++j) {
+        const int jj = j < c.n_resblocks ? j : 0;
+        q.fresh(state + S.s0[j] + (size_t)2 * Hd2 * r0 * row, (size_t)(2 * Hd2 + h) * r0 * row,
+                ws + p.W.ra[0][(size_t)jj] + (size_t)Hd1 * r0 * row, (size_t)T * r0 * row, (size_t)r0 * row, 1);
+      }
+      q.flush();
+    }
+    // ---- D2: the rest of the decoder; the first n of the central hop frames are the tick's output
+    {
+      const int T = 2 * Hd2 + h;
+      const size_t spf = (size_t)samples_per_frame(P);
+      Path<Backend> p = seg.make(T, He + G.nf * Hf + Hd1);
+      for (int j = 0; j < 3; ++j) p.s0_override[j] = state + S.s0[j];
+      p.dec_back_wave(p.template wsp<float>(p.W.post), reinterpret_cast<float*>(ws + X.wave));
+      q.ok(p.status);
+      q.fresh(out, (size_t)h * spf * 4, ws + X.wave + (size_t)Hd2 * spf * 4, (size_t)T * spf * 4, spf * 4, 1, kCountedIdleZero);
+    }
+    // ---- slide every ring by the slot's n frames: kept parts out (in the launch that also delivers the output and
+    //      advances pos: no launch reads pos after the first), then back in
+    q.head.pos_add = pos;
+    q.slide_out(state, ws, S.rings, X.tmp);
+    q.flush();
+    q.slide_back(state, ws, S.rings, X.tmp);
+    q.flush();
+    return q.st;
+  } else {
+    return QVC_ERR_BAD_CONFIG;
+  }
 }
 
 // ---------------------------------------------------------------- windowed step with a bounded look-ahead (live_step)

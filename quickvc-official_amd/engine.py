@@ -269,8 +269,8 @@ class QvcEngine:
         return out
 
     # ---- streaming: the segment rings (qvc_stream_*), the windowed step with a bounded look-ahead (qvc_live_*: every
-    #      decoder, the lag is the caller's choice) and its tick form (qvc_live_tick*: per-slot frame counts on the
-    #      device).  Sizes, one step and the per-slot reset of each; the state / workspace tensors belong to the caller.
+    #      decoder, the lag is the caller's choice) and the tick forms of both (qvc_stream_tick*, qvc_live_tick*: per-slot
+    #      frame counts on the device).  Sizes, one step and the per-slot reset of each; the state / workspace tensors belong to the caller.
     def _stream_sizes(self, form: str, queries, *args):
         """The values of lib.qvc_<query>(cfg, ...) -- the byte queries with ``args``, the frame queries without."""
         cfg = ctypes.byref(self.cfg)
@@ -318,6 +318,23 @@ class QvcEngine:
                           lens: torch.Tensor) -> None:
         """qvc_stream_reset_slot: zero slot `slot`'s ring rows, pos[slot] = 0, lens[slot] = length (on the current stream)."""
         self._stream_reset_slot("stream", state, batch, (hop,), slot, length, pos, lens)
+
+    def stream_tick_sizes(self, batch: int, hop: int):
+        """(state_bytes, workspace_bytes, lag_frames, noise_lag_frames) for `batch` streams that bring AT MOST `hop` frames
+        per tick (qvc_stream_tick): stream_step's state, a larger workspace."""
+        return self._stream_sizes("stream_tick", ("stream_state_bytes", "stream_tick_workspace_bytes", "stream_lag_frames",
+                                                  "stream_noise_lag_frames"), batch, hop)
+
+    @_on_device
+    def stream_tick(self, state: torch.Tensor, ws: torch.Tensor, unit_new: torch.Tensor, g: torch.Tensor, noise_new: Optional[torch.Tensor],
+                    out: torch.Tensor, n_new: torch.Tensor, pos: torch.Tensor, lens: torch.Tensor, rng=None) -> None:
+        """One tick of the segment rings (all tensors fp32 / int32, contiguous, on this device; see include/qvc.h): slot b
+        brings clamp(n_new[b], 0, hop) frames in the first columns of its row of ``unit_new`` (B, unit_channels, hop);
+        `out` receives that many frames from pos - lag on, then zeros; ``pos`` is advanced on the device.  The state is
+        stream_step's (started with stream_reset_slot); the two calls may alternate on it."""
+        if n_new.dtype != torch.int32 or n_new.device != self.device or n_new.numel() != unit_new.shape[0]:
+            raise ValueError("stream_tick needs n_new as an int32 tensor of one count per slot on the engine's device")
+        self._stream_call("stream_tick", state, ws, unit_new, g, noise_new, out, (unit_new.shape[2],), (n_new, pos, lens), rng)
 
     def live_sizes(self, batch: int, hop: int, look_ahead: int):
         """(state_bytes, workspace_bytes, context_frames) for `batch` streams fed `hop` frames per step whose output lags

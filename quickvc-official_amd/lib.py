@@ -189,6 +189,16 @@ def declare(lib: ctypes.CDLL, prefix: str = "qvc") -> None:
         fn = getattr(lib, prefix + stem + "_reset_slot")
         fn.restype = ctypes.c_int
         fn.argtypes = [cfgp, V, L, I] + [I] * ints + [I, I, V, V, V]
+    # the tick form of the segment rings (qvc_stream_tick*): qvc_stream_step's state, size query and reset, so only a
+    # workspace query and the two calls of its own -- a step's signature with n_new_dev in front of pos_dev
+    if hasattr(lib, prefix + "_stream_tick_workspace_bytes"):
+        fn = getattr(lib, prefix + "_stream_tick_workspace_bytes")
+        fn.restype = L
+        fn.argtypes = [cfgp, I, I]
+        for name, draw in (("_stream_tick", V), ("_stream_tick_rng", P(QvcNoiseRng))):
+            fn = getattr(lib, prefix + name)
+            fn.restype = ctypes.c_int
+            fn.argtypes = [cfgp, V, V, L, V, V, draw, V, I, I, V, V, V, V, L, V]
     for name in ("_stream_lag_frames", "_stream_noise_lag_frames", "_live_context_frames"):
         if hasattr(lib, prefix + name):
             fn = getattr(lib, prefix + name)

@@ -317,6 +317,56 @@ class StreamConverter:
         return out
 
 
+class StreamTickConverter(StreamConverter):
+    """StreamConverter for streams that tick on their own (qvc_stream_tick): per call, slot ``b`` brings ``n_new[b]``
+    frames, ``0 <= n_new[b] <= hop_frames`` -- nothing when its packet is late, several packets when it catches up, a
+    short last chunk.  ``hop_frames`` is the MOST a slot may bring per tick; it sizes the buffers.  StreamConverter's
+    lifecycle, lag and noise lag, and one graph replay per tick: the counts travel in a device tensor the captured call
+    reads, the positions advance on the device by the clamped counts and the host mirror follows them.  A slot that
+    brings nothing leaves no trace.  The segment rings are exact, so a stream's concatenated output is its
+    whole-utterance conversion however it was cut into ticks.  ``step`` is the tick in which every slot brings
+    ``hop_frames`` frames: bit for bit StreamConverter's."""
+
+    def _sizes(self):
+        n_state, n_ws, self.lag, self.noise_lag = self.engine.stream_tick_sizes(self.streams, self.hop)
+        # the counts of the tick in flight (the captured call holds this tensor's pointer); zeros: the warm-up and capture
+        # ticks of the constructor move nothing
+        self._n = torch.zeros(self.streams, dtype=torch.int32, device=self.engine.device)
+        return n_state, n_ws
+
+    def _one_step(self, rng: bool = False):
+        noise, draw = (None, (self._rng[0], self._keys, self._rng[1])) if rng else (self._noise, None)
+        self.engine.stream_tick(self._state, self._ws, self._unit, self._g, noise, self._out, self._n, self._pos, self._len,
+                                rng=draw)                                 # advances self._pos itself
+
+    @torch.no_grad()
+    def tick(self, unit_new: torch.Tensor, n_new, noise_new: Optional[torch.Tensor] = None):
+        """unit_new (S, 256, hop): columns [0, n_new[b]) of row b are frames [pos, pos + n_new[b]) of slot b, the rest is
+        never read; ``n_new``: a sequence of ints or a CPU int32 tensor of length S (clamped to [0, hop] on the device);
+        ``noise_new`` (S, inter, hop): the draw for frames [pos - noise_lag, ... + n_new[b]), or None for the generator form.
+        -> (out, n): out (S, hop * samples_per_frame) with row b valid in [:n[b] * samples_per_frame] -- frames
+        [pos - lag, pos - lag + n[b]) -- and zero behind it, n the clamped counts."""
+        if noise_new is None and self._rng is None:
+            raise ValueError("tick() without noise_new needs a seed (StreamTickConverter(seed=...) or set_seed)")
+        return _tick(self, unit_new, n_new, noise_new)
+
+    @torch.no_grad()
+    def step(self, unit_new: torch.Tensor, noise_new: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The tick in which every slot brings ``hop`` frames (StreamConverter.step's contract and bits)."""
+        return self.tick(unit_new, [self.hop] * self.streams, noise_new)[0]
+
+
+def _tick(conv, unit_new, n_new, noise_new):
+    """What the two tick converters' ``tick`` share: the counts checked, the call issued, the host mirror advanced."""
+    counts = torch.as_tensor(n_new, dtype=torch.int32, device="cpu").reshape(-1)
+    if counts.numel() != conv.streams:
+        raise ValueError(f"{conv.streams} slots need {conv.streams} counts, got {counts.numel()}")
+    out = conv._issue(unit_new, noise_new, counts)
+    n = [min(max(int(v), 0), conv.hop) for v in counts.tolist()]
+    conv._pos_host = [p + k for p, k in zip(conv._pos_host, n)]
+    return out, n
+
+
 class LiveConverter(StreamConverter):
     """Streaming with a bounded look-ahead, for EVERY decoder (qvc_live_step).  StreamConverter's surface -- ``start`` /
     ``end_slot`` / ``finished`` / ``position`` / ``reset`` / ``end`` / ``set_seed`` / ``step`` / ``convert``, one graph
@@ -389,13 +439,7 @@ class TickConverter(LiveConverter):
         n the clamped counts."""
         if noise_new is None and self._rng is None:
             raise ValueError("tick() without noise_new needs a seed (TickConverter(seed=...) or set_seed)")
-        counts = torch.as_tensor(n_new, dtype=torch.int32, device="cpu").reshape(-1)
-        if counts.numel() != self.streams:
-            raise ValueError(f"{self.streams} slots need {self.streams} counts, got {counts.numel()}")
-        out = self._issue(unit_new, noise_new, counts)
-        n = [min(max(int(v), 0), self.hop) for v in counts.tolist()]
-        self._pos_host = [p + k for p, k in zip(self._pos_host, n)]
-        return out, n
+        return _tick(self, unit_new, n_new, noise_new)
 
     @torch.no_grad()
     def step(self, unit_new: torch.Tensor, noise_new: Optional[torch.Tensor] = None) -> torch.Tensor:

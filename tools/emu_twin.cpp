@@ -1,4 +1,4 @@
-// emu_twin.cpp -- TEST INFRASTRUCTURE: the CPU twin of qvc_live_step and qvc_live_tick.
+// emu_twin.cpp -- TEST INFRASTRUCTURE: the CPU twin of qvc_live_step, qvc_live_tick and qvc_stream_tick.
 //
 // The host emulation under oracle/ is frozen, and its backend sits in an unnamed namespace of oracle/qvc_emu.cpp, so this
 // translation unit includes that file.  The frozen EmuBackend does not state kLiveTick; TickEmuBackend derives from it,
@@ -6,7 +6,8 @@
 // tick_rings_kernel, tick_deliver_kernel).  CountingBackend derives from that and counts the launches that move data
 // (copy_batch, tick_rings, tick_deliver): live_step, live_tick and stream_step (csrc/qvc_stream.h) are instantiated on
 // it, so a host test can pin how a step groups its copies into launches.  Built by build.py into
-// oracle/_build/libqvc_emu_twin.so and loaded only by the host tests.  The emulation's backend has no single-band tail
+// oracle/_build/libqvc_emu_twin.so and loaded only by the tests.  The same backend states kStreamTick and adds the host
+// version of the count-aware batched copy (csrc/qvc_small.hip: copy_counted_kernel), on which stream_tick is instantiated.  The emulation's backend has no single-band tail
 // and no generator form of the noise: band-synthesis decoders, pointer form only.
 #include "../oracle/qvc_emu.cpp"
 
@@ -51,15 +52,49 @@ struct TickEmuBackend : EmuBackend {
     }
     return QVC_OK;
   }
+  // csrc/qvc_small.hip copy_counted_kernel: the bookkeeping, then every descriptor slot by slot
+  static constexpr bool kStreamTick = true;
+  int copy_counted(const qvc::CountedHead& h, const qvc::CountedDesc* d, int n) {
+    if (n <= 0) return QVC_OK;
+    if (!d || n > qvc::kCopyBatchMax || !h.n_new || h.slots < 1 || h.hop < 1) return QVC_ERR_BAD_ARG;
+    if ((h.pos_eff != nullptr) != (h.len_eff != nullptr) || (h.pos_eff && (!h.pos || !h.lens))) return QVC_ERR_BAD_ARG;
+    for (int i = 0; i < n; ++i) {
+      const qvc::CountedDesc& c = d[i];
+      if (!c.dst || (!c.src && (c.fixed | c.unit | c.shift))) return QVC_ERR_BAD_ARG;
+      if ((uint64_t)c.fixed + (uint64_t)h.hop * c.unit > c.width || c.width > c.dpitch) return QVC_ERR_BAD_ARG;
+      if (c.src && (uint64_t)h.hop * c.shift + c.fixed + (uint64_t)h.hop * c.unit > c.spitch) return QVC_ERR_BAD_ARG;
+    }
+    for (int b = 0; b < h.slots; ++b) {
+      const int nb = qvc::tick_count(h.n_new, b, h.hop);
+      if (h.pos_eff) { h.pos_eff[b] = nb > 0 ? h.pos[b] : h.idle_pos; h.len_eff[b] = nb > 0 ? h.lens[b] : 0; }
+      if (h.pos_add && nb > 0) h.pos_add[b] += nb;
+    }
+    for (int i = 0; i < n; ++i) {
+      const qvc::CountedDesc& c = d[i];
+      for (int b = 0; b < h.slots; ++b) {
+        const size_t nb = (size_t)qvc::tick_count(h.n_new, b, h.hop);
+        if (nb == 0 && !(c.flags & qvc::kCountedIdleZero)) continue;
+        const size_t valid = nb == 0 ? 0 : c.fixed + nb * c.unit;
+        for (size_t r = 0; r < c.rows; ++r) {
+          char* dst = static_cast<char*>(c.dst) + ((size_t)b * c.rows + r) * c.dpitch;
+          if (valid) std::memcpy(dst, static_cast<const char*>(c.src) + ((size_t)b * c.rows + r) * c.spitch + nb * c.shift, valid);
+          std::memset(dst + valid, 0, c.width - valid);
+        }
+      }
+    }
+    return QVC_OK;
+  }
 };
 
 // calls of copy_batch, descriptors in them, calls of tick_rings, calls of tick_deliver -- since qvc_emu_twin_counts
 int64_t g_counts[4] = {0, 0, 0, 0};
+int64_t g_counted[2] = {0, 0};      // calls of copy_counted, descriptors in them -- since qvc_emu_stream_tick_counts
 
 struct CountingBackend : TickEmuBackend {
   int copy_batch(const qvc::CopyDesc* d, int n) { ++g_counts[0]; g_counts[1] += n; return TickEmuBackend::copy_batch(d, n); }
   int tick_rings(const qvc::TickRingsArgs& a) { ++g_counts[2]; return TickEmuBackend::tick_rings(a); }
   int tick_deliver(const qvc::TickDeliverArgs& a) { ++g_counts[3]; return TickEmuBackend::tick_deliver(a); }
+  int copy_counted(const qvc::CountedHead& h, const qvc::CountedDesc* d, int n) { ++g_counted[0]; g_counted[1] += n; return TickEmuBackend::copy_counted(h, d, n); }
 };
 
 bool g_trim = true;
@@ -158,6 +193,64 @@ int qvc_emu_twin_stream_step(const qvc_config* cfg, const void* blob, void* stat
   CountingBackend be;
   return qvc::stream_step(P, static_cast<const char*>(blob), static_cast<char*>(state), static_cast<char*>(workspace), unit_new, g,
                           noise_new, out, batch, hop, pos, lens, be);
+}
+
+// Same signature as qvc_stream_tick, host pointers, no stream.
+int qvc_emu_stream_tick(const qvc_config* cfg, const void* blob, void* state, int64_t state_bytes, const float* unit_new,
+                        const float* g, const float* noise_new, float* out, int32_t batch, int32_t hop, const int32_t* n_new,
+                        int32_t* pos, const int32_t* lens, void* workspace, int64_t workspace_bytes) {
+  qvc::Plan P; qvc::StreamGeom G;
+  const int st = qvc::stream_checks(blob && state && unit_new && g && noise_new && out && n_new && pos && lens && workspace, batch, state_bytes,
+                                    workspace_bytes, [&](qvc::StreamBytes& b) {
+    const int gs = qvc::stream_plan(cfg, hop, P, G);
+    if (gs == QVC_OK) b = {qvc::carve_stream_state(P, G, batch).bytes, qvc::carve_stream_scratch(P, G, batch, true).bytes};
+    return gs;
+  });
+  if (st != QVC_OK) return st;
+  CountingBackend be;
+  return qvc::stream_tick(P, static_cast<const char*>(blob), static_cast<char*>(state), static_cast<char*>(workspace), unit_new, g,
+                          noise_new, out, batch, hop, n_new, pos, lens, be);
+}
+
+// The frozen backend, which does not state kStreamTick, through the same driver: what a backend without the hook gets.
+int qvc_emu_stream_tick_frozen(const qvc_config* cfg, int32_t batch, int32_t hop) {
+  qvc::Plan P; qvc::StreamGeom G;
+  const int gs = qvc::stream_plan(cfg, hop, P, G);
+  if (gs != QVC_OK) return gs;
+  EmuBackend be;
+  return qvc::stream_tick(P, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, batch, hop, nullptr, nullptr, nullptr, be);
+}
+
+// Same signature as qvc_stream_reset_slot, host pointers, no stream.
+int qvc_emu_stream_reset_slot(const qvc_config* cfg, void* state, int64_t state_bytes, int32_t batch, int32_t hop, int32_t slot,
+                              int32_t length, int32_t* pos, int32_t* lens) {
+  const int st = qvc::reset_slot(state, state_bytes, batch, slot, length, pos, lens, [&](qvc::Rings& R) {
+    qvc::Plan P; qvc::StreamGeom G;
+    const int gs = qvc::stream_plan(cfg, hop, P, G);
+    if (gs == QVC_OK) R = qvc::stream_rings(P, G, batch);
+    return gs;
+  }, [](char* p, size_t n) { std::memset(p, 0, n); });
+  if (st == QVC_OK) { pos[slot] = 0; lens[slot] = length; }
+  return st;
+}
+
+// Ring `ring` of the segment rings' table for slot `slot`: v = {offset of the slot's rows in the state, their bytes
+// (slot_range), rows per slot, kept bytes per row, new bytes per row}.  ring >= the table's size: QVC_ERR_BAD_ARG.
+int qvc_emu_stream_ring(const qvc_config* cfg, int32_t batch, int32_t hop, int32_t slot, int32_t ring, int64_t* v) {
+  if (!v || batch <= 0 || slot < 0 || slot >= batch || ring < 0) return QVC_ERR_BAD_ARG;
+  qvc::Plan P; qvc::StreamGeom G;
+  const int gs = qvc::stream_plan(cfg, hop, P, G);
+  if (gs != QVC_OK) return gs;
+  const qvc::Rings R = qvc::stream_rings(P, G, batch);
+  if (ring >= R.n) return QVC_ERR_BAD_ARG;
+  const qvc::ByteRange s = qvc::slot_range(R.r[ring], slot);
+  v[0] = s.off; v[1] = s.bytes; v[2] = R.r[ring].rows; v[3] = R.r[ring].keep; v[4] = R.r[ring].hopb;
+  return QVC_OK;
+}
+
+// counts[2] = calls of copy_counted, descriptors in them since the last call of this function; the counts are cleared.
+void qvc_emu_stream_tick_counts(int64_t* counts) {
+  for (int i = 0; i < 2; ++i) { if (counts) counts[i] = g_counted[i]; g_counted[i] = 0; }
 }
 
 // counts[4] = calls of copy_batch, descriptors in them, calls of tick_rings, calls of tick_deliver since the last call

@@ -10,7 +10,9 @@ TickConverter -- the tick form, qvc_live_tick -- with every slot bringing hop fr
 per tick, and with uniform random counts in [0, hop]; alternating rounds of one process, medians.  The counts of a tick are
 copied into the converter's count tensor on the device in front of every replay (inside the timed region, for all three
 tick rows).
-usage: python tools/stream_bench.py [--live L[,L...]] [--ticks] [streams] [hop_frames ...]"""
+With --ring-ticks, ONLY (f): per hop the lockstep StreamConverter.step -- the yardstick -- against StreamTickConverter --
+the tick form of the segment rings, qvc_stream_tick -- under the same three patterns, timed the same way.
+usage: python tools/stream_bench.py [--live L[,L...]] [--ticks | --ring-ticks] [streams] [hop_frames ...]"""
 import json
 import os
 import random
@@ -22,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import quickvc_official_amd as q  # noqa: E402
 from quickvc_official_amd.lib import debug_set  # noqa: E402
-from quickvc_official_amd.streaming import ChunkedConverter, LiveConverter, StreamConverter, TickConverter  # noqa: E402
+from quickvc_official_amd.streaming import ChunkedConverter, LiveConverter, StreamConverter, StreamTickConverter, TickConverter  # noqa: E402
 from quickvc_official_amd.synth import make_synthetic_inputs, make_synthetic_state_dict  # noqa: E402
 
 
@@ -66,36 +68,73 @@ def live_rows(model, streams, hop, looks, rounds=5):
     return out
 
 
-def timed_ticks(conv, counts, n=20):
-    """ms per tick of a TickConverter: `counts` (12 + n, streams) int32 on the device, row i = n_new of replay i."""
+def timed_ticks(conv, counts, n=20, copy=True):
+    """ms per tick of a TickConverter: `counts` (12 + n, streams) int32 on the device, row i = n_new of replay i.
+    copy=False: the counts are written once, in front of the warm-up (a pattern that is the same at every tick)."""
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     with torch.cuda.stream(conv._stream):
         conv._unit.normal_()
         conv._noise.normal_()
         conv._g.copy_(torch.nn.functional.normalize(torch.rand_like(conv._g), dim=1))
+        conv._n.copy_(counts[0])
         for i in range(12):
-            conv._n.copy_(counts[i])
+            if copy:
+                conv._n.copy_(counts[i])
             conv._graph.replay()
         e0.record(conv._stream)
         for i in range(12, 12 + n):
-            conv._n.copy_(counts[i])
+            if copy:
+                conv._n.copy_(counts[i])
             conv._graph.replay()
         e1.record(conv._stream)
     conv._stream.synchronize()
     return e0.elapsed_time(e1) / n
 
 
-def tick_rows(model, streams, hop, looks, rounds=5, n=20):
-    """ms per step of LiveConverter (lockstep) and of TickConverter under three tick patterns, per look-ahead of `looks`,
-    alternating, median of `rounds`."""
-    context = model.engine().live_sizes(streams, hop, 0)[2]
+def tick_patterns(streams, hop, n):
+    """The three tick patterns of 12 + n replays (seeded per hop): every slot hop frames, a half of the slots idle per tick,
+    uniform counts in [0, hop] -> (the lists, the same as int32 device tensors)."""
     rnd = random.Random(1300 + hop)
     pats = {"full": [[hop] * streams for _ in range(12 + n)], "half_idle": [], "uniform": []}
     for _ in range(12 + n):
         idle = set(rnd.sample(range(streams), streams // 2))
         pats["half_idle"].append([0 if s in idle else hop for s in range(streams)])
         pats["uniform"].append([rnd.randint(0, hop) for _s in range(streams)])
-    dev_pats = {k: torch.tensor(v, dtype=torch.int32, device="cuda") for k, v in pats.items()}
+    return pats, {k: torch.tensor(v, dtype=torch.int32, device="cuda") for k, v in pats.items()}
+
+
+def ring_tick_rows(model, streams, hop, rounds=7, n=20):
+    """ms per step of StreamConverter (lockstep: the yardstick, its spread over the rounds the margin) and of
+    StreamTickConverter under the three tick patterns, alternating, median of `rounds`."""
+    pats, dev_pats = tick_patterns(streams, hop, n)
+    convs = {"lockstep": StreamConverter(model, streams, hop_frames=hop)}
+    for k in pats:
+        convs["tick_" + k] = StreamTickConverter(model, streams, hop_frames=hop)
+    convs["tick_full_counts_written_once"] = convs["tick_full"]       # the same converter without the copy of the counts per tick
+    ms = {k: [] for k in convs}
+    for _ in range(rounds):
+        for k, conv in convs.items():
+            if k == "lockstep":
+                ms[k].append(timed_replays(conv, n))
+            else:
+                once = k.endswith("_written_once")
+                ms[k].append(timed_ticks(conv, dev_pats["full" if once else k[5:]], n, copy=not once))
+    n_flows = int(model.model_config.get("n_flows", 4))
+    row = {"lag_frames": convs["lockstep"].lag,
+           "data_movement_launches": {"lockstep_step": f"{5 + n_flows} copy_batch", "tick": f"{5 + n_flows} copy_counted"},
+           "mean_frames_per_slot_and_tick": {k: sum(map(sum, v[12:])) / (n * streams) for k, v in pats.items()}}
+    for k in convs:
+        mid = sorted(ms[k])[len(ms[k]) // 2]
+        row[k] = {"ms_per_step": mid, "ms_rounds": [round(v, 4) for v in ms[k]]}
+    row["lockstep_spread_ms"] = round(max(ms["lockstep"]) - min(ms["lockstep"]), 4)
+    return row
+
+
+def tick_rows(model, streams, hop, looks, rounds=5, n=20):
+    """ms per step of LiveConverter (lockstep) and of TickConverter under three tick patterns, per look-ahead of `looks`,
+    alternating, median of `rounds`."""
+    context = model.engine().live_sizes(streams, hop, 0)[2]
+    pats, dev_pats = tick_patterns(streams, hop, n)
     out = {"context_frames": context,
            "launches_beside_the_path": {"lockstep_step": "3 copy_batch (append; deliver + rings out; rings back)",
                                         "tick": "2 (tick_rings, tick_deliver)"},
@@ -125,6 +164,9 @@ def main():
     ticks = "--ticks" in argv
     if ticks:
         argv.remove("--ticks")
+    ring_ticks = "--ring-ticks" in argv
+    if ring_ticks:
+        argv.remove("--ring-ticks")
     if "--live" in argv:
         i = argv.index("--live")
         looks = argv[i + 1].split(",")
@@ -135,6 +177,13 @@ def main():
     model.load_state_dict(make_synthetic_state_dict(model, 1234))
     model = model.cuda().eval()
     spf = model.samples_per_frame
+    if ring_ticks:
+        res = {"streams": streams, "ring_ticks": {}}
+        for hop in hops:
+            res["ring_ticks"][str(hop)] = ring_tick_rows(model, streams, hop)
+            torch.cuda.empty_cache()
+        print(json.dumps(res))
+        return
     if ticks:
         res = {"streams": streams, "ticks": {str(hop): tick_rows(model, streams, hop, looks or ["0", "8", "C"]) for hop in hops}}
         print(json.dumps(res))
