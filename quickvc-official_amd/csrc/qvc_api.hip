@@ -304,37 +304,26 @@ int run_stream(bool ptrs_ok, const float* noise_new, const qvc_noise_rng* rng, c
   return rc != QVC_OK ? rc : be.finish();
 }
 
-int stream_step_api(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
+// qvc_stream_step (tick == false: no n_new_dev, pos_dev is only read) and qvc_stream_tick (the tick's scratch; pos_dev is
+// the caller's int32_t*)
+int stream_step_api(bool tick, const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
                     const float* g, const float* noise_new, const qvc_noise_rng* rng, float* out, int32_t batch, int32_t hop,
-                    const int32_t* pos_dev, const int32_t* len_dev, void* workspace, int64_t workspace_bytes, void* stream) {
+                    const int32_t* n_new_dev, const int32_t* pos_dev, const int32_t* len_dev, void* workspace, int64_t workspace_bytes,
+                    void* stream) {
   Plan P; StreamGeom G;
-  return run_stream(unit_new && g && out && pos_dev && len_dev, noise_new, rng, blob_dev, state, state_bytes, workspace, workspace_bytes, batch, stream,
+  return run_stream(unit_new && g && out && (n_new_dev || !tick) && pos_dev && len_dev, noise_new, rng, blob_dev, state, state_bytes, workspace,
+                    workspace_bytes, batch, stream,
     [&](StreamBytes& b) {
       const int gs = stream_plan(cfg, hop, P, G);
-      if (gs == QVC_OK) b = {carve_stream_state(P, G, batch).bytes, carve_stream_scratch(P, G, batch).bytes};
+      if (gs == QVC_OK) b = {carve_stream_state(P, G, batch).bytes, carve_stream_scratch(P, G, batch, tick).bytes};
       return gs;
     },
     [&](HipBackend& be, const NoiseRng* rv) {
-      return stream_step(P, static_cast<const char*>(blob_dev), static_cast<char*>(state), static_cast<char*>(workspace), unit_new, g,
-                         noise_new, out, batch, hop, pos_dev, len_dev, be, rv);
-    });
-}
-
-// qvc_stream_tick: stream_step_api's checks plus n_new_dev, the tick's scratch, and pos_dev as the caller's int32_t*
-int stream_tick_api(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
-                    const float* g, const float* noise_new, const qvc_noise_rng* rng, float* out, int32_t batch, int32_t hop,
-                    const int32_t* n_new_dev, int32_t* pos_dev, const int32_t* len_dev, void* workspace, int64_t workspace_bytes, void* stream) {
-  Plan P; StreamGeom G;
-  return run_stream(unit_new && g && out && n_new_dev && pos_dev && len_dev, noise_new, rng, blob_dev, state, state_bytes, workspace, workspace_bytes,
-                    batch, stream,
-    [&](StreamBytes& b) {
-      const int gs = stream_plan(cfg, hop, P, G);
-      if (gs == QVC_OK) b = {carve_stream_state(P, G, batch).bytes, carve_stream_scratch(P, G, batch, true).bytes};
-      return gs;
-    },
-    [&](HipBackend& be, const NoiseRng* rv) {
-      return stream_tick(P, static_cast<const char*>(blob_dev), static_cast<char*>(state), static_cast<char*>(workspace), unit_new, g,
-                         noise_new, out, batch, hop, n_new_dev, pos_dev, len_dev, be, rv);
+      const char* blob = static_cast<const char*>(blob_dev);
+      char* st = static_cast<char*>(state);
+      char* ws = static_cast<char*>(workspace);
+      return tick ? stream_tick(P, blob, st, ws, unit_new, g, noise_new, out, batch, hop, n_new_dev, const_cast<int32_t*>(pos_dev), len_dev, be, rv)
+                  : stream_step(P, blob, st, ws, unit_new, g, noise_new, out, batch, hop, pos_dev, len_dev, be, rv);
     });
 }
 
@@ -579,7 +568,7 @@ int32_t qvc_stream_noise_lag_frames(const qvc_config* cfg) {
 int qvc_stream_step(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
                     const float* g, const float* noise_new, float* out, int32_t batch, int32_t hop, const int32_t* pos_dev,
                     const int32_t* len_dev, void* workspace, int64_t workspace_bytes, void* stream) {
-  return stream_step_api(cfg, blob_dev, state, state_bytes, unit_new, g, noise_new, nullptr, out, batch, hop, pos_dev, len_dev, workspace,
+  return stream_step_api(false, cfg, blob_dev, state, state_bytes, unit_new, g, noise_new, nullptr, out, batch, hop, nullptr, pos_dev, len_dev, workspace,
                          workspace_bytes, stream);
 }
 
@@ -587,7 +576,7 @@ int qvc_stream_step_rng(const qvc_config* cfg, const void* blob_dev, void* state
                         const float* g, const qvc_noise_rng* rng, float* out, int32_t batch, int32_t hop, const int32_t* pos_dev,
                         const int32_t* len_dev, void* workspace, int64_t workspace_bytes, void* stream) {
   if (!rng) return QVC_ERR_BAD_ARG;
-  return stream_step_api(cfg, blob_dev, state, state_bytes, unit_new, g, nullptr, rng, out, batch, hop, pos_dev, len_dev, workspace,
+  return stream_step_api(false, cfg, blob_dev, state, state_bytes, unit_new, g, nullptr, rng, out, batch, hop, nullptr, pos_dev, len_dev, workspace,
                          workspace_bytes, stream);
 }
 
@@ -610,7 +599,7 @@ int64_t qvc_stream_tick_workspace_bytes(const qvc_config* cfg, int32_t batch, in
 int qvc_stream_tick(const qvc_config* cfg, const void* blob_dev, void* state, int64_t state_bytes, const float* unit_new,
                     const float* g, const float* noise_new, float* out, int32_t batch, int32_t hop, const int32_t* n_new_dev,
                     int32_t* pos_dev, const int32_t* len_dev, void* workspace, int64_t workspace_bytes, void* stream) {
-  return stream_tick_api(cfg, blob_dev, state, state_bytes, unit_new, g, noise_new, nullptr, out, batch, hop, n_new_dev, pos_dev, len_dev,
+  return stream_step_api(true, cfg, blob_dev, state, state_bytes, unit_new, g, noise_new, nullptr, out, batch, hop, n_new_dev, pos_dev, len_dev,
                          workspace, workspace_bytes, stream);
 }
 
@@ -618,7 +607,7 @@ int qvc_stream_tick_rng(const qvc_config* cfg, const void* blob_dev, void* state
                         const float* g, const qvc_noise_rng* rng, float* out, int32_t batch, int32_t hop, const int32_t* n_new_dev,
                         int32_t* pos_dev, const int32_t* len_dev, void* workspace, int64_t workspace_bytes, void* stream) {
   if (!rng) return QVC_ERR_BAD_ARG;
-  return stream_tick_api(cfg, blob_dev, state, state_bytes, unit_new, g, nullptr, rng, out, batch, hop, n_new_dev, pos_dev, len_dev,
+  return stream_step_api(true, cfg, blob_dev, state, state_bytes, unit_new, g, nullptr, rng, out, batch, hop, n_new_dev, pos_dev, len_dev,
                          workspace, workspace_bytes, stream);
 }
 

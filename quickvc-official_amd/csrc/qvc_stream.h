@@ -21,14 +21,22 @@
 // Sequence starts and ends inside a window are exact: every kernel masks its input rows by the absolute position
 // of the window (Ragged: pos / lens), i.e. each conv zero-pads at the sequence's own ends.
 //
-// Four drivers share this file: stream_step (the segment rings above), stream_tick (stream_step with per-slot frame
-// counts, on the same state), live_step (one window over the whole path, below) and live_tick (live_step with per-slot
-// frame counts).  What they share is stated once:
+// Three bodies share this file: stream_run (the segment rings above -- stream_step and stream_tick, the step with per-slot
+// frame counts on the same state, are that ONE body on two movers), live_step (one window over the whole path, below) and
+// live_tick (live_step with per-slot frame counts).  What they share is stated once:
 //   Rings         the ring table of a driver (stream_rings / live_rings): where every ring lies in the state and its
 //                 geometry.  The state size, the slide buffers of the scratch, the slide loops and the per-slot reset
 //                 (reset_slot, slot_range) all read the table, so a ring is added or resized in ONE place.
-//   CopyQueue     the copy-descriptor queue in front of the backend's copy_batch (all data movement of a step);
-//                 CountedQueue: its sibling in front of copy_counted (all data movement of a stream_tick).
+//   movers        the queue all data movement of a call goes through: CopyQueue in front of the backend's copy_batch
+//                 (every slot moves by hop frames), CountedQueue in front of copy_counted (slot b moves by its n frames).
+//                 Both speak the same verbs, rows always PER SLOT:
+//                   fresh   a slot's new frames of this call (step: hop; tick: n, then zeros up to hop and a tail)
+//                   kept    a fixed number of bytes per row;  slid: the same, read from the slot's new frames into the row on
+//                   zeros   a zero fill
+//                   append / slide_out / slide_back   a ring's new frames behind its kept ones; the kept parts out to the
+//                           slide buffers and back in (RingMoves: written once on fresh / slid / kept)
+//                   open    the pos / lens arrays the segments' launches read;  advance: the stream positions move on
+//                   flush   what was queued since the last flush runs as ONE launch;  ok / st: the first error
 //   Segments      the factory of a step's Path segments.
 //   stream_checks the pure-host checks of an entry point (the C ABI's scaffold in qvc_api.hip and the CPU twin call it).
 #pragma once
@@ -51,8 +59,9 @@ inline int mrf_reach(const qvc_config& c) {
 // behind the first `keep` of every row and then slides the row left by hopb.
 struct Ring { int64_t off, rows, keep, hopb; };
 
+constexpr int kMaxRings = 1 + 16 + 1 + 3;   // the segment rings at the most coupling layers: unit, zf[0..16), zd, s0[0..3)
 struct Rings {          // a driver's rings in the order they lie in the state; bytes = the state's size
-  Ring r[21] = {};      // stream_step: unit, zf[0..16), zd, s0[0..3)
+  Ring r[kMaxRings] = {};
   int n = 0;
   Carver cv;
   void add(int B, int64_t rows, int64_t keep, int64_t hopb) { r[n++] = Ring{cv.take(B * rows * (keep + hopb)), rows, keep, hopb}; }
@@ -96,35 +105,112 @@ int stream_checks(bool ptrs_ok, int batch, int64_t state_bytes, int64_t ws_bytes
   return state_bytes < b.state || ws_bytes < b.ws ? QVC_ERR_SMALL_BUFFER : QVC_OK;
 }
 
-// The queue in front of the backend's  int copy_batch(const CopyDesc* d, int n)  -- n independent strided copies / zero
-// fills in one launch (qvc_kernels.h).  The descriptors between two flushes run as ONE launch and must be independent
-// of each other; st is the first error.
-template <class Backend>
-struct CopyQueue {
+// A mover's ring verbs, written once on its fresh / slid / kept (one frame of a ring row: hopb / hop bytes): a ring's
+// new frames of this call behind its kept ones; then, for the first `count` rings of R, the kept parts out to the slide
+// buffers -- from the slot's new frames into the row on -- and back in (out and back are two launches: a kept part and its
+// destination overlap).
+template <class Q>
+struct RingMoves {
+  Q& q() { return static_cast<Q&>(*this); }
+  void append(char* state, const Ring& r, const void* src) {
+    q().fresh(state + r.off + r.keep, (size_t)(r.keep + r.hopb), src, (size_t)r.hopb, (size_t)r.hopb / q().hop, (size_t)r.rows);
+  }
+  void slide_out(char* state, char* ws, const Rings& R, const int64_t* tmp, int count) {
+    for (const Ring* r = R.r; r < R.r + count; ++r, ++tmp)
+      q().slid(ws + *tmp, (size_t)r->keep, state + r->off, (size_t)(r->keep + r->hopb), (size_t)r->keep, (size_t)r->hopb / q().hop, (size_t)r->rows);
+  }
+  void slide_back(char* state, char* ws, const Rings& R, const int64_t* tmp, int count) {
+    for (const Ring* r = R.r; r < R.r + count; ++r, ++tmp)
+      q().kept(state + r->off, (size_t)(r->keep + r->hopb), ws + *tmp, (size_t)r->keep, (size_t)r->keep, (size_t)r->rows);
+  }
+};
+
+struct StreamPos { const int32_t* pos; const int32_t* lens; };   // what open() returns
+
+// The mover of a step: the queue in front of the backend's  int copy_batch(const CopyDesc* d, int n)  -- n independent
+// strided copies / zero fills in one launch (qvc_kernels.h).  The descriptors between two flushes run as ONE launch and
+// must be independent of each other; st is the first error.  Every slot moves by hop frames and every buffer is
+// batch-major, so a verb's rows per slot become B * rows rows of one descriptor.
+template <class Backend_>
+struct CopyQueue : RingMoves<CopyQueue<Backend_>> {
+  using Backend = Backend_;
+  using Pos = const int32_t;                     // the caller advances pos
+  static constexpr bool kTick = false;           // the scratch to carve
   Backend& be;
+  const size_t B, hop;
   int st = QVC_OK;
   CopyDesc cd[kCopyBatchMax];
   int n = 0;
-  explicit CopyQueue(Backend& b) : be(b) {}
+  CopyQueue(Backend& b, int slots, int hop_frames) : be(b), B((size_t)slots), hop((size_t)hop_frames) {}
   void ok(int rc) { if (st == QVC_OK && rc != QVC_OK) st = rc; }
   void flush() { if (n) ok(be.copy_batch(cd, n)); n = 0; }
-  // queue a strided copy (src == nullptr: zero fill)
+  // queue a strided copy of `rows` rows in all (src == nullptr: zero fill): the low-level call
   void add(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows) {
     if (n == kCopyBatchMax) flush();
     if ((dpitch | spitch | width | rows) >> 32) { ok(QVC_ERR_BAD_ARG); return; }
     cd[n++] = CopyDesc{dst, src, (uint32_t)dpitch, (uint32_t)spitch, (uint32_t)width, (uint32_t)rows};
   }
-  // a ring's new bytes of this step behind its kept ones; then, for the first `count` rings of R, the kept parts out to
-  // the slide buffers / back in, slid by one hop (out and back are two launches: a kept part and its destination overlap)
-  void append(char* state, const Ring& r, int B, const void* fresh) {
-    add(state + r.off + r.keep, (size_t)(r.keep + r.hopb), fresh, (size_t)r.hopb, (size_t)r.hopb, (size_t)(B * r.rows));
+  // hop frames of `frame` bytes each from the front of a source row; `tail` zero bytes behind them (a descriptor of its own)
+  void fresh(void* dst, size_t dpitch, const void* src, size_t spitch, size_t frame, size_t rows, size_t tail = 0, uint32_t = 0) {
+    add(dst, dpitch, src, spitch, hop * frame, B * rows);
+    if (tail) zeros(static_cast<char*>(dst) + hop * frame, dpitch, tail, rows);
   }
-  void slide_out(char* state, char* ws, const Rings& R, const int64_t* tmp, int count, int B) {
-    for (int i = 0; i < count; ++i) add(ws + tmp[i], (size_t)R.r[i].keep, state + R.r[i].off + R.r[i].hopb, (size_t)(R.r[i].keep + R.r[i].hopb), (size_t)R.r[i].keep, (size_t)(B * R.r[i].rows));
+  void kept(void* dst, size_t dpitch, const void* src, size_t spitch, size_t bytes, size_t rows) { add(dst, dpitch, src, spitch, bytes, B * rows); }
+  void slid(void* dst, size_t dpitch, const void* src, size_t spitch, size_t bytes, size_t frame, size_t rows) {
+    kept(dst, dpitch, static_cast<const char*>(src) + hop * frame, spitch, bytes, rows);
   }
-  void slide_back(char* state, char* ws, const Rings& R, const int64_t* tmp, int count, int B) {
-    for (int i = 0; i < count; ++i) add(state + R.r[i].off, (size_t)(R.r[i].keep + R.r[i].hopb), ws + tmp[i], (size_t)R.r[i].keep, (size_t)R.r[i].keep, (size_t)(B * R.r[i].rows));
+  void zeros(void* dst, size_t dpitch, size_t width, size_t rows) { add(dst, dpitch, nullptr, 0, width, B * rows); }
+  StreamPos open(const int32_t* pos, const int32_t* lens, int, int32_t*, int32_t*) { return {pos, lens}; }
+  void advance(const int32_t*) {}
+};
+
+// The mover of a tick: CopyQueue's sibling in front of the backend's  int copy_counted(const CountedHead&, const
+// CountedDesc*, int n)  (qvc_kernels.h).  `head` carries the counts -- slot b moves by n = clamp(n_new[b], 0, hop) frames,
+// decided on the device -- and, for ONE launch each, the tick's bookkeeping: open() and advance() set it for the next
+// flush, which clears it.
+template <class Backend_>
+struct CountedQueue : RingMoves<CountedQueue<Backend_>> {
+  using Backend = Backend_;
+  using Pos = int32_t;                           // advanced here
+  static constexpr bool kTick = true;
+  Backend& be;
+  const size_t hop;
+  CountedHead head;
+  int st = QVC_OK;
+  CountedDesc cd[kCopyBatchMax];
+  int n = 0;
+  CountedQueue(Backend& b, const int32_t* n_new, int slots, int hop_frames) : be(b), hop((size_t)hop_frames) {
+    head.n_new = n_new; head.slots = slots; head.hop = hop_frames;
   }
+  void ok(int rc) { if (st == QVC_OK && rc != QVC_OK) st = rc; }
+  void flush() {
+    if (n) ok(be.copy_counted(head, cd, n));
+    n = 0;
+    head.pos = head.lens = nullptr; head.pos_eff = head.len_eff = head.pos_add = nullptr;
+  }
+  // per slot `rows` rows: `fixed + n * unit` bytes from src (read from byte n * shift of the row on), zeros up to width
+  void add(void* dst, size_t dpitch, const void* src, size_t spitch, size_t fixed, size_t unit, size_t shift, size_t width, size_t rows,
+           uint32_t flags = 0) {
+    if (n == kCopyBatchMax) flush();
+    if ((dpitch | spitch | fixed | unit | shift | width | rows) >> 32) { ok(QVC_ERR_BAD_ARG); return; }
+    cd[n++] = CountedDesc{dst, src, (uint32_t)dpitch, (uint32_t)spitch, (uint32_t)fixed, (uint32_t)unit, (uint32_t)shift, (uint32_t)width,
+                          (uint32_t)rows, flags};
+  }
+  // n frames of `frame` bytes each from the front of a source row, then zeros up to hop frames and `tail` bytes
+  void fresh(void* dst, size_t dpitch, const void* src, size_t spitch, size_t frame, size_t rows, size_t tail = 0, uint32_t flags = 0) {
+    add(dst, dpitch, src, spitch, 0, frame, 0, hop * frame + tail, rows, flags);
+  }
+  void kept(void* dst, size_t dpitch, const void* src, size_t spitch, size_t bytes, size_t rows) { add(dst, dpitch, src, spitch, bytes, 0, 0, bytes, rows); }
+  void slid(void* dst, size_t dpitch, const void* src, size_t spitch, size_t bytes, size_t frame, size_t rows) {
+    add(dst, dpitch, src, spitch, bytes, 0, frame, bytes, rows);
+  }
+  void zeros(void* dst, size_t dpitch, size_t width, size_t rows) { add(dst, dpitch, nullptr, 0, 0, 0, 0, width, rows); }
+  // the next launch writes what the segments see: n > 0: pos[b], lens[b];  n == 0: idle_pos, 0 (an empty sequence)
+  StreamPos open(const int32_t* pos, const int32_t* lens, int idle_pos, int32_t* pos_eff, int32_t* len_eff) {
+    head.pos = pos; head.lens = lens; head.pos_eff = pos_eff; head.len_eff = len_eff; head.idle_pos = idle_pos;
+    return {pos_eff, len_eff};
+  }
+  void advance(int32_t* pos) { head.pos_add = pos; }   // the next launch: pos[b] += n
 };
 
 // A step's segments: make(T, lag_before) is a Path over the last T rows of a window whose newest `hop` rows are this
@@ -215,7 +301,7 @@ struct StreamScratch {   // carved from the END of the step's workspace, after t
   int64_t zwork[2] = {};    // fp32 [B][2*Hf + hop][C]: the coupling layer updates z in place on a copy of its ring
                             // (two of them: layer k's result feeds the copy for layer k+1 in the same launch)
   int64_t wave = 0;         // fp32 (B, spf * (2*Hd2 + hop))
-  int64_t tmp[21] = {};     // slide buffers, one per ring of the table
+  int64_t tmp[kMaxRings] = {};   // slide buffers, one per ring of the table
   int64_t pos_eff = 0, len_eff = 0;   // int32 [B] each: a tick's effective positions and lengths (tick = true only)
   int64_t bytes = 0;
 };
@@ -236,8 +322,11 @@ inline StreamScratch carve_stream_scratch(const Plan& P, const StreamGeom& G, in
   return X;
 }
 
-// One step.  All data movement of a step goes through the backend's copy_batch (CopyQueue): 5 + n_flows launches (9 at
-// the shipped config) where one memcpy per hand-off / slide would be ~35.
+// One call of the segment rings, step or tick: what moves per slot is the mover's business (Moves: CopyQueue or
+// CountedQueue), everything else -- the segments, their windows and workspace offsets, the hand-offs, the delivery, the
+// two slide launches -- is written here once.  All data movement goes through the mover: 5 + n_flows launches (9 at the
+// shipped config) where one memcpy per hand-off / slide would be ~35.  Arguments for a step (stream_tick states what a
+// tick changes):
 //   unit_new  (B, unit_channels, hop) fp32: unit frames [pos, pos + hop) of every stream
 //   noise_new (B, inter, hop) fp32:         the N(0,1) draw of models.py:94 for frames [pos - He, pos - He + hop)
 //                                           (the frames enc_p finishes in this step)
@@ -246,40 +335,41 @@ inline StreamScratch carve_stream_scratch(const Plan& P, const StreamGeom& G, in
 //   pos, lens (B,) int32 in the backend's memory: first new frame of this step / sequence length (large if unknown)
 //   rng       with noise_new == nullptr: the draw is computed in enc_p's draw site for key rng->keys[slot] at the absolute
 //             frame of every window row (Path::rng) -- no noise staging, X.noise stays untouched
-template <class Backend>
-int stream_step(const Plan& P, const char* blob, char* state, char* ws, const float* unit_new, const float* g,
-                const float* noise_new, float* out, int B, int hop, const int32_t* pos, const int32_t* lens, Backend& be,
-                const NoiseRng* rng = nullptr) {
+template <class Moves>
+int stream_run(Moves& q, const Plan& P, const char* blob, char* state, char* ws, const float* unit_new, const float* g,
+               const float* noise_new, float* out, int B, int hop, typename Moves::Pos* pos, const int32_t* lens, const NoiseRng* rng) {
+  using Backend = typename Moves::Backend;
   const StreamGeom G = stream_geom(P, hop);
   if (G.status != QVC_OK) return G.status;
   const StreamState S = carve_stream_state(P, G, B);
-  const StreamScratch X = carve_stream_scratch(P, G, B);
-  const qvc_config& c = P.cfg;
-  const int C = c.inter_channels;
+  const StreamScratch X = carve_stream_scratch(P, G, B, Moves::kTick);
+  const size_t C = (size_t)P.cfg.inter_channels;
   const int h = hop, He = G.He, Hf = G.Hf, Hd1 = G.Hd1, Hd2 = G.Hd2;
-  CopyQueue<Backend> q(be);
-  const Segments<Backend> seg{P, blob, ws, B, h, pos, lens, be};
-  // the rings slide at the END of the step, all of them in two launches.  A ring is read by exactly one segment per
-  // step, so nothing needs it slid earlier.
-  const size_t zrow = (size_t)C * 4;                               // one frame of z
+  // the positions and lengths every segment's launch reads; a tick's are written by the first launch queued below, in
+  // front of every launch that reads them (the conditioning table reads neither)
+  const StreamPos at = q.open(pos, lens, G.lag() + G.max_window(), reinterpret_cast<int32_t*>(ws + X.pos_eff), reinterpret_cast<int32_t*>(ws + X.len_eff));
+  const Segments<Backend> seg{P, blob, ws, B, h, at.pos, at.lens, q.be};
+  // the rings slide at the END of the call, all of them in two launches.  A ring is read by exactly one segment per
+  // call, so nothing needs it slid earlier.
+  const size_t zrow = C * 4;                                       // one frame of z
   const int Tf = 2 * Hf + h;
-  // hand the central hop frames of a segment's result (`src`, frame pitch zrow, `srcT` frames per stream) to coupling
+  // hand the central frames of a segment's result (from `src` on, frame pitch zrow, `srcT` frames per stream) to coupling
   // layer k: into its ring's tail AND -- together with the ring's kept part -- into the work copy the layer updates
   auto feed_flow = [&](int k, const char* src, int srcT) {
     char* ring = state + S.zf[k];
     char* zw = ws + X.zwork[k & 1];
-    q.add(ring + (size_t)2 * Hf * zrow, (size_t)Tf * zrow, src, (size_t)srcT * zrow, (size_t)h * zrow, (size_t)B);
-    q.add(zw, (size_t)Tf * zrow, ring, (size_t)Tf * zrow, (size_t)2 * Hf * zrow, (size_t)B);
-    q.add(zw + (size_t)2 * Hf * zrow, (size_t)Tf * zrow, src, (size_t)srcT * zrow, (size_t)h * zrow, (size_t)B);
+    q.fresh(ring + (size_t)2 * Hf * zrow, (size_t)Tf * zrow, src, (size_t)srcT * zrow, zrow, 1);
+    q.kept(zw, (size_t)Tf * zrow, ring, (size_t)Tf * zrow, (size_t)2 * Hf * zrow, 1);
+    q.fresh(zw + (size_t)2 * Hf * zrow, (size_t)Tf * zrow, src, (size_t)srcT * zrow, zrow, 1);
     q.flush();
   };
-  // ... or, behind the last coupling layer (or enc_p without a flow), into the tail of the decoder's ring
+  // ... or, behind the last coupling layer, into the tail of the decoder's ring
   auto feed_dec = [&](const char* src, int srcT) {
-    q.add(state + S.zd + (size_t)2 * Hd1 * zrow, (size_t)(2 * Hd1 + h) * zrow, src, (size_t)srcT * zrow, (size_t)h * zrow, (size_t)B);
+    q.fresh(state + S.zd + (size_t)2 * Hd1 * zrow, (size_t)(2 * Hd1 + h) * zrow, src, (size_t)srcT * zrow, zrow, 1);
     q.flush();
   };
 
-  {   // the conditioning table (cond rows x g) once per step: every segment's workspace keeps it at the same place
+  {   // the conditioning table (cond rows x g) once per call: every segment's workspace keeps it at the same place
     Path<Backend> p = seg.make(Tf);
     p.cond_table(g);
     q.ok(p.status);
@@ -288,20 +378,18 @@ int stream_step(const Plan& P, const char* blob, char* state, char* ws, const fl
   {
     const int T = 2 * He + h;
     char* ring = state + S.unit;
-    char* nz = ws + X.noise;                                       // zeros either side of the step's noise
-    q.append(state, S.rings.r[0], B, unit_new);
+    char* nz = ws + X.noise;                                       // zeros either side of the call's noise
+    q.append(state, S.rings.r[0], unit_new);
     if (noise_new) {
-      q.add(nz, (size_t)T * 4, nullptr, 0, (size_t)He * 4, (size_t)B * C);
-      q.add(nz + (size_t)He * 4, (size_t)T * 4, noise_new, (size_t)h * 4, (size_t)h * 4, (size_t)B * C);
-      q.add(nz + (size_t)(He + h) * 4, (size_t)T * 4, nullptr, 0, (size_t)He * 4, (size_t)B * C);
+      q.zeros(nz, (size_t)T * 4, (size_t)He * 4, C);
+      q.fresh(nz + (size_t)He * 4, (size_t)T * 4, noise_new, (size_t)h * 4, 4, C, (size_t)He * 4);
     }
     q.flush();
     Path<Backend> p = seg.make(T);
     if (!noise_new && rng) p.rng = *rng;     // (neither: enc_p refuses)
     p.enc_p(reinterpret_cast<const float*>(ring), noise_new ? reinterpret_cast<const float*>(nz) : nullptr, p.template wsp<float>(p.W.z));
     q.ok(p.status);
-    if (G.nf > 0) feed_flow(0, ws + p.W.z + (size_t)He * zrow, T);
-    else feed_dec(ws + p.W.z + (size_t)He * zrow, T);
+    feed_flow(0, ws + p.W.z + (size_t)He * zrow, T);               // (validate(): at least one coupling layer)
   }
   // ---- F_k: one coupling layer per segment, in place on a copy of its ring (its edge rows come out wrong and
   //      must not be written back: the ring has to keep the untouched values for the next step's context)
@@ -320,30 +408,40 @@ int stream_step(const Plan& P, const char* blob, char* state, char* ws, const fl
     Path<Backend> p = seg.make(T, He + G.nf * Hf);
     p.dec_front(reinterpret_cast<const float*>(state + S.zd));
     q.ok(p.status);
-    const size_t row = (size_t)ch0 * 2;
-    for (int j = 0; j < 3; ++j) {
-      const int jj = j < c.n_resblocks ? j : 0;
-      q.add(state + S.s0[j] + (size_t)2 * Hd2 * r0 * row, (size_t)(2 * Hd2 + h) * r0 * row,
-            ws + p.W.ra[0][(size_t)jj] + (size_t)Hd1 * r0 * row, (size_t)T * r0 * row, (size_t)h * r0 * row, (size_t)B);
-    }
+    const size_t row = (size_t)ch0 * 2 * r0;                         // one unit frame of a stage-0 stream
+    for (int j = 0; j < 3; ++j)                                    // (validate(): three ResBlocks)
+      q.fresh(state + S.s0[j] + (size_t)2 * Hd2 * row, (size_t)(2 * Hd2 + h) * row, ws + p.W.ra[0][(size_t)j] + (size_t)Hd1 * row,
+              (size_t)T * row, row, 1);
     q.flush();
   }
-  // ---- D2: remaining stages + conv_post + iSTFT / band synthesis; the central hop frames are the step's output
+  // ---- D2: remaining stages + conv_post + iSTFT / band synthesis; the central frames are the call's output (an idle
+  //      slot of a tick gets a row of zeros)
   {
     const int T = 2 * Hd2 + h;
-    const int spf = samples_per_frame(P);
+    const size_t spf = (size_t)samples_per_frame(P);
     Path<Backend> p = seg.make(T, He + G.nf * Hf + Hd1);
     for (int j = 0; j < 3; ++j) p.s0_override[j] = state + S.s0[j];
     p.dec_back_wave(p.template wsp<float>(p.W.post), reinterpret_cast<float*>(ws + X.wave));
     q.ok(p.status);
-    q.add(out, (size_t)h * spf * 4, ws + X.wave + (size_t)Hd2 * spf * 4, (size_t)T * spf * 4, (size_t)h * spf * 4, (size_t)B);
+    q.fresh(out, (size_t)h * spf * 4, ws + X.wave + (size_t)Hd2 * spf * 4, (size_t)T * spf * 4, spf * 4, 1, 0, kCountedIdleZero);
   }
-  // ---- slide every ring by one hop: kept parts out (in the launch that also delivers the output), then back in
-  q.slide_out(state, ws, S.rings, X.tmp, S.rings.n, B);
+  // ---- slide every ring by the slot's new frames: kept parts out (in the launch that also delivers the output and
+  //      moves the positions on: no launch reads pos after the first), then back in
+  q.advance(pos);
+  q.slide_out(state, ws, S.rings, X.tmp, S.rings.n);
   q.flush();
-  q.slide_back(state, ws, S.rings, X.tmp, S.rings.n, B);
+  q.slide_back(state, ws, S.rings, X.tmp, S.rings.n);
   q.flush();
   return q.st;
+}
+
+// One step: every slot moves by hop frames (arguments: stream_run).  pos is only read; the caller advances it.
+template <class Backend>
+int stream_step(const Plan& P, const char* blob, char* state, char* ws, const float* unit_new, const float* g,
+                const float* noise_new, float* out, int B, int hop, const int32_t* pos, const int32_t* lens, Backend& be,
+                const NoiseRng* rng = nullptr) {
+  CopyQueue<Backend> q(be, B, hop);
+  return stream_run(q, P, blob, state, ws, unit_new, g, noise_new, out, B, hop, pos, lens, rng);
 }
 
 // ---------------------------------------------------------------- the tick form of the segment rings (stream_tick)
@@ -365,54 +463,13 @@ int stream_step(const Plan& P, const char* blob, char* state, char* ws, const fl
 // rows or its pos; only its row of `out` is written (zeros).
 // With every n == hop: pos_eff = pos, len_eff = lens, every copy moves what stream_step's moves, and out and the bytes
 // of the rings a later call can read are stream_step's bit for bit.
-// All data movement is the backend's copy_counted (qvc_kernels.h: CountedDesc / CountedHead), queued as CopyQueue
-// queues copy_batch: the same 5 + n_flows launches as a step.
+// All data movement is the backend's copy_counted (qvc_kernels.h: CountedDesc / CountedHead), queued by CountedQueue
+// under the ONE body stream_step runs (stream_run): the same 5 + n_flows launches, hand-offs, appends, delivery and two
+// slide launches as a step by construction; what differs is what a verb of the mover queues.
 // Backend adds:  static constexpr bool kStreamTick = true  with  int copy_counted(const CountedHead&, const CountedDesc*, int n);
 //                -- one that does not say so gets QVC_ERR_BAD_CONFIG.
 template <class B, class = void> constexpr bool stream_tick_backend = false;
 template <class B> constexpr bool stream_tick_backend<B, std::void_t<decltype(B::kStreamTick)>> = B::kStreamTick;
-
-// CopyQueue's counted sibling.  `head` carries the counts; book() adds the tick's bookkeeping to the NEXT launch.
-template <class Backend>
-struct CountedQueue {
-  Backend& be;
-  CountedHead head;                  // n_new, slots, hop: every launch; the rest is set by book() and cleared by flush()
-  int st = QVC_OK;
-  CountedDesc cd[kCopyBatchMax];
-  int n = 0;
-  CountedQueue(Backend& b, const int32_t* n_new, int B, int hop) : be(b) { head.n_new = n_new; head.slots = B; head.hop = hop; }
-  void ok(int rc) { if (st == QVC_OK && rc != QVC_OK) st = rc; }
-  void flush() {
-    if (n) ok(be.copy_counted(head, cd, n));
-    n = 0;
-    head.pos = head.lens = nullptr; head.pos_eff = head.len_eff = head.pos_add = nullptr;
-  }
-  // per slot `rows` rows: `fixed + n * unit` bytes from src (read from byte n * shift of the row on), zeros up to width
-  void add(void* dst, size_t dpitch, const void* src, size_t spitch, size_t fixed, size_t unit, size_t shift, size_t width, size_t rows,
-           uint32_t flags = 0) {
-    if (n == kCopyBatchMax) flush();
-    if ((dpitch | spitch | fixed | unit | shift | width | rows) >> 32) { ok(QVC_ERR_BAD_ARG); return; }
-    cd[n++] = CountedDesc{dst, src, (uint32_t)dpitch, (uint32_t)spitch, (uint32_t)fixed, (uint32_t)unit, (uint32_t)shift, (uint32_t)width,
-                          (uint32_t)rows, flags};
-  }
-  // n frames of `frame` bytes each from the front of a source row, then zeros up to hop frames
-  void fresh(void* dst, size_t dpitch, const void* src, size_t spitch, size_t frame, size_t rows, uint32_t flags = 0) {
-    add(dst, dpitch, src, spitch, 0, frame, 0, (size_t)head.hop * frame, rows, flags);
-  }
-  // a ring's new frames of this tick behind its kept ones (one frame of a ring row: hopb / hop bytes)
-  void append(char* state, const Ring& r, const void* src) {
-    fresh(state + r.off + r.keep, (size_t)(r.keep + r.hopb), src, (size_t)r.hopb, (size_t)(r.hopb / head.hop), (size_t)r.rows);
-  }
-  // the kept parts out to the slide buffers -- from n frames into the row on -- and back in (two launches, as CopyQueue's)
-  void slide_out(char* state, char* ws, const Rings& R, const int64_t* tmp) {
-    for (int i = 0; i < R.n; ++i) add(ws + tmp[i], (size_t)R.r[i].keep, state + R.r[i].off, (size_t)(R.r[i].keep + R.r[i].hopb), (size_t)R.r[i].keep, 0,
-                                      (size_t)(R.r[i].hopb / head.hop), (size_t)R.r[i].keep, (size_t)R.r[i].rows);
-  }
-  void slide_back(char* state, char* ws, const Rings& R, const int64_t* tmp) {
-    for (int i = 0; i < R.n; ++i) add(state + R.r[i].off, (size_t)(R.r[i].keep + R.r[i].hopb), ws + tmp[i], (size_t)R.r[i].keep, (size_t)R.r[i].keep, 0, 0,
-                                      (size_t)R.r[i].keep, (size_t)R.r[i].rows);
-  }
-};
 
 // One tick.  State as stream_step's; scratch carved with tick = true.  Arguments as stream_step's, except:
 //   unit_new  columns [0, n) of row b are frames [pos[b], pos[b] + n); columns [n, hop) are never read
@@ -424,102 +481,8 @@ int stream_tick(const Plan& P, const char* blob, char* state, char* ws, const fl
                 const float* noise_new, float* out, int B, int hop, const int32_t* n_new, int32_t* pos, const int32_t* lens,
                 Backend& be, const NoiseRng* rng = nullptr) {
   if constexpr (stream_tick_backend<Backend>) {
-    const StreamGeom G = stream_geom(P, hop);
-    if (G.status != QVC_OK) return G.status;
-    const StreamState S = carve_stream_state(P, G, B);
-    const StreamScratch X = carve_stream_scratch(P, G, B, true);
-    const qvc_config& c = P.cfg;
-    const int C = c.inter_channels;
-    const int h = hop, He = G.He, Hf = G.Hf, Hd1 = G.Hd1, Hd2 = G.Hd2;
-    int32_t* pos_eff = reinterpret_cast<int32_t*>(ws + X.pos_eff);
-    int32_t* len_eff = reinterpret_cast<int32_t*>(ws + X.len_eff);
-    CountedQueue<Backend> q(be, n_new, B, h);
-    const Segments<Backend> seg{P, blob, ws, B, h, pos_eff, len_eff, be};
-    const size_t zrow = (size_t)C * 4;                               // one frame of z
-    const int Tf = 2 * Hf + h;
-    // a segment's central rows (from `src` on, frame pitch zrow, `srcT` frames per stream) to coupling layer k: the n
-    // exact ones into its ring's tail AND -- together with the ring's kept part -- into the work copy the layer updates
-    auto feed_flow = [&](int k, const char* src, int srcT) {
-      char* ring = state + S.zf[k];
-      char* zw = ws + X.zwork[k & 1];
-      q.fresh(ring + (size_t)2 * Hf * zrow, (size_t)Tf * zrow, src, (size_t)srcT * zrow, zrow, 1);
-      q.add(zw, (size_t)Tf * zrow, ring, (size_t)Tf * zrow, (size_t)2 * Hf * zrow, 0, 0, (size_t)2 * Hf * zrow, 1);
-      q.fresh(zw + (size_t)2 * Hf * zrow, (size_t)Tf * zrow, src, (size_t)srcT * zrow, zrow, 1);
-      q.flush();
-    };
-    auto feed_dec = [&](const char* src, int srcT) {
-      q.fresh(state + S.zd + (size_t)2 * Hd1 * zrow, (size_t)(2 * Hd1 + h) * zrow, src, (size_t)srcT * zrow, zrow, 1);
-      q.flush();
-    };
-
-    {   // the conditioning table, as stream_step
-      Path<Backend> p = seg.make(Tf);
-      p.cond_table(g);
-      q.ok(p.status);
-    }
-    // ---- E: enc_p over the unit ring.  The launch that appends also writes pos_eff / len_eff, in front of every
-    //      launch that reads them (the conditioning table reads neither).
-    {
-      const int T = 2 * He + h;
-      char* ring = state + S.unit;
-      char* nz = ws + X.noise;                                       // zeros either side of the tick's noise
-      q.head.pos = pos; q.head.lens = lens; q.head.pos_eff = pos_eff; q.head.len_eff = len_eff;
-      q.head.idle_pos = G.lag() + G.max_window();
-      q.append(state, S.rings.r[0], unit_new);
-      if (noise_new) {
-        q.add(nz, (size_t)T * 4, nullptr, 0, 0, 0, 0, (size_t)He * 4, (size_t)C);
-        q.add(nz + (size_t)He * 4, (size_t)T * 4, noise_new, (size_t)h * 4, 0, 4, 0, (size_t)(h + He) * 4, (size_t)C);
-      }
-      q.flush();
-      Path<Backend> p = seg.make(T);
-      if (!noise_new && rng) p.rng = *rng;     // (neither: enc_p refuses)
-      p.enc_p(reinterpret_cast<const float*>(ring), noise_new ? reinterpret_cast<const float*>(nz) : nullptr, p.template wsp<float>(p.W.z));
-      q.ok(p.status);
-      if (G.nf > 0) feed_flow(0, ws + p.W.z + (size_t)He * zrow, T);
-      else feed_dec(ws + p.W.z + (size_t)He * zrow, T);
-    }
-    // ---- F_k: one coupling layer per segment, in place on a copy of its ring
-    for (int k = 0; k < G.nf; ++k) {
-      char* zw = ws + X.zwork[k & 1];
-      Path<Backend> p = seg.make(Tf, He + k * Hf);
-      p.flow_step(P.flow[(size_t)k], reinterpret_cast<float*>(zw), -1.f);
-      q.ok(p.status);
-      if (k + 1 < G.nf) feed_flow(k + 1, zw + (size_t)Hf * zrow, Tf);
-      else feed_dec(zw + (size_t)Hf * zrow, Tf);
-    }
-    // ---- D1: conv_pre + stage 0; its three ResBlock outputs feed the stage-0 rings
-    const int ch0 = P.stages[0].ch, r0 = G.r0;
-    {
-      const int T = 2 * Hd1 + h;
-      Path<Backend> p = seg.make(T, He + G.nf * Hf);
-      p.dec_front(reinterpret_cast<const float*>(state + S.zd));
-      q.ok(p.status);
-      const size_t row = (size_t)ch0 * 2;
-      for (int j = 0; j < 3; ++j) {
-        const int jj = j < c.n_resblocks ? j : 0;
-        q.fresh(state + S.s0[j] + (size_t)2 * Hd2 * r0 * row, (size_t)(2 * Hd2 + h) * r0 * row,
-                ws + p.W.ra[0][(size_t)jj] + (size_t)Hd1 * r0 * row, (size_t)T * r0 * row, (size_t)r0 * row, 1);
-      }
-      q.flush();
-    }
-    // ---- D2: the rest of the decoder; the first n of the central hop frames are the tick's output
-    {
-      const int T = 2 * Hd2 + h;
-      const size_t spf = (size_t)samples_per_frame(P);
-      Path<Backend> p = seg.make(T, He + G.nf * Hf + Hd1);
-      for (int j = 0; j < 3; ++j) p.s0_override[j] = state + S.s0[j];
-      p.dec_back_wave(p.template wsp<float>(p.W.post), reinterpret_cast<float*>(ws + X.wave));
-      q.ok(p.status);
-      q.fresh(out, (size_t)h * spf * 4, ws + X.wave + (size_t)Hd2 * spf * 4, (size_t)T * spf * 4, spf * 4, 1, kCountedIdleZero);
-    }
-    // ---- slide every ring by the slot's n frames: kept parts out (in the launch that also delivers the output and
-    //      advances pos: no launch reads pos after the first), then back in
-    q.head.pos_add = pos;
-    q.slide_out(state, ws, S.rings, X.tmp);
-    q.flush();
-    q.slide_back(state, ws, S.rings, X.tmp);
-    q.flush();
-    return q.st;
+    CountedQueue<Backend> q(be, n_new, B, hop);
+    return stream_run(q, P, blob, state, ws, unit_new, g, noise_new, out, B, hop, pos, lens, rng);
   } else {
     return QVC_ERR_BAD_CONFIG;
   }
@@ -651,7 +614,7 @@ int live_window(const Plan& P, const LiveGeom& G, const LiveScratch& X, const ch
                 size_t& wave_rows, size_t& first) {
   const qvc_config& c = P.cfg;
   const size_t W = (size_t)G.W;
-  CopyQueue<Backend> q(be);                  // one strided copy per hand-off, each a launch of its own
+  CopyQueue<Backend> q(be, B, G.hop);        // one strided copy per hand-off, each a launch of its own
   const Segments<Backend> seg{P, blob, ws, B, G.hop, pos, lens, be};
   float* wave = reinterpret_cast<float*>(ws + X.wave);
   wave_rows = W; first = (size_t)G.C();
@@ -706,20 +669,20 @@ int live_step(const Plan& P, const LiveGeom& G, const char* blob, char* state, c
   const LiveScratch X = carve_live_scratch(P, G, B);
   const size_t h = (size_t)G.hop, spf = (size_t)samples_per_frame(P);
   const int nrings = noise_new ? 2 : 1;                            // the generator form leaves the noise ring alone
-  CopyQueue<Backend> q(be);
+  CopyQueue<Backend> q(be, B, G.hop);
   // ---- append the new frames behind the kept ones
-  q.append(state, S.rings.r[0], B, unit_new);
-  if (noise_new) q.append(state, S.rings.r[1], B, noise_new);
+  q.append(state, S.rings.r[0], unit_new);
+  if (noise_new) q.append(state, S.rings.r[1], noise_new);
   q.flush();
   const float* unit = reinterpret_cast<const float*>(state + S.unit);
   const float* noise = noise_new ? reinterpret_cast<const float*>(state + S.noise) : nullptr;
   size_t wave_rows = 0, first = 0;                                 // rows of X.wave, and the first delivered one
   q.ok(live_window(P, G, X, blob, ws, unit, g, noise, B, pos, lens, be, rng, trim, wave_rows, first));
   // ---- deliver rows [first, first + hop) and slide the rings by one hop: kept parts out, then back in
-  q.add(out, h * spf * 4, ws + X.wave + first * spf * 4, wave_rows * spf * 4, h * spf * 4, (size_t)B);
-  q.slide_out(state, ws, S.rings, X.tmp, nrings, B);
+  q.fresh(out, h * spf * 4, ws + X.wave + first * spf * 4, wave_rows * spf * 4, spf * 4, 1);
+  q.slide_out(state, ws, S.rings, X.tmp, nrings);
   q.flush();
-  q.slide_back(state, ws, S.rings, X.tmp, nrings, B);
+  q.slide_back(state, ws, S.rings, X.tmp, nrings);
   q.flush();
   return q.st;
 }

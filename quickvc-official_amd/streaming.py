@@ -317,7 +317,44 @@ class StreamConverter:
         return out
 
 
-class StreamTickConverter(StreamConverter):
+class _Ticks:
+    """What the two tick converters share, in front of their lockstep converter in the bases: the count tensor, the draw
+    selection of the captured call, ``tick`` and ``step``.  Per class: ``_engine_tick``, the one engine call."""
+
+    def _count_tensor(self) -> torch.Tensor:
+        """The counts of the tick in flight (the captured call holds this tensor's pointer); zeros: the warm-up and capture
+        ticks of the constructor move nothing."""
+        return torch.zeros(self.streams, dtype=torch.int32, device=self.engine.device)
+
+    def _one_step(self, rng: bool = False):
+        noise, draw = (None, (self._rng[0], self._keys, self._rng[1])) if rng else (self._noise, None)
+        self._engine_tick(noise, draw)                           # advances self._pos itself
+
+    @torch.no_grad()
+    def tick(self, unit_new: torch.Tensor, n_new, noise_new: Optional[torch.Tensor] = None):
+        """unit_new (S, 256, hop): columns [0, n_new[b]) of row b are frames [pos, pos + n_new[b]) of slot b, the rest is
+        never read; ``n_new``: a sequence of ints or a CPU int32 tensor of length S (clamped to [0, hop] on the device);
+        ``noise_new`` (S, inter, hop): the draw for frames [pos - noise_lag, ... + n_new[b]) -- the same frames where
+        ``noise_lag`` is 0 --, or None for the generator form.
+        -> (out, n): out (S, hop * samples_per_frame) with row b valid in [:n[b] * samples_per_frame] -- frames
+        [pos - lag, pos - lag + n[b]) -- and zero behind it, n the clamped counts."""
+        if noise_new is None and self._rng is None:
+            raise ValueError(f"tick() without noise_new needs a seed ({type(self).__name__}(seed=...) or set_seed)")
+        counts = torch.as_tensor(n_new, dtype=torch.int32, device="cpu").reshape(-1)
+        if counts.numel() != self.streams:
+            raise ValueError(f"{self.streams} slots need {self.streams} counts, got {counts.numel()}")
+        out = self._issue(unit_new, noise_new, counts)
+        n = [min(max(int(v), 0), self.hop) for v in counts.tolist()]
+        self._pos_host = [p + k for p, k in zip(self._pos_host, n)]     # the host mirror follows the device
+        return out, n
+
+    @torch.no_grad()
+    def step(self, unit_new: torch.Tensor, noise_new: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The tick in which every slot brings ``hop`` frames (the lockstep converter's ``step``: its contract and bits)."""
+        return self.tick(unit_new, [self.hop] * self.streams, noise_new)[0]
+
+
+class StreamTickConverter(_Ticks, StreamConverter):
     """StreamConverter for streams that tick on their own (qvc_stream_tick): per call, slot ``b`` brings ``n_new[b]``
     frames, ``0 <= n_new[b] <= hop_frames`` -- nothing when its packet is late, several packets when it catches up, a
     short last chunk.  ``hop_frames`` is the MOST a slot may bring per tick; it sizes the buffers.  StreamConverter's
@@ -329,42 +366,11 @@ class StreamTickConverter(StreamConverter):
 
     def _sizes(self):
         n_state, n_ws, self.lag, self.noise_lag = self.engine.stream_tick_sizes(self.streams, self.hop)
-        # the counts of the tick in flight (the captured call holds this tensor's pointer); zeros: the warm-up and capture
-        # ticks of the constructor move nothing
-        self._n = torch.zeros(self.streams, dtype=torch.int32, device=self.engine.device)
+        self._n = self._count_tensor()
         return n_state, n_ws
 
-    def _one_step(self, rng: bool = False):
-        noise, draw = (None, (self._rng[0], self._keys, self._rng[1])) if rng else (self._noise, None)
-        self.engine.stream_tick(self._state, self._ws, self._unit, self._g, noise, self._out, self._n, self._pos, self._len,
-                                rng=draw)                                 # advances self._pos itself
-
-    @torch.no_grad()
-    def tick(self, unit_new: torch.Tensor, n_new, noise_new: Optional[torch.Tensor] = None):
-        """unit_new (S, 256, hop): columns [0, n_new[b]) of row b are frames [pos, pos + n_new[b]) of slot b, the rest is
-        never read; ``n_new``: a sequence of ints or a CPU int32 tensor of length S (clamped to [0, hop] on the device);
-        ``noise_new`` (S, inter, hop): the draw for frames [pos - noise_lag, ... + n_new[b]), or None for the generator form.
-        -> (out, n): out (S, hop * samples_per_frame) with row b valid in [:n[b] * samples_per_frame] -- frames
-        [pos - lag, pos - lag + n[b]) -- and zero behind it, n the clamped counts."""
-        if noise_new is None and self._rng is None:
-            raise ValueError("tick() without noise_new needs a seed (StreamTickConverter(seed=...) or set_seed)")
-        return _tick(self, unit_new, n_new, noise_new)
-
-    @torch.no_grad()
-    def step(self, unit_new: torch.Tensor, noise_new: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The tick in which every slot brings ``hop`` frames (StreamConverter.step's contract and bits)."""
-        return self.tick(unit_new, [self.hop] * self.streams, noise_new)[0]
-
-
-def _tick(conv, unit_new, n_new, noise_new):
-    """What the two tick converters' ``tick`` share: the counts checked, the call issued, the host mirror advanced."""
-    counts = torch.as_tensor(n_new, dtype=torch.int32, device="cpu").reshape(-1)
-    if counts.numel() != conv.streams:
-        raise ValueError(f"{conv.streams} slots need {conv.streams} counts, got {counts.numel()}")
-    out = conv._issue(unit_new, noise_new, counts)
-    n = [min(max(int(v), 0), conv.hop) for v in counts.tolist()]
-    conv._pos_host = [p + k for p, k in zip(conv._pos_host, n)]
-    return out, n
+    def _engine_tick(self, noise, rng) -> None:
+        self.engine.stream_tick(self._state, self._ws, self._unit, self._g, noise, self._out, self._n, self._pos, self._len, rng=rng)
 
 
 class LiveConverter(StreamConverter):
@@ -397,7 +403,7 @@ class LiveConverter(StreamConverter):
         self.engine.live_reset_slot(self._state, self.streams, self.hop, self.look_ahead, slot, length, self._pos, self._len)
 
 
-class TickConverter(LiveConverter):
+class TickConverter(_Ticks, LiveConverter):
     """LiveConverter for streams that tick on their own (qvc_live_tick): per call, slot ``b`` brings ``n_new[b]`` frames,
     ``0 <= n_new[b] <= hop_frames`` -- nothing when its packet is late, several packets when it catches up, a short last
     chunk.  ``hop_frames`` is the MOST a slot may bring per tick; it sizes the buffers and the window
@@ -417,31 +423,11 @@ class TickConverter(LiveConverter):
         n_state, n_ws, self.context = self.engine.live_tick_sizes(self.streams, self.hop, self.look_ahead)
         self.window = self.context + self.look_ahead + self.hop
         self.lag, self.noise_lag = self.look_ahead, 0
-        # the counts of the tick in flight (the captured call holds this tensor's pointer); zeros: the warm-up and capture
-        # ticks of the constructor move nothing
-        self._n = torch.zeros(self.streams, dtype=torch.int32, device=self.engine.device)
+        self._n = self._count_tensor()
         return n_state, n_ws
 
-    def _one_step(self, rng: bool = False):
-        noise, draw = (None, (self._rng[0], self._keys, self._rng[1])) if rng else (self._noise, None)
-        self.engine.live_tick(self._state, self._ws, self._unit, self._g, noise, self._out, self._n, self._pos, self._len,
-                              self.look_ahead, rng=draw)                  # advances self._pos itself
+    def _engine_tick(self, noise, rng) -> None:
+        self.engine.live_tick(self._state, self._ws, self._unit, self._g, noise, self._out, self._n, self._pos, self._len, self.look_ahead, rng=rng)
 
     def _engine_reset_slot(self, slot: int, length: int) -> None:
         self.engine.live_tick_reset_slot(self._state, self.streams, self.hop, self.look_ahead, slot, length, self._pos, self._len)
-
-    @torch.no_grad()
-    def tick(self, unit_new: torch.Tensor, n_new, noise_new: Optional[torch.Tensor] = None):
-        """unit_new (S, 256, hop): columns [0, n_new[b]) of row b are frames [pos, pos + n_new[b]) of slot b, the rest is
-        never read; ``n_new``: a sequence of ints or a CPU int32 tensor of length S (clamped to [0, hop] on the device);
-        ``noise_new`` (S, inter, hop): the draw for the same frames, or None for the generator form.
-        -> (out, n): out (S, hop * samples_per_frame) with row b valid in [:n[b] * samples_per_frame] and zero behind it,
-        n the clamped counts."""
-        if noise_new is None and self._rng is None:
-            raise ValueError("tick() without noise_new needs a seed (TickConverter(seed=...) or set_seed)")
-        return _tick(self, unit_new, n_new, noise_new)
-
-    @torch.no_grad()
-    def step(self, unit_new: torch.Tensor, noise_new: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The tick in which every slot brings ``hop`` frames (LiveConverter.step's contract and bits)."""
-        return self.tick(unit_new, [self.hop] * self.streams, noise_new)[0]

@@ -7,9 +7,13 @@
 // (copy_batch, tick_rings, tick_deliver): live_step, live_tick and stream_step (csrc/qvc_stream.h) are instantiated on
 // it, so a host test can pin how a step groups its copies into launches.  Built by build.py into
 // oracle/_build/libqvc_emu_twin.so and loaded only by the tests.  The same backend states kStreamTick and adds the host
-// version of the count-aware batched copy (csrc/qvc_small.hip: copy_counted_kernel), on which stream_tick is instantiated.  The emulation's backend has no single-band tail
-// and no generator form of the noise: band-synthesis decoders, pointer form only.
+// version of the count-aware batched copy (csrc/qvc_small.hip: copy_counted_kernel), on which stream_tick is instantiated.
+// RecordingBackend derives from CountingBackend and writes down every copy_batch / copy_counted call of one stream_step
+// or stream_tick, descriptor by descriptor (qvc_emu_stream_moves; tests/test_stream_moves_host.py).  The emulation's
+// backend has no single-band tail and no generator form of the noise: band-synthesis decoders, pointer form only.
 #include "../oracle/qvc_emu.cpp"
+
+#include <array>
 
 namespace {
 
@@ -126,6 +130,71 @@ int live_call(const qvc_config* cfg, const void* blob, void* state, int64_t stat
               : qvc::live_step(P, G, w, s, ws, unit_new, g, noise_new, out, batch, pos, lens, be, nullptr, g_trim);
 }
 
+// qvc_emu_twin_stream_step (tick == false) and qvc_emu_stream_tick on backend `be`: the checks of the C ABI's scaffold,
+// then the driver
+template <class Backend>
+int stream_call(Backend& be, const qvc_config* cfg, const void* blob, void* state, int64_t state_bytes, const float* unit_new,
+                const float* g, const float* noise_new, float* out, int32_t batch, int32_t hop, bool tick, const int32_t* n_new,
+                int32_t* pos, const int32_t* lens, void* workspace, int64_t workspace_bytes) {
+  qvc::Plan P; qvc::StreamGeom G;
+  const int st = qvc::stream_checks(blob && state && unit_new && g && noise_new && out && (n_new || !tick) && pos && lens && workspace, batch,
+                                    state_bytes, workspace_bytes, [&](qvc::StreamBytes& b) {
+    const int gs = qvc::stream_plan(cfg, hop, P, G);
+    if (gs == QVC_OK) b = {qvc::carve_stream_state(P, G, batch).bytes, qvc::carve_stream_scratch(P, G, batch, tick).bytes};
+    return gs;
+  });
+  if (st != QVC_OK) return st;
+  const char* w = static_cast<const char*>(blob);
+  char* s = static_cast<char*>(state);
+  char* ws = static_cast<char*>(workspace);
+  return tick ? qvc::stream_tick(P, w, s, ws, unit_new, g, noise_new, out, batch, hop, n_new, pos, lens, be)
+              : qvc::stream_step(P, w, s, ws, unit_new, g, noise_new, out, batch, hop, pos, lens, be);
+}
+
+// The recording backend of qvc_emu_stream_moves: every copy_batch / copy_counted call of one driver call, written down in
+// call order and then forwarded, so the run stays a real run.  A pointer is two words, (region, byte offset): the index
+// of the buffer of the call it points into -- the order of kMoveRegions -- or kMoveNull with offset 0.  One call is
+//   copy_batch:    0, n, then per descriptor  dst, src, dpitch, spitch, width, rows
+//   copy_counted:  1, n, slots, hop, idle_pos, n_new, pos, lens, pos_eff, len_eff, pos_add, then per descriptor
+//                  dst, src, dpitch, spitch, fixed, unit, shift, width, rows, flags
+// tests/golden/make_golden_stream_moves.py reads this layout.
+constexpr int kMoveRegions = 8;        // state, workspace, unit_new, noise_new, out, pos, lens, n_new
+constexpr int kMoveNull = kMoveRegions;
+constexpr int kMoveOutside = -100;     // qvc_emu_stream_moves: a pointer outside every region
+struct MoveRegion { const void* base; int64_t bytes; };
+struct RecordingBackend : CountingBackend {
+  std::array<MoveRegion, kMoveRegions> region = {};
+  std::vector<int64_t> words;
+  bool outside = false;
+  void ptr(const void* p) {
+    int r = p ? -1 : kMoveNull;
+    int64_t off = 0;
+    for (int i = 0; p && i < kMoveRegions; ++i) {
+      const int64_t d = static_cast<const char*>(p) - static_cast<const char*>(region[(size_t)i].base);
+      if (region[(size_t)i].base && d >= 0 && d < region[(size_t)i].bytes) { r = i; off = d; break; }
+    }
+    outside = outside || r < 0;
+    words.push_back(r); words.push_back(off);
+  }
+  int copy_batch(const qvc::CopyDesc* d, int n) {
+    words.push_back(0); words.push_back(n);
+    for (int i = 0; d && i < n; ++i) {
+      ptr(d[i].dst); ptr(d[i].src);
+      for (uint32_t v : {d[i].dpitch, d[i].spitch, d[i].width, d[i].rows}) words.push_back(v);
+    }
+    return CountingBackend::copy_batch(d, n);
+  }
+  int copy_counted(const qvc::CountedHead& h, const qvc::CountedDesc* d, int n) {
+    for (int64_t v : {1, n, h.slots, h.hop, h.idle_pos}) words.push_back(v);
+    for (const void* p : {(const void*)h.n_new, (const void*)h.pos, (const void*)h.lens, (const void*)h.pos_eff, (const void*)h.len_eff, (const void*)h.pos_add}) ptr(p);
+    for (int i = 0; d && i < n; ++i) {
+      ptr(d[i].dst); ptr(d[i].src);
+      for (uint32_t v : {d[i].dpitch, d[i].spitch, d[i].fixed, d[i].unit, d[i].shift, d[i].width, d[i].rows, d[i].flags}) words.push_back(v);
+    }
+    return CountingBackend::copy_counted(h, d, n);
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -182,34 +251,43 @@ int qvc_emu_live_tick_ring(const qvc_config* cfg, int32_t batch, int32_t hop, in
 int qvc_emu_twin_stream_step(const qvc_config* cfg, const void* blob, void* state, int64_t state_bytes, const float* unit_new,
                              const float* g, const float* noise_new, float* out, int32_t batch, int32_t hop, const int32_t* pos,
                              const int32_t* lens, void* workspace, int64_t workspace_bytes) {
-  qvc::Plan P; qvc::StreamGeom G;
-  const int st = qvc::stream_checks(blob && state && unit_new && g && noise_new && out && pos && lens && workspace, batch, state_bytes,
-                                    workspace_bytes, [&](qvc::StreamBytes& b) {
-    const int gs = qvc::stream_plan(cfg, hop, P, G);
-    if (gs == QVC_OK) b = {qvc::carve_stream_state(P, G, batch).bytes, qvc::carve_stream_scratch(P, G, batch).bytes};
-    return gs;
-  });
-  if (st != QVC_OK) return st;
   CountingBackend be;
-  return qvc::stream_step(P, static_cast<const char*>(blob), static_cast<char*>(state), static_cast<char*>(workspace), unit_new, g,
-                          noise_new, out, batch, hop, pos, lens, be);
+  return stream_call(be, cfg, blob, state, state_bytes, unit_new, g, noise_new, out, batch, hop, false, nullptr,
+                     const_cast<int32_t*>(pos), lens, workspace, workspace_bytes);    // stream_step only reads pos
 }
 
 // Same signature as qvc_stream_tick, host pointers, no stream.
 int qvc_emu_stream_tick(const qvc_config* cfg, const void* blob, void* state, int64_t state_bytes, const float* unit_new,
                         const float* g, const float* noise_new, float* out, int32_t batch, int32_t hop, const int32_t* n_new,
                         int32_t* pos, const int32_t* lens, void* workspace, int64_t workspace_bytes) {
-  qvc::Plan P; qvc::StreamGeom G;
-  const int st = qvc::stream_checks(blob && state && unit_new && g && noise_new && out && n_new && pos && lens && workspace, batch, state_bytes,
-                                    workspace_bytes, [&](qvc::StreamBytes& b) {
-    const int gs = qvc::stream_plan(cfg, hop, P, G);
-    if (gs == QVC_OK) b = {qvc::carve_stream_state(P, G, batch).bytes, qvc::carve_stream_scratch(P, G, batch, true).bytes};
-    return gs;
-  });
-  if (st != QVC_OK) return st;
   CountingBackend be;
-  return qvc::stream_tick(P, static_cast<const char*>(blob), static_cast<char*>(state), static_cast<char*>(workspace), unit_new, g,
-                          noise_new, out, batch, hop, n_new, pos, lens, be);
+  return stream_call(be, cfg, blob, state, state_bytes, unit_new, g, noise_new, out, batch, hop, true, n_new, pos, lens, workspace,
+                     workspace_bytes);
+}
+
+// One qvc_emu_twin_stream_step (n_new == nullptr) or one qvc_emu_stream_tick on the recording backend: the call runs as
+// usual and rec[0, *used) receives every copy_batch / copy_counted call of it in order (RecordingBackend states the layout).
+// QVC_ERR_SMALL_BUFFER: more than `cap` words; kMoveOutside: a launch named a pointer outside every buffer of the call.
+int qvc_emu_stream_moves(const qvc_config* cfg, const void* blob, void* state, int64_t state_bytes, const float* unit_new,
+                         const float* g, const float* noise_new, float* out, int32_t batch, int32_t hop, const int32_t* n_new,
+                         int32_t* pos, const int32_t* lens, void* workspace, int64_t workspace_bytes, int64_t* rec, int64_t cap,
+                         int64_t* used) {
+  if (!rec || !used || !cfg || batch <= 0 || hop <= 0) return QVC_ERR_BAD_ARG;
+  qvc::Plan P; qvc::StreamGeom G;
+  const int gs = qvc::stream_plan(cfg, hop, P, G);
+  if (gs != QVC_OK) return gs;
+  const int64_t col = (int64_t)batch * hop * 4;
+  RecordingBackend be;
+  be.region = {{{state, state_bytes}, {workspace, workspace_bytes}, {unit_new, col * cfg->unit_channels}, {noise_new, col * cfg->inter_channels},
+                {out, col * qvc::samples_per_frame(P)}, {pos, batch * 4}, {lens, batch * 4}, {n_new, n_new ? batch * 4 : 0}}};
+  const int st = stream_call(be, cfg, blob, state, state_bytes, unit_new, g, noise_new, out, batch, hop, n_new != nullptr, n_new, pos, lens,
+                             workspace, workspace_bytes);
+  if (st != QVC_OK) return st;
+  if (be.outside) return kMoveOutside;
+  *used = (int64_t)be.words.size();
+  if (*used > cap) return QVC_ERR_SMALL_BUFFER;
+  std::memcpy(rec, be.words.data(), be.words.size() * sizeof(int64_t));
+  return QVC_OK;
 }
 
 // The frozen backend, which does not state kStreamTick, through the same driver: what a backend without the hook gets.
