@@ -33,49 +33,28 @@ struct qvc_aux {
 namespace {
 using namespace qvc;
 
-// Layers per whole-stack WaveNet launch.  The debug switch "wn_chunk" overrides it (tuning runs; -1 = no stack kernel
-// at all: one fused launch per layer and the coupling layers' pre / post as separate convs -- the path taken by
-// configurations the stack kernel does not cover, selectable so that the tests can exercise it).
-inline int wn_chunk(int layers) {
-  const int env = debug_get(DBG_WN_CHUNK);
-  if (env < 0) return 0;
-  if (env > 0) return env <= layers ? env : layers;
-  return layers % 4 == 0 ? 4 : layers;
-}
-
-// Stream fork/join for the parallel ResBlock branches (branch 0 = the caller's stream).
-struct Branches {
-  hipStream_t main = nullptr;
-  qvc_aux* aux = nullptr;
-  hipStream_t cur = nullptr;
-  bool ok = true;
-  hipStream_t of(int j) const { return (aux && j >= 1 && j <= 2) ? aux->streams[j - 1] : main; }
-  void fork(int n) {
-    cur = main;
-    if (!aux) return;
-    if (hipEventRecord(aux->fork, main) != hipSuccess) ok = false;
-    for (int j = 1; j < n && j <= 2; ++j) if (hipStreamWaitEvent(aux->streams[j - 1], aux->fork, 0) != hipSuccess) ok = false;
-  }
-  void branch(int j) { cur = of(j); }
-  void branch_done(int j) { if (aux && j < 3 && hipEventRecord(aux->done[j], of(j)) != hipSuccess) ok = false; }
-  void join(int n) {
-    if (aux)     // branches 1 and 2 ran on the auxiliary streams (further ones, and branch 0, on main)
-      for (int j = 1; j < n && j <= 2; ++j)
-        if (hipStreamWaitEvent(main, aux->done[j], 0) != hipSuccess) ok = false;
-    cur = main;
-  }
-};
-
 struct HipBackend {
   static constexpr bool kSingleBandTail = true;   // the launchers pick the kernels by TailArgs::bands / post_tail_bands(conv_post)
   hipStream_t stream0, stream;                    // the caller's stream / the current branch's
-  Branches br;
-  explicit HipBackend(void* s, qvc_aux* aux = nullptr) : stream0(static_cast<hipStream_t>(s)), stream(stream0) { br.aux = aux; }
-  void fork(int n) { br.main = stream0; br.fork(n); stream = br.cur; }
-  void branch(int j) { br.branch(j); stream = br.cur; }
-  void branch_done(int j) { br.branch_done(j); }
-  void join(int n) { br.join(n); stream = stream0; }
-  int finish() const { return br.ok ? QVC_OK : QVC_ERR_LAUNCH; }
+  qvc_aux* aux;                                   // streams and events of the parallel ResBlock branches, or none: one stream
+  bool ok = true;
+  explicit HipBackend(void* s, qvc_aux* aux = nullptr) : stream0(static_cast<hipStream_t>(s)), stream(stream0), aux(aux) {}
+  // Stream fork/join for the parallel ResBlock branches: branches 1 and 2 run on the auxiliary streams, branch 0 and any
+  // further one on the caller's
+  hipStream_t of(int j) const { return (aux && j >= 1 && j <= 2) ? aux->streams[j - 1] : stream0; }
+  void fork(int n) {
+    stream = stream0;
+    if (!aux) return;
+    if (hipEventRecord(aux->fork, stream0) != hipSuccess) ok = false;
+    for (int j = 1; j < n && j <= 2; ++j) if (hipStreamWaitEvent(aux->streams[j - 1], aux->fork, 0) != hipSuccess) ok = false;
+  }
+  void branch(int j) { stream = of(j); }
+  void branch_done(int j) { if (aux && j < 3 && hipEventRecord(aux->done[j], of(j)) != hipSuccess) ok = false; }
+  void join(int n) {
+    for (int j = 1; aux && j < n && j <= 2; ++j) if (hipStreamWaitEvent(stream0, aux->done[j], 0) != hipSuccess) ok = false;
+    stream = stream0;
+  }
+  int finish() const { return ok ? QVC_OK : QVC_ERR_LAUNCH; }
   int conv(const ConvDesc& d, const ConvArgs& a, int batch, int epi, int dtype) { return launch_conv(d, a, batch, epi, dtype, stream); }
   int pair3(const ConvDesc* d1, const ConvDesc* d2, const PairArgs3& a, int batch, int dtype) { return launch_pair3(d1, d2, a, batch, dtype, stream); }
   bool chain_ok(const ConvDesc* d1, const ConvDesc* d2, int n) const { return debug_get(DBG_PAIR_CHAIN3) != 0 && chain_supported(d1, d2, n); }

@@ -409,6 +409,15 @@ inline const char* const* debug_names() {
                                            "launch_stop", "live_trim"};
   return n;
 }
+// Layers per whole-stack WaveNet launch.  The debug switch "wn_chunk" overrides it (tuning runs; -1 = no stack kernel
+// at all: one fused launch per layer and the coupling layers' pre / post as separate convs -- the path taken by
+// configurations the stack kernel does not cover, selectable so that the tests can exercise it).
+inline int wn_chunk(int layers) {
+  const int env = debug_get(DBG_WN_CHUNK);
+  if (env < 0) return 0;
+  if (env > 0) return env <= layers ? env : layers;
+  return layers % 4 == 0 ? 4 : layers;
+}
 // Read-only companion of launch_stop (qvc_debug_get "launch_steps"): the steps the last whole-path call would have issued.
 inline std::atomic<int32_t>& debug_launch_steps() {
   static std::atomic<int32_t> n{0};

@@ -207,7 +207,7 @@ def samples_per_frame(cfg):
 
 # ---------------------------------------------------------------- routes
 def wn_windows(cfg):
-    """Python restatement of the plan's WaveNet choice (csrc/qvc_plan.h: wn_stack_nf, wn_stack_ok; qvc_api.hip: wn_chunk)
+    """Python restatement of the plan's WaveNet choice (csrc/qvc_plan.h: wn_stack_nf, wn_stack_ok; qvc_kernels.h: wn_chunk)
     -> dict(enc=(chunk, nf) or None, flow=(chunk, nf) or None): layers per whole-stack launch and its window in 16-column
     fragments, None where the stack runs one launch per layer.  The host test checks it against the step kinds."""
     k, enc_layers, flow_layers, _n = (int(cfg.get(key, d)) for key, d in zip(("wn_kernel_size", "enc_layers", "flow_layers", "n_flows"), WN_DEFAULT))

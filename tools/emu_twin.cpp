@@ -11,9 +11,13 @@
 // RecordingBackend derives from CountingBackend and writes down every copy_batch / copy_counted call of one stream_step
 // or stream_tick, descriptor by descriptor (qvc_emu_stream_moves; tests/test_stream_moves_host.py).  The emulation's
 // backend has no single-band tail and no generator form of the noise: band-synthesis decoders, pointer form only.
+// TraceBackend stands alone: it computes nothing and writes down every backend call of a Path, field by field
+// (qvc_emu_path_trace; tests/test_path_trace_host.py) -- every decoder and every form, since nothing is run.
 #include "../oracle/qvc_emu.cpp"
 
 #include <array>
+#include <string>
+#include <type_traits>
 
 namespace {
 
@@ -195,9 +199,316 @@ struct RecordingBackend : CountingBackend {
   }
 };
 
+// The recording backend of qvc_emu_path_trace: it computes nothing.  Every method of the backend contract (csrc/qvc_path.h)
+// appends one record -- the call's name, its non-Args parameters, the ConvDesc fields the launchers read and EVERY field of
+// its Args struct -- and returns QVC_OK, so a Path instantiated on it leaves the list of launches the GPU would be handed.
+// A record is  kind (index into kTraceKinds), n, then n words.  A pointer is two words, (region, byte offset), as in
+// RecordingBackend; a float is its bit pattern; everything else its value.  Each struct below is one PUT that lists its
+// fields; the static_assert next to it fails when the struct grows, so a new field cannot be left out silently.  The
+// words are named after the listing itself (PUT stringifies it): qvc_emu_path_trace_layout, for the golden generator's
+// --dump and its coverage checks.
+constexpr const char* kTraceKinds[] = {"conv", "pair3", "chain", "wn", "wn_stack", "gemv", "sample", "sample_rows", "tail", "post_tail", "zero",
+                                       "fork", "branch", "branch_done", "join", "lstm", "spk_embed", "spk_map", "steps"};
+constexpr int kTraceKindCount = (int)(sizeof(kTraceKinds) / sizeof(kTraceKinds[0]));
+constexpr int kTraceSteps = kTraceKindCount - 1;     // the closing record of a Path form: the StepKind of every step
+enum TraceRegion { TR_BLOB, TR_WORKSPACE, TR_UNIT, TR_G, TR_NOISE, TR_OUT, TR_LENS, TR_POS, TR_FRAMES, TR_SRC, TR_ROW_FRAMES, TR_KEYS, TR_MEL,
+                   TR_Z, TR_STATE, TR_COUNT };     // TR_Z: z or spec; TR_STATE: the streaming use's stage-0 hand-over; TR_COUNT = null
+#define PUT(...) put(#__VA_ARGS__, __VA_ARGS__)
+struct TraceBackend {
+  static constexpr bool kSingleBandTail = true, kFanout = true, kNoiseRng = true;
+  std::array<MoveRegion, TR_COUNT> region = {};
+  std::vector<int64_t> words;
+  std::vector<std::string>* names = nullptr;     // layout mode: the name of every word
+  std::string cur;
+  bool outside = false;
+  size_t open_at = 0;
+
+  void word(int64_t v, const char* suffix = "") { words.push_back(v); if (names) names->push_back(cur + suffix); }
+  void ptr(const void* p) {
+    int r = p ? -1 : (int)TR_COUNT;
+    int64_t off = 0;
+    for (int i = 0; p && i < TR_COUNT; ++i) {
+      const int64_t d = static_cast<const char*>(p) - static_cast<const char*>(region[(size_t)i].base);
+      if (region[(size_t)i].base && d >= 0 && d < region[(size_t)i].bytes) { r = i; off = d; break; }
+    }
+    outside = outside || r < 0;
+    word(r); word(off, "+");
+  }
+  // one argument of a PUT: an array element by element, a pointer as (region, offset), a float as its bits, an integer as
+  // its value, a struct through its listing (fields)
+  template <class T> void one(const T& v) {
+    if constexpr (std::is_array_v<T>) {
+      const std::string outer = cur;
+      for (size_t i = 0; i < std::extent_v<T>; ++i) { cur = outer + "[" + std::to_string(i) + "]"; one(v[i]); }
+      cur = outer;
+    } else if constexpr (std::is_same_v<T, const qvc::ConvDesc*>) {
+      const int has = v != nullptr;
+      PUT(has); fields(v ? *v : qvc::ConvDesc());
+    } else if constexpr (std::is_pointer_v<T>) {
+      ptr(v);
+    } else if constexpr (std::is_floating_point_v<T>) {
+      const float f = (float)v; uint32_t u; std::memcpy(&u, &f, 4); word(u);
+    } else if constexpr (std::is_arithmetic_v<T> || std::is_enum_v<T>) {
+      word((int64_t)v);
+    } else {
+      fields(v);
+    }
+  }
+  // `list` is the text of the arguments: word names are the field names, "a.x" -> "x", nested "rg.lens"
+  template <class... A> void put(const char* list, const A&... a) {
+    const std::string outer = cur;
+    const char* p = list;
+    auto next = [&] {
+      while (*p == ' ' || *p == ',') ++p;
+      const char* e = p;
+      while (*e && *e != ',') ++e;
+      std::string s(p, e);
+      p = e;
+      const size_t dot = s.find('.');
+      return (outer.empty() ? "" : outer + ".") + (dot == std::string::npos ? s : s.substr(dot + 1));
+    };
+    ((cur = next(), one(a)), ...);
+    cur = outer;
+  }
+  static_assert(sizeof(qvc::Ragged) == 32 && sizeof(qvc::NoiseRng) == 24, "list the new field below");
+  void fields(const qvc::Ragged& a) { PUT(a.lens, a.pos, a.mul, a.add, a.off); }
+  void fields(const qvc::NoiseRng& a) { PUT(a.keys, a.seed_lo, a.seed_hi, a.scale); }
+  static_assert(sizeof(qvc::ConvArgs) == 352, "list the new field below");
+  void fields(const qvc::ConvArgs& a) {
+    PUT(a.x, a.x_kind, a.x_bs, a.x_ts, a.x_c0, a.Cin, a.CinP, a.T_in, a.slope_in, a.x2, a.x3, a.reflect, a.w, a.bias, a.bbias, a.bbias_bs,
+        a.taps, a.dil, a.left, a.KS, a.nIt, a.nchunk, a.M, a.Nq, a.up_s, a.up_p, a.Cout, a.T_out, a.res, a.res_bs, a.res_ts, a.res_c0,
+        a.res_sign, a.res16, a.y32, a.y32_bs, a.y32_ts, a.y32_c0, a.y_scale, a.y_accum, a.y16, a.y16_bs, a.y16_ts, a.slope_out, a.y32b,
+        a.split, a.gau_H, a.noise, a.noise_bs, a.noise_ts, a.ksize, a.lp, a.rg, a.rng);
+  }
+  static_assert(sizeof(qvc::PairArgs) == 96, "list the new field below");
+  void fields(const qvc::PairArgs& a) { PUT(a.x, a.bs, a.T, a.C, a.CP, a.w1, a.b1, a.w2, a.b2, a.k, a.dil, a.KS, a.nIt, a.slope, a.y); }
+  // the ConvDesc fields the launchers read
+  void fields(const qvc::ConvDesc& d) { PUT(d.MF, d.WM, d.nchunk, d.lp, d.gau, d.M, d.taps); }
+  // descriptors [0, n) of a launch of up to three chains / pairs; the rest as a default descriptor
+  struct Descs { const qvc::ConvDesc* d; int n; };
+  void fields(const Descs& v) {
+    const std::string outer = cur;
+    for (int i = 0; i < 3; ++i) { cur = outer + "[" + std::to_string(i) + "]"; fields(i < v.n && v.d ? v.d[i] : qvc::ConvDesc()); }
+    cur = outer;
+  }
+
+  void open(int kind) { words.push_back(kind); words.push_back(0); open_at = words.size(); }
+  int close() { words[open_at - 1] = (int64_t)(words.size() - open_at); return QVC_OK; }
+
+  int conv(const qvc::ConvDesc& d, const qvc::ConvArgs& a, int batch, int epi, int dtype) { open(0); PUT(batch, epi, dtype, d, a); return close(); }
+  static_assert(sizeof(qvc::PairArgs3) == 336, "list the new field below");
+  int pair3(const qvc::ConvDesc* d1s, const qvc::ConvDesc* d2s, const qvc::PairArgs3& a, int batch, int dtype) {
+    const Descs d1{d1s, a.n}, d2{d2s, a.n};
+    open(1); PUT(batch, dtype, d1, d2, a.p, a.n, a.rg, a.chain_major); return close();
+  }
+  bool chain_ok(const qvc::ConvDesc* d1, const qvc::ConvDesc* d2, int n) const { return qvc::debug_get(qvc::DBG_PAIR_CHAIN3) != 0 && qvc::chain_supported(d1, d2, n); }
+  static_assert(sizeof(qvc::ChainArgs) == 344, "list the new field below");
+  int chain(const qvc::ConvDesc* d1s, const qvc::ConvDesc* d2s, const qvc::ChainArgs& a, int batch, int dtype) {
+    const Descs d1{d1s, a.n}, d2{d2s, a.n};
+    open(2); PUT(batch, dtype, d1, d2, a.p, a.n, a.rg, a.halo, a.margin, a.NT); return close();
+  }
+  static_assert(sizeof(qvc::WnArgs) == 136, "list the new field below");
+  int wn(const qvc::ConvDesc& din, const qvc::ConvDesc& drs, const qvc::WnArgs& a, int batch, int dtype) {
+    open(3);
+    PUT(batch, dtype, din, drs, a.x_in, a.x_out, a.oacc, a.bs, a.T, a.H, a.HP, a.w_in, a.w_rs, a.b_rs, a.bbias, a.bbias_bs, a.taps, a.KS, a.nIt1, a.last, a.rg);
+    return close();
+  }
+  int wn_stack_chunk(int layers) const { return qvc::wn_chunk(layers); }
+  static_assert(sizeof(qvc::WnStackArgs) == 600, "list the new field below");
+  int wn_stack(const qvc::ConvDesc& din, const qvc::ConvDesc& drs, const qvc::ConvDesc& drs_last, const qvc::WnStackArgs& a, int batch, int dtype,
+               const qvc::ConvDesc* pre, const qvc::ConvDesc* post) {
+    open(4);
+    PUT(batch, dtype, din, drs, drs_last, pre, post, a.x0, a.out, a.bs, a.T, a.H, a.HP, a.w_in, a.w_rs, a.b_rs, a.bbias, a.bbias_bs, a.layers, a.taps,
+        a.KS, a.nIt1, a.x_out, a.accum, a.final_layer, a.w_pre, a.b_pre, a.pre_cin, a.pre_c0, a.pre_KS, a.w_post, a.b_post, a.post_m, a.post_c0,
+        a.post_mf, a.z, a.z_bs, a.z_ts, a.post_sign, a.rg, a.wide);
+    return close();
+  }
+  static_assert(sizeof(qvc::GemvArgs) == 48, "list the new field below");
+  int gemv(const qvc::GemvArgs& a) { open(5); PUT(a.w, a.bias, a.g, a.out, a.rows, a.gin, a.batch); return close(); }
+  static_assert(sizeof(qvc::SampleArgs) == 80, "list the new field below");
+  int sample(const qvc::SampleArgs& a) { open(6); PUT(a.stats, a.noise, a.z, a.batch, a.frames, a.C, a.rng, a.pos, a.off); return close(); }
+  static_assert(sizeof(qvc::SampleRowsArgs) == 88, "list the new field below");
+  int sample_rows(const qvc::SampleRowsArgs& a) {
+    open(7); PUT(a.stats, a.noise, a.z, a.src, a.frames, a.row_frames, a.sources, a.rows, a.frames_max, a.C, a.rng); return close();
+  }
+  static_assert(sizeof(qvc::TailArgs) == 80, "list the new field below");
+  int tail(const qvc::TailArgs& a) { open(8); PUT(a.post, a.fir, a.out, a.y_mb, a.batch, a.F, a.rg, a.bands); return close(); }
+  bool post_tail_ok(const qvc::ConvDesc& d) const { return qvc::debug_get(qvc::DBG_POST_TAIL) != 0 && qvc::post_tail_supported(d); }
+  static_assert(sizeof(qvc::PostTailArgs) == 408, "list the new field below");
+  int post_tail(const qvc::ConvDesc& d, const qvc::PostTailArgs& a, int batch, int dtype) {
+    open(9); PUT(batch, dtype, d, a.c, a.fir, a.out, a.F, a.rg); return close();
+  }
+  int zero(void* ptr, size_t bytes) { open(10); PUT(ptr, bytes); return close(); }
+  void fork(int n) { open(11); PUT(n); close(); }
+  void branch(int j) { open(12); PUT(j); close(); }
+  void branch_done(int j) { open(13); PUT(j); close(); }
+  void join(int n) { open(14); PUT(n); close(); }
+  static_assert(sizeof(qvc::LstmArgs) == 88, "list the new field below");
+  int lstm(const qvc::LstmArgs& a, int KS, int dtype) {
+    open(15); PUT(KS, dtype, a.xp, a.shared, a.F, a.n_part, a.S, a.P, a.H, a.w_hh, a.hseq, a.hfin, a.prow, a.pstart, a.psteps, a.phdr); return close();
+  }
+  static_assert(sizeof(qvc::SpkEmbedArgs) == 56, "list the new field below");
+  int spk_embed(const qvc::SpkEmbedArgs& a) { open(16); PUT(a.hfin, a.lw, a.lb, a.g, a.utterances, a.n_part, a.H, a.poff); return close(); }
+  static_assert(sizeof(qvc::SpkMapArgs) == 72, "list the new field below");
+  int spk_map(const qvc::SpkMapArgs& a) { open(17); PUT(a.frames, a.U, a.F, a.P, a.flen, a.poff, a.prow, a.pstart, a.psteps, a.phdr); return close(); }
+};
+#undef PUT
+
+// the forms of qvc_emu_path_trace, in the order of its `form` argument
+enum TraceForm { TF_UNIFORM, TF_RAGGED_FM, TF_RAGGED_RNG, TF_FANOUT, TF_FANOUT_RNG, TF_ENC_Q, TF_FLOW_FORWARD, TF_ENC_P, TF_DEC_TRUNK, TF_STREAM_DEC,
+                 TF_SPK, TF_SPK_RAGGED, TF_COUNT };
+constexpr int kTraceSwitches = 5;      // pair_chain3, post_tail, wn_chunk (the emulation's three), pair_cm4, pair_wide_launch
+constexpr int kTraceSwitch[kTraceSwitches] = {qvc::DBG_PAIR_CHAIN3, qvc::DBG_POST_TAIL, qvc::DBG_WN_CHUNK, qvc::DBG_PAIR_CM4, qvc::DBG_PAIR_WIDE_LAUNCH};
+
 }  // namespace
 
 extern "C" {
+
+// One form of the path (TraceForm) for (cfg, B rows of T frames; U sources of a fan-out, U utterances of T mel frames of
+// the speaker forms) on the recording backend: rec[0, *used) receives every backend call in order (TraceBackend states the
+// layout), closed for the Path forms by a "steps" record that holds the StepKind of every step.  The buffers are sized as
+// the entry points of include/qvc.h ask and never read or written.  switches (null: the defaults) = the values of
+// kTraceSwitch for the call, set in this library's own debug table and put back before it returns.
+// QVC_ERR_SMALL_BUFFER: more than `cap` words; kMoveOutside: a launch named a pointer outside every buffer of the call.
+int qvc_emu_path_trace(const qvc_config* cfg, int32_t form, int32_t B, int32_t T, int32_t U, const int32_t* switches, int64_t* rec, int64_t cap,
+                       int64_t* used) {
+  using namespace qvc;
+  if (!cfg || !rec || !used || form < 0 || form >= TF_COUNT || B <= 0 || T <= 1 || U <= 0) return QVC_ERR_BAD_ARG;
+  const bool spk = form == TF_SPK || form == TF_SPK_RAGGED;
+  const Plan P = build_plan(*cfg);
+  const EncQPlan Q = build_encq_plan(*cfg);
+  const SpkPlan S = build_spk_plan(*cfg);
+  const int plan_status = spk ? S.status : (form == TF_ENC_Q ? Q.status : P.status);
+  if (plan_status != QVC_OK) return plan_status;
+  const Workspace W = spk ? Workspace() : carve_workspace(P, B, T);
+  const SpkWorkspace SW = form == TF_SPK ? carve_spk_workspace(S, U, T) : carve_spk_ragged_workspace(S, U, T);
+  const int64_t rows = std::max(B, U), C = cfg->inter_channels, t0 = spk ? 0 : (int64_t)T * P.stages[0].rate;
+  std::array<int64_t, TR_COUNT> bytes = {};
+  bytes[TR_BLOB] = spk ? S.blob_bytes : (form == TF_ENC_Q ? Q.blob_bytes : P.blob_bytes);
+  bytes[TR_WORKSPACE] = spk ? SW.bytes : W.bytes;
+  bytes[TR_UNIT] = rows * cfg->unit_channels * T * 4;
+  bytes[TR_G] = rows * cfg->gin_channels * 4;
+  bytes[TR_NOISE] = rows * C * T * 4;
+  bytes[TR_OUT] = spk ? 0 : rows * std::max<int64_t>({(int64_t)T * samples_per_frame(P), ((int64_t)T * P.total_up + 1) * P.post_channels, T * C}) * 4;
+  bytes[TR_LENS] = bytes[TR_POS] = bytes[TR_FRAMES] = bytes[TR_SRC] = bytes[TR_ROW_FRAMES] = rows * 4;
+  bytes[TR_KEYS] = rows * 8;
+  bytes[TR_MEL] = rows * S.n_mel * T * 4;
+  bytes[TR_Z] = rows * std::max<int64_t>(C, Q.spec_channels) * T * 4;
+  bytes[TR_STATE] = spk ? 0 : 3 * rows * t0 * P.stages[0].ch * 2;
+  TraceBackend be;
+  std::array<void*, TR_COUNT> buf = {};
+  bool alloc_ok = true;
+  for (int i = 0; i < TR_COUNT; ++i) {
+    buf[(size_t)i] = std::malloc((size_t)std::max<int64_t>(bytes[(size_t)i], 1));
+    alloc_ok = alloc_ok && buf[(size_t)i];
+    be.region[(size_t)i] = {buf[(size_t)i], bytes[(size_t)i]};
+  }
+  auto f32 = [&](int r) { return static_cast<float*>(buf[(size_t)r]); };
+  auto i32 = [&](int r) { return static_cast<int32_t*>(buf[(size_t)r]); };
+  int32_t saved[kTraceSwitches];
+  for (int i = 0; i < kTraceSwitches; ++i) {
+    saved[i] = debug_get(kTraceSwitch[i]);
+    if (switches) debug_table()[kTraceSwitch[i]].store(switches[i], std::memory_order_relaxed);
+  }
+  int st = alloc_ok ? QVC_OK : QVC_ERR_BAD_ARG;
+  std::vector<int32_t> kinds(4096, -1);
+  int steps = 0;
+  if (st == QVC_OK && spk) {
+    const char* blob = static_cast<const char*>(buf[TR_BLOB]);
+    char* ws = static_cast<char*>(buf[TR_WORKSPACE]);
+    st = form == TF_SPK ? spk_path(S, dec_dtype(*cfg), blob, ws, SW, f32(TR_MEL), f32(TR_G), U, T, be)
+                        : spk_path_ragged(S, dec_dtype(*cfg), blob, ws, SW, f32(TR_MEL), i32(TR_FRAMES), f32(TR_G), U, T, be);
+  } else if (st == QVC_OK) {
+    NoiseRng rng;
+    rng.keys = static_cast<const uint64_t*>(buf[TR_KEYS]); rng.seed_lo = 0x1234567u; rng.seed_hi = 0x89abcdeu; rng.scale = 0.75f;
+    auto path = [&] {
+      Path<TraceBackend> c{P, static_cast<const char*>(buf[TR_BLOB]), static_cast<char*>(buf[TR_WORKSPACE]), W, B, T, be};
+      c.step_n = steps; c.step_kinds = kinds.data(); c.max_step_kinds = (int)kinds.size();
+      return c;
+    };
+    Path<TraceBackend> c = path();
+    switch (form) {
+      case TF_UNIFORM: c.infer(f32(TR_UNIT), f32(TR_G), f32(TR_NOISE), f32(TR_OUT)); break;
+      case TF_RAGGED_FM: c.lens = i32(TR_LENS); c.unit_fm = true; c.infer(f32(TR_UNIT), f32(TR_G), f32(TR_NOISE), f32(TR_OUT)); break;
+      case TF_RAGGED_RNG: c.lens = i32(TR_LENS); c.rng = rng; c.infer(f32(TR_UNIT), f32(TR_G), nullptr, f32(TR_OUT)); break;
+      case TF_FANOUT:
+        c.infer_fanout(f32(TR_UNIT), i32(TR_FRAMES), i32(TR_SRC), U, f32(TR_G), f32(TR_NOISE), f32(TR_OUT), i32(TR_ROW_FRAMES));
+        break;
+      case TF_FANOUT_RNG:
+        c.unit_fm = true; c.rng = rng;
+        c.infer_fanout(f32(TR_UNIT), i32(TR_FRAMES), i32(TR_SRC), U, f32(TR_G), nullptr, f32(TR_OUT), i32(TR_ROW_FRAMES));
+        break;
+      case TF_ENC_Q: c.enc_q(Q, c.blob, f32(TR_Z), f32(TR_G), f32(TR_NOISE), f32(TR_OUT)); break;
+      case TF_FLOW_FORWARD: c.cond_table(f32(TR_G)); c.flow(f32(TR_Z), /*forward=*/true); break;
+      case TF_ENC_P: c.enc_p(f32(TR_UNIT), f32(TR_NOISE), f32(TR_Z)); break;
+      case TF_DEC_TRUNK: c.cond_table(f32(TR_G)); c.dec_trunk(f32(TR_Z), f32(TR_OUT)); break;
+      default: {   // TF_STREAM_DEC: two segments of a streaming step, as Segments::make sets them up (csrc/qvc_stream.h)
+        c.lens = i32(TR_LENS); c.pos = i32(TR_POS); c.off = 7; c.wn_wide = false;
+        c.dec_front(f32(TR_Z));
+        st = c.status; steps = c.step_n;
+        Path<TraceBackend> d = path();
+        d.lens = i32(TR_LENS); d.pos = i32(TR_POS); d.off = 11; d.wn_wide = false;
+        for (int j = 0; j < 3; ++j) d.s0_override[j] = static_cast<char*>(buf[TR_STATE]) + (int64_t)j * rows * t0 * P.stages[0].ch * 2;
+        if (st == QVC_OK) { d.dec_back_wave(d.wsp<float>(d.W.post), f32(TR_OUT)); st = d.status; steps = d.step_n; }
+        break;
+      }
+    }
+    if (form != TF_STREAM_DEC) { st = c.status; steps = c.step_n; }
+    if (steps > (int)kinds.size()) st = QVC_ERR_SMALL_BUFFER;
+    be.open(kTraceSteps);
+    for (int i = 0; st == QVC_OK && i < steps; ++i) be.words.push_back(kinds[(size_t)i]);
+    be.close();
+  }
+  for (int i = 0; i < kTraceSwitches; ++i) debug_table()[kTraceSwitch[i]].store(saved[i], std::memory_order_relaxed);
+  for (void* p : buf) std::free(p);
+  if (st != QVC_OK) return st;
+  if (be.outside) return kMoveOutside;
+  *used = (int64_t)be.words.size();
+  if (*used > cap) return QVC_ERR_SMALL_BUFFER;
+  std::memcpy(rec, be.words.data(), be.words.size() * sizeof(int64_t));
+  return QVC_OK;
+}
+
+// The layout of the records of qvc_emu_path_trace as text, one line per kind: "<kind> <name of word 0> <name of word 1> ..."
+// (a pointer is "<field>" "<field>+": region, offset).  Returns the bytes the text needs, the closing 0 included; the text
+// is written when `cap` holds it.
+int64_t qvc_emu_path_trace_layout(char* text, int64_t cap) {
+  using namespace qvc;
+  std::vector<std::string> names;
+  TraceBackend be;
+  be.names = &names;
+  std::string out;
+  auto line = [&](int kind) {
+    out += kTraceKinds[kind];
+    for (const std::string& n : names) out += " " + n;
+    out += "\n";
+    names.clear();
+  };
+  ConvDesc d[3];
+  int kind = 0;
+  be.conv(d[0], ConvArgs(), 0, 0, 0); line(kind++);
+  be.pair3(d, d, PairArgs3(), 0, 0); line(kind++);
+  be.chain(d, d, ChainArgs(), 0, 0); line(kind++);
+  be.wn(d[0], d[0], WnArgs(), 0, 0); line(kind++);
+  be.wn_stack(d[0], d[0], d[0], WnStackArgs(), 0, 0, nullptr, nullptr); line(kind++);
+  be.gemv(GemvArgs()); line(kind++);
+  be.sample(SampleArgs()); line(kind++);
+  be.sample_rows(SampleRowsArgs()); line(kind++);
+  be.tail(TailArgs()); line(kind++);
+  be.post_tail(d[0], PostTailArgs(), 0, 0); line(kind++);
+  be.zero(nullptr, 0); line(kind++);
+  be.fork(0); line(kind++);
+  be.branch(0); line(kind++);
+  be.branch_done(0); line(kind++);
+  be.join(0); line(kind++);
+  be.lstm(LstmArgs(), 0, 0); line(kind++);
+  be.spk_embed(SpkEmbedArgs()); line(kind++);
+  be.spk_map(SpkMapArgs()); line(kind++);
+  line(kind++);      // "steps": one word per step, no names
+  const int64_t need = (int64_t)out.size() + 1;
+  if (text && cap >= need) std::memcpy(text, out.c_str(), (size_t)need);
+  return need;
+}
 
 // The library's debug switch "live_trim" for the twin: 1 (default) the trimmed form, 0 the plain one.  One switch, two names.
 void qvc_emu_live_trim(int32_t on) { g_trim = on != 0; }
