@@ -410,6 +410,43 @@ int qvc_stream_tick_rng(const qvc_config* cfg, const void* blob_dev, void* state
                         int32_t batch, int32_t hop, const int32_t* n_new_dev, int32_t* pos_dev, const int32_t* len_dev,
                         void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- slot snapshots: move a running segment-ring stream between slots, batch sizes, hops, devices and processes ---
+ * Between two calls of qvc_stream_step / qvc_stream_tick a stream IS the kept 2*H frames of its rows of every ring plus
+ * pos[slot] and len[slot] (the hop frames behind the kept ones are rewritten before they are read).  None of that
+ * depends on the batch size, the slot or the hop, so a snapshot cut from one state continues in any slot of any other
+ * state of the same model: another converter, a larger or smaller batch, another hop, after a trip through host
+ * memory.  A snapshot of one slot is qvc_stream_snapshot_bytes() bytes (a multiple of 256; a function of the
+ * configuration alone): per ring, in the order the rings lie in the state, the kept part of the slot's rows, each ring
+ * 256-byte aligned; then pos and len as two int32.
+ *   qvc_stream_snapshot_tag   a 64-bit fingerprint of that layout: a format version, cfg.operand_dtype (the stage-0
+ *              rings are stored in the operand type), the decoder kind, the channel counts, the reaches of the five
+ *              kinds of segment and every ring's rows and kept bytes.  It does not depend on batch, hop or the weights:
+ *              two snapshots are interchangeable when their tags are equal AND they come from the same checkpoint.  The
+ *              caller stores the tag beside the bytes; the library does not.
+ *   qvc_stream_export_slots   snapshot i (at snap_dev + i * qvc_stream_snapshot_bytes()) <- slot slots_host[i].  Reads only.
+ *   qvc_stream_import_slots   slot slots_host[i] <- snapshot i: writes the kept part of that slot's rows of every ring,
+ *              pos_dev[slot] and len_dev[slot], and NOTHING else -- not the hop part of the rows, not another slot.
+ *              The slots of one import must be distinct.
+ *   state, batch, hop   the state the slots live in, as passed to qvc_stream_step / _tick for it
+ *   slots_host HOST int32 [n_slots], each in [0, batch); read during the call (baked into the launches)
+ *   snap_dev   DEVICE, 256-byte aligned, n_slots snapshots back to back; snap_bytes >= n_slots * qvc_stream_snapshot_bytes()
+ * As with qvc_stream_reset_slot the caller moves the slot's g row and generator key itself.  Both calls only enqueue
+ * batched strided copies on `stream`: asynchronous, allocation-free, graph-capturable.  Checks, in this order:
+ * QVC_ERR_BAD_ARG for a null cfg / state / pos_dev / len_dev / snap_dev / slots_host, batch < 1, n_slots < 1 or a slot
+ * outside [0, batch); the plan -- QVC_ERR_BAD_ARG for hop < 1, QVC_ERR_BAD_CONFIG for what qvc_stream_step refuses (the
+ * single-band decoder, decoders without exactly two up-samplers; from the two queries too); QVC_ERR_SMALL_BUFFER for
+ * state_bytes or snap_bytes too small; QVC_ERR_BAD_ARG for a state or snap_dev that is not 256-byte aligned.  A refused
+ * call launches nothing.  The windowed step (qvc_live_*) is not covered: its state is the caller's own last C + L input
+ * frames.  csrc/qvc_stream.h (SnapLayout, move_slots) has the details. */
+int64_t qvc_stream_snapshot_bytes(const qvc_config* cfg);
+int qvc_stream_snapshot_tag(const qvc_config* cfg, uint64_t* tag);
+int qvc_stream_export_slots(const qvc_config* cfg, const void* state, int64_t state_bytes, int32_t batch, int32_t hop,
+                            const int32_t* slots_host, int32_t n_slots, const int32_t* pos_dev, const int32_t* len_dev,
+                            void* snap_dev, int64_t snap_bytes, void* stream);
+int qvc_stream_import_slots(const qvc_config* cfg, void* state, int64_t state_bytes, int32_t batch, int32_t hop,
+                            const int32_t* slots_host, int32_t n_slots, int32_t* pos_dev, int32_t* len_dev,
+                            const void* snap_dev, int64_t snap_bytes, void* stream);
+
 /* ---- optional fork/join resources: lets the three independent ResBlocks of an MRF stage
  * (models.py:378-384) run as parallel branches (two auxiliary non-blocking streams + events), so a
  * memory-bound k=3 launch overlaps a compute-bound k=11 launch.  Created/destroyed by the caller

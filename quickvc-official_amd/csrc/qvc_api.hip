@@ -344,6 +344,15 @@ int reset_slot_api(void* state, int64_t state_bytes, int32_t batch, int32_t slot
   return ok ? QVC_OK : QVC_ERR_LAUNCH;
 }
 
+// qvc_stream_export_slots / qvc_stream_import_slots: snapshot_slots of qvc_stream.h (the checks, then copy_batch launches
+// only) on the caller's stream.
+int snapshot_api(bool import, const qvc_config* cfg, void* state, int64_t state_bytes, int32_t batch, int32_t hop, const int32_t* slots_host,
+                 int32_t n_slots, int32_t* pos_dev, int32_t* len_dev, void* snap_dev, int64_t snap_bytes, void* stream) {
+  HipBackend be(stream);
+  const int rc = snapshot_slots(import, be, cfg, state, state_bytes, batch, hop, slots_host, n_slots, pos_dev, len_dev, snap_dev, snap_bytes);
+  return rc != QVC_OK ? rc : be.finish();
+}
+
 }  // namespace
 
 extern "C" {
@@ -567,6 +576,30 @@ int qvc_stream_reset_slot(const qvc_config* cfg, void* state, int64_t state_byte
     if (gs == QVC_OK) R = stream_rings(P, G, batch);
     return gs;
   });
+}
+
+int64_t qvc_stream_snapshot_bytes(const qvc_config* cfg) {
+  SnapLayout L;
+  const int st = stream_snapshot(cfg, L);
+  return st != QVC_OK ? st : L.bytes;
+}
+
+int qvc_stream_snapshot_tag(const qvc_config* cfg, uint64_t* tag) {
+  SnapLayout L;
+  return tag ? stream_snapshot(cfg, L, tag) : QVC_ERR_BAD_ARG;
+}
+
+int qvc_stream_export_slots(const qvc_config* cfg, const void* state, int64_t state_bytes, int32_t batch, int32_t hop,
+                            const int32_t* slots_host, int32_t n_slots, const int32_t* pos_dev, const int32_t* len_dev, void* snap_dev,
+                            int64_t snap_bytes, void* stream) {
+  return snapshot_api(false, cfg, const_cast<void*>(state), state_bytes, batch, hop, slots_host, n_slots, const_cast<int32_t*>(pos_dev),
+                      const_cast<int32_t*>(len_dev), snap_dev, snap_bytes, stream);      // an export only reads them
+}
+
+int qvc_stream_import_slots(const qvc_config* cfg, void* state, int64_t state_bytes, int32_t batch, int32_t hop, const int32_t* slots_host,
+                            int32_t n_slots, int32_t* pos_dev, int32_t* len_dev, const void* snap_dev, int64_t snap_bytes, void* stream) {
+  return snapshot_api(true, cfg, state, state_bytes, batch, hop, slots_host, n_slots, pos_dev, len_dev, const_cast<void*>(snap_dev), snap_bytes,
+                      stream);                                                          // an import only reads the snapshots
 }
 
 int64_t qvc_stream_tick_workspace_bytes(const qvc_config* cfg, int32_t batch, int32_t hop) {

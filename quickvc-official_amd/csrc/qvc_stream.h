@@ -26,7 +26,8 @@
 // live_tick (live_step with per-slot frame counts).  What they share is stated once:
 //   Rings         the ring table of a driver (stream_rings / live_rings): where every ring lies in the state and its
 //                 geometry.  The state size, the slide buffers of the scratch, the slide loops and the per-slot reset
-//                 (reset_slot, slot_range) all read the table, so a ring is added or resized in ONE place.
+//                 (reset_slot, slot_range) all read the table, so a ring is added or resized in ONE place.  So do the
+//                 snapshot of a slot (SnapLayout: the kept parts, pos and len) and its export / import (move_slots).
 //   movers        the queue all data movement of a call goes through: CopyQueue in front of the backend's copy_batch
 //                 (every slot moves by hop frames), CountedQueue in front of copy_counted (slot b moves by its n frames).
 //                 Both speak the same verbs, rows always PER SLOT:
@@ -91,6 +92,24 @@ int reset_slot(void* state, int64_t state_bytes, int batch, int slot, int length
     zero(static_cast<char*>(state) + s.off, (size_t)s.bytes);
   }
   return QVC_OK;
+}
+
+// What a stream IS between two calls: the kept part of its rows of every ring, plus pos and len (stream_tick's INVARIANT: the
+// hop part of a row is rewritten before it is read).  The snapshot of ONE slot, written once on the table: per ring, in
+// table order, rows x keep bytes (a row's kept part, rows back to back), each ring 256-byte aligned; then pos and len as
+// two int32.  It depends on the kept geometry only -- never on the batch, the slot or the hop of the state it is cut from.
+struct SnapLayout {
+  int64_t ring[kMaxRings] = {};   // byte offset of ring i's kept rows
+  int64_t pos = 0;                // pos at this offset, len 4 bytes behind it
+  int64_t bytes = 0;              // a multiple of 256: snapshots lie back to back
+};
+inline SnapLayout snap_layout(const Rings& R) {
+  SnapLayout L;
+  Carver cv;
+  for (int i = 0; i < R.n; ++i) L.ring[i] = cv.take(R.r[i].rows * R.r[i].keep);
+  L.pos = cv.take(8);
+  L.bytes = cv.off;
+  return L;
 }
 
 // The pure-host checks of a step / tick entry point, in the order the status codes are pinned to: pointers and batch,
@@ -213,6 +232,52 @@ struct CountedQueue : RingMoves<CountedQueue<Backend_>> {
   void advance(int32_t* pos) { head.pos_add = pos; }   // the next launch: pos[b] += n
 };
 
+// Export and import of slots, reset_slot's siblings: the copies between the state of `batch` slots (pos, lens beside it) and
+// n snapshots back to back in `snap`, snapshot i <-> slot slots[i] (host array; every slot in [0, batch), distinct for an
+// import), queued through CopyQueue in front of the backend's copy_batch -- nothing else is launched.  A ring of several
+// rows per slot (the unit ring) is one strided descriptor per slot: rows x keep out of rows of keep + hopb.  A ring of one
+// row per slot is one contiguous run per slot, so a run of consecutive slots is ONE descriptor whose rows are the slots
+// (pitch: a slot's row in the state, a snapshot in `snap`); pos and len travel the same way as 4-byte copies.  All
+// descriptors of a call are independent, so it does not matter where the queue flushes.
+// Import writes the kept part of the named slots' rows, pos[slot] and lens[slot]; the hop parts and the other slots are
+// left as they are.  Export only reads the state.
+template <class Backend>
+int move_slots(bool import, Backend& be, const Rings& R, char* state, const int32_t* slots, int n, int32_t* pos, int32_t* lens, char* snap) {
+  const SnapLayout L = snap_layout(R);
+  CopyQueue<Backend> q(be, 1, 1);
+  auto mv = [&](char* st, int64_t st_pitch, char* sn, int64_t sn_pitch, int64_t width, int64_t rows) {
+    if (import) q.add(st, (size_t)st_pitch, sn, (size_t)sn_pitch, (size_t)width, (size_t)rows);
+    else q.add(sn, (size_t)sn_pitch, st, (size_t)st_pitch, (size_t)width, (size_t)rows);
+  };
+  int64_t widest = L.bytes;                                        // the widest pitch of a run descriptor
+  for (int k = 0; k < R.n; ++k) widest = std::max(widest, R.r[k].keep + R.r[k].hopb);
+  const int64_t max_run = std::max<int64_t>(1, ((int64_t)1 << 31) / widest);   // copy_batch: 32-bit offsets inside a descriptor
+  for (int i = 0; i < n;) {
+    int run = 1;
+    while (i + run < n && run < max_run && slots[i + run] == slots[i] + run) ++run;
+    char* sn = snap + (int64_t)i * L.bytes;
+    for (int k = 0; k < R.n; ++k) {
+      const Ring& r = R.r[k];
+      const int64_t pitch = r.keep + r.hopb;
+      if (r.rows == 1) { mv(state + slot_range(r, slots[i]).off, pitch, sn + L.ring[k], L.bytes, r.keep, run); continue; }
+      for (int j = 0; j < run; ++j) mv(state + slot_range(r, slots[i] + j).off, pitch, sn + j * L.bytes + L.ring[k], r.keep, r.keep, r.rows);
+    }
+    mv(reinterpret_cast<char*>(pos + slots[i]), 4, sn + L.pos, L.bytes, 4, run);
+    mv(reinterpret_cast<char*>(lens + slots[i]), 4, sn + L.pos + 4, L.bytes, 4, run);
+    i += run;
+  }
+  q.flush();
+  return q.st;
+}
+template <class Backend>
+int export_slots(Backend& be, const Rings& R, const char* state, const int32_t* slots, int n, const int32_t* pos, const int32_t* lens, char* snap) {
+  return move_slots(false, be, R, const_cast<char*>(state), slots, n, const_cast<int32_t*>(pos), const_cast<int32_t*>(lens), snap);
+}
+template <class Backend>
+int import_slots(Backend& be, const Rings& R, char* state, const int32_t* slots, int n, int32_t* pos, int32_t* lens, const char* snap) {
+  return move_slots(true, be, R, state, slots, n, pos, lens, const_cast<char*>(snap));
+}
+
 // A step's segments: make(T, lag_before) is a Path over the last T rows of a window whose newest `hop` rows are this
 // step's frames -- buffer row lag_before + T - hop is absolute frame pos[b].
 template <class Backend>
@@ -275,6 +340,52 @@ inline Rings stream_rings(const Plan& P, const StreamGeom& G, int B) {
   R.add(B, 1, 2 * G.Hd1 * zrow, h * zrow);
   for (int j = 0; j < 3; ++j) R.add(B, 1, 2 * G.Hd2 * srow, h * srow);
   return R;
+}
+
+// The snapshot of one slot of the segment rings: its layout (sized on the plan alone: any batch, any hop) and the tag
+// that fingerprints it -- FNV-1a over a format version, the operand type (the stage-0 rings are stored in it), the
+// decoder kind, the channel counts and r0, the five reaches and every ring's (rows, keep).  Neither depends on the batch,
+// the hop or the weights: snapshots of one checkpoint are interchangeable exactly when their tags are equal.
+constexpr uint64_t kSnapshotFormat = 1;
+inline int stream_snapshot(const qvc_config* cfg, SnapLayout& L, uint64_t* tag = nullptr) {
+  Plan P; StreamGeom G;
+  const int gs = stream_plan(cfg, 1, P, G);
+  if (gs != QVC_OK) return gs;
+  const Rings R = stream_rings(P, G, 1);
+  L = snap_layout(R);
+  if (tag) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    auto word = [&](uint64_t v) { for (int i = 0; i < 8; ++i) { h ^= (v >> (8 * i)) & 0xff; h *= 0x100000001b3ull; } };
+    const qvc_config& c = P.cfg;
+    for (int64_t v : {(int64_t)kSnapshotFormat, (int64_t)c.operand_dtype, (int64_t)c.decoder, (int64_t)c.unit_channels, (int64_t)c.inter_channels,
+                      (int64_t)P.stages[0].ch, (int64_t)G.r0, (int64_t)G.He, (int64_t)G.Hf, (int64_t)G.nf, (int64_t)G.Hd1, (int64_t)G.Hd2, (int64_t)R.n})
+      word((uint64_t)v);
+    for (int i = 0; i < R.n; ++i) { word((uint64_t)R.r[i].rows); word((uint64_t)R.r[i].keep); }
+    *tag = h;
+  }
+  return QVC_OK;
+}
+
+// What qvc_stream_export_slots / qvc_stream_import_slots (and the CPU twin's) do on backend `be`: the checks in the order
+// the status codes are pinned to -- pointers, counts and slots; the plan; the two sizes (stream_checks, the snapshots in
+// the workspace's place); the alignments -- and then the copies.  A refused call launches nothing.
+template <class Backend>
+int snapshot_slots(bool import, Backend& be, const qvc_config* cfg, void* state, int64_t state_bytes, int batch, int hop, const int32_t* slots,
+                   int n_slots, int32_t* pos, int32_t* lens, void* snap, int64_t snap_bytes) {
+  bool args_ok = cfg && state && pos && lens && snap && slots && n_slots >= 1;
+  for (int i = 0; args_ok && i < n_slots; ++i) args_ok = slots[i] >= 0 && slots[i] < batch;
+  Rings R;
+  const int st = stream_checks(args_ok, batch, state_bytes, snap_bytes, [&](StreamBytes& b) {
+    Plan P; StreamGeom G;
+    const int gs = stream_plan(cfg, hop, P, G);
+    if (gs != QVC_OK) return gs;
+    R = stream_rings(P, G, batch);
+    b = {R.bytes(), (int64_t)n_slots * snap_layout(R).bytes};
+    return gs;
+  });
+  if (st != QVC_OK) return st;
+  if ((reinterpret_cast<uintptr_t>(state) & 255) || (reinterpret_cast<uintptr_t>(snap) & 255)) return QVC_ERR_BAD_ARG;
+  return move_slots(import, be, R, static_cast<char*>(state), slots, n_slots, pos, lens, static_cast<char*>(snap));
 }
 
 struct StreamState {     // the ring table and, by name, the byte offsets of its rings in the caller-owned state buffer

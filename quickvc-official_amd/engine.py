@@ -319,6 +319,41 @@ class QvcEngine:
         """qvc_stream_reset_slot: zero slot `slot`'s ring rows, pos[slot] = 0, lens[slot] = length (on the current stream)."""
         self._stream_reset_slot("stream", state, batch, (hop,), slot, length, pos, lens)
 
+    # ---- slot snapshots of the segment rings: what a stream is between two calls, free of batch, slot and hop
+    def stream_snapshot_bytes(self) -> int:
+        """Bytes of ONE slot's snapshot (qvc_stream_snapshot_bytes): a multiple of 256, a function of the model alone."""
+        return self._stream_sizes("stream_snapshot", ("stream_snapshot_bytes",))[0]
+
+    def stream_snapshot_tag(self) -> int:
+        """The 64-bit fingerprint of the snapshot layout (qvc_stream_snapshot_tag): equal tags + the same checkpoint =
+        interchangeable snapshots."""
+        tag = ctypes.c_uint64(0)
+        L.check(self.lib, self.lib.qvc_stream_snapshot_tag(ctypes.byref(self.cfg), ctypes.byref(tag)), "qvc_stream_snapshot_tag")
+        return int(tag.value)
+
+    def _stream_snapshot_call(self, name: str, state, batch, hop, slots, pos, lens, snap) -> None:
+        slots = [int(s) for s in slots]
+        arr = (ctypes.c_int32 * max(len(slots), 1))(*slots)
+        st = getattr(self.lib, name)(ctypes.byref(self.cfg), state.data_ptr(), state.numel(), int(batch), int(hop), arr, len(slots),
+                                     pos.data_ptr(), lens.data_ptr(), snap.data_ptr(), snap.numel(),
+                                     torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib, st, name)
+
+    @_on_device
+    def stream_export_slots(self, state: torch.Tensor, batch: int, hop: int, slots, pos: torch.Tensor, lens: torch.Tensor,
+                            snap: torch.Tensor) -> None:
+        """qvc_stream_export_slots: snapshot i of ``snap`` (uint8, 256-byte aligned, on this device, len(slots) *
+        stream_snapshot_bytes()) <- slot ``slots[i]`` of ``state`` (built for ``batch`` slots and ``hop``), on the current
+        stream.  Reads the state only."""
+        self._stream_snapshot_call("qvc_stream_export_slots", state, batch, hop, slots, pos, lens, snap)
+
+    @_on_device
+    def stream_import_slots(self, state: torch.Tensor, batch: int, hop: int, slots, pos: torch.Tensor, lens: torch.Tensor,
+                            snap: torch.Tensor) -> None:
+        """qvc_stream_import_slots: slot ``slots[i]`` <- snapshot i: the kept part of that slot's ring rows, pos[slot] and
+        lens[slot], nothing else.  The slot's g row and generator key are the caller's to move."""
+        self._stream_snapshot_call("qvc_stream_import_slots", state, batch, hop, slots, pos, lens, snap)
+
     def stream_tick_sizes(self, batch: int, hop: int):
         """(state_bytes, workspace_bytes, lag_frames, noise_lag_frames) for `batch` streams that bring AT MOST `hop` frames
         per tick (qvc_stream_tick): stream_step's state, a larger workspace."""

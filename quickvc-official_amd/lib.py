@@ -199,6 +199,19 @@ def declare(lib: ctypes.CDLL, prefix: str = "qvc") -> None:
             fn = getattr(lib, prefix + name)
             fn.restype = ctypes.c_int
             fn.argtypes = [cfgp, V, V, L, V, V, draw, V, I, I, V, V, V, V, L, V]
+    # slot snapshots of the segment rings (qvc_stream_export_slots / _import_slots): (cfg, state, state_bytes, batch, hop,
+    # slots_host, n_slots, pos_dev, len_dev, snap_dev, snap_bytes, stream) and the two queries on the configuration alone
+    if hasattr(lib, prefix + "_stream_snapshot_bytes"):
+        fn = getattr(lib, prefix + "_stream_snapshot_bytes")
+        fn.restype = L
+        fn.argtypes = [cfgp]
+        fn = getattr(lib, prefix + "_stream_snapshot_tag")
+        fn.restype = ctypes.c_int
+        fn.argtypes = [cfgp, P(ctypes.c_uint64)]
+        for name in ("_stream_export_slots", "_stream_import_slots"):
+            fn = getattr(lib, prefix + name)
+            fn.restype = ctypes.c_int
+            fn.argtypes = [cfgp, V, L, I, I, P(I), I, V, V, V, L, V]
     for name in ("_stream_lag_frames", "_stream_noise_lag_frames", "_live_context_frames"):
         if hasattr(lib, prefix + name):
             fn = getattr(lib, prefix + name)

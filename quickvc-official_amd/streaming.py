@@ -13,6 +13,7 @@ in a hipGraph and replayed per chunk.  Latency of a streamed chunk = ``context``
 """
 from __future__ import annotations
 
+import struct
 from typing import Iterator, Optional, Tuple
 
 import torch
@@ -89,6 +90,59 @@ class ChunkedConverter:
         return out
 
 
+class StreamSnapshot:
+    """One segment-ring stream between two calls, free of the slot, the batch size and the hop it ran under
+    (qvc_stream_export_slots): ``data`` -- the kept frames of every ring, the position and the length, a uint8 tensor on
+    a device or the host --, ``tag`` -- the layout fingerprint the destination must share --, the stream's speaker
+    embedding ``g`` and generator ``key``, ``position`` / ``length`` from the converter's host mirrors, and
+    ``rng = (seed, noise_scale)`` when the source converter draws its noise from the generator, else None.
+    ``tobytes`` / ``frombytes``: a fixed header, ``g``, then the data -- for another process or machine."""
+
+    _HEAD = struct.Struct("<8sQQqqBQdIQ")      # magic, tag, key, position, length, has rng, seed, noise_scale, len(g), len(data)
+    _MAGIC = b"QVCSNAP1"
+
+    def __init__(self, tag: int, data: torch.Tensor, g: torch.Tensor, key: int, position: int, length: int,
+                 rng: Optional[Tuple[int, float]] = None):
+        self.tag, self.data, self.g, self.key = int(tag), data, g, int(key) & 0xFFFFFFFFFFFFFFFF
+        self.position, self.length = int(position), int(length)
+        self.rng = None if rng is None else (int(rng[0]), float(rng[1]))
+
+    def to(self, device) -> "StreamSnapshot":
+        """The same snapshot with ``data`` and ``g`` on ``device`` (device data is 256-byte aligned, as an import needs)."""
+        device = torch.device(device)
+        if device.type == "cpu":
+            data = self.data.cpu()
+        else:
+            from .engine import aligned_empty
+            data = aligned_empty(self.data.numel(), device)
+            data.copy_(self.data)
+        return StreamSnapshot(self.tag, data, self.g.to(device), self.key, self.position, self.length, self.rng)
+
+    def cpu(self) -> "StreamSnapshot":
+        return self.to("cpu")
+
+    def tobytes(self) -> bytes:
+        g = self.g.detach().to("cpu", torch.float32).contiguous().reshape(-1)
+        data = self.data.detach().cpu().contiguous().reshape(-1)
+        seed, scale = self.rng if self.rng is not None else (0, 0.0)
+        head = self._HEAD.pack(self._MAGIC, self.tag, self.key, self.position, self.length, self.rng is not None,
+                               seed & 0xFFFFFFFFFFFFFFFF, scale, g.numel(), data.numel())
+        return head + g.numpy().tobytes() + data.numpy().tobytes()
+
+    @classmethod
+    def frombytes(cls, raw: bytes) -> "StreamSnapshot":
+        """The host snapshot ``tobytes`` wrote; ValueError for anything else."""
+        n = cls._HEAD.size
+        if len(raw) < n or raw[:8] != cls._MAGIC:
+            raise ValueError("not a StreamSnapshot byte string")
+        _magic, tag, key, position, length, has_rng, seed, scale, n_g, n_data = cls._HEAD.unpack(raw[:n])
+        if len(raw) != n + 4 * n_g + n_data:
+            raise ValueError(f"StreamSnapshot byte string of {len(raw)} bytes, its header says {n + 4 * n_g + n_data}")
+        g = torch.frombuffer(bytearray(raw[n:n + 4 * n_g]), dtype=torch.float32) if n_g else torch.zeros(0)
+        data = torch.frombuffer(bytearray(raw[n + 4 * n_g:]), dtype=torch.uint8) if n_data else torch.zeros(0, dtype=torch.uint8)
+        return cls(tag, data, g, key, position, length, (seed, scale) if has_rng else None)
+
+
 class StreamConverter:
     """Incremental conversion of ``streams`` concurrent streams, ``hop_frames`` new unit frames per step
     (qvc_stream_step; BASELINE.json configs[4]).  Unlike ChunkedConverter it needs nothing but the frames seen so
@@ -126,6 +180,7 @@ class StreamConverter:
         self._pos_host = [0] * S
         self._len_host = [2 ** 30] * S
         self._keys = torch.zeros(S, dtype=torch.int64, device=dev)   # generator key per slot (read by the step as uint64)
+        self._keys_host = [0] * S                                # host mirror of the keys (a snapshot carries its slot's)
         self._use_graph = use_graph
         self._rng = None                                         # (seed, noise_scale) of the generator form, once asked for
         self._rng_graph = None
@@ -222,6 +277,7 @@ class StreamConverter:
             if key is not None:
                 k = int(key) & 0xFFFFFFFFFFFFFFFF
                 self._keys[slot:slot + 1].fill_(k - (1 << 64) if k >> 63 else k)
+                self._keys_host[slot] = k
         self._pos_host[slot] = 0
         self._len_host[slot] = n
 
@@ -230,6 +286,133 @@ class StreamConverter:
         with torch.cuda.stream(self._stream):
             self._len[slot:slot + 1].fill_(int(length))
         self._len_host[slot] = int(length)
+
+    # ---- slot snapshots: a running stream moves between slots, converters, batch sizes, hops and processes
+    def _check_slot(self, slot: int) -> int:
+        if not 0 <= int(slot) < self.streams:
+            raise ValueError(f"slot {slot} outside [0, {self.streams})")
+        return int(slot)
+
+    def snapshot_tag(self) -> int:
+        """The layout fingerprint of this converter's snapshots (the model's: no batch, no hop in it)."""
+        return self.engine.stream_snapshot_tag()
+
+    def _check_origin(self, tag: int, rng) -> None:
+        """What import_slot / move_slots refuse, before anything is launched: a snapshot of another layout, or one drawn
+        from the generator under another (seed, noise_scale)."""
+        if tag != self.snapshot_tag():
+            raise ValueError(f"snapshot tag {tag:#018x} is not this model's ({self.snapshot_tag():#018x}): another geometry or operand type")
+        if rng is not None and rng != self._rng:
+            raise ValueError(f"the snapshot draws its noise from the generator under (seed, noise_scale) = {rng}, this converter under {self._rng}")
+
+    def export_slot(self, slot: int) -> StreamSnapshot:
+        """The stream in ``slot`` as it stands between two calls (qvc_stream_export_slots on the side stream; the slot is
+        only read and keeps running).  Nothing synchronises: position, length and key come from the host mirrors."""
+        from .engine import aligned_empty
+        slot = self._check_slot(slot)
+        dev = self.engine.device
+        with torch.cuda.stream(self._stream):
+            data = aligned_empty(self.engine.stream_snapshot_bytes(), dev)
+            self.engine.stream_export_slots(self._state, self.streams, self.hop, [slot], self._pos, self._len, data)
+            g = self._g[slot].clone()
+        cur = torch.cuda.current_stream(dev)
+        cur.wait_stream(self._stream)
+        data.record_stream(cur)
+        g.record_stream(cur)
+        return StreamSnapshot(self.snapshot_tag(), data, g, self._keys_host[slot], self._pos_host[slot], self._len_host[slot], self._rng)
+
+    def import_slot(self, slot: int, snap: StreamSnapshot) -> None:
+        """Continue the stream of ``snap`` in ``slot``: the kept frames of every ring, the position and the length
+        (qvc_stream_import_slots), ``g[slot]``, the slot's generator key and the host mirrors.  The other slots and the
+        captured graph are untouched.  ValueError -- before anything is launched -- when the snapshot's layout tag is not
+        this model's, or when it was drawn from the generator under a (seed, noise_scale) other than this converter's."""
+        from .engine import aligned_empty
+        slot = self._check_slot(slot)
+        self._check_origin(snap.tag, snap.rng)
+        n = self.engine.stream_snapshot_bytes()
+        if snap.data.numel() != n or snap.data.dtype != torch.uint8 or snap.g.numel() != self._g.shape[1]:
+            raise ValueError(f"a snapshot of this model is {n} bytes with a g of {self._g.shape[1]}, got {snap.data.numel()} and {snap.g.numel()}")
+        dev = self.engine.device
+        self._after_caller(snap.data, snap.g)
+        with torch.cuda.stream(self._stream):
+            data = snap.data
+            if data.device != dev or data.data_ptr() % 256 or not data.is_contiguous():
+                data = aligned_empty(n, dev)
+                data.copy_(snap.data, non_blocking=True)
+            self.engine.stream_import_slots(self._state, self.streams, self.hop, [slot], self._pos, self._len, data)
+            self._g[slot].copy_(snap.g.reshape(-1), non_blocking=True)
+            self._keys[slot:slot + 1].fill_(snap.key - (1 << 64) if snap.key >> 63 else snap.key)
+        self._keys_host[slot] = snap.key
+        self._pos_host[slot], self._len_host[slot] = snap.position, snap.length
+
+    def free_slot(self, slot: int) -> None:
+        """Leave ``slot`` idle: zeroed rows, position 0, length 0 -- an empty stream, whose rows of the output are zeros."""
+        slot = self._check_slot(slot)
+        self._after_caller()
+        with torch.cuda.stream(self._stream):
+            self._engine_reset_slot(slot, 0)
+        self._pos_host[slot], self._len_host[slot] = 0, 0
+
+    def occupied(self, slot: int) -> bool:
+        """``slot`` carries a stream that still has output to come (a slot no stream was ever admitted into counts: its
+        length is unknown; ``free_slot`` or ``end_slot(slot, 0)`` says otherwise)."""
+        return self._len_host[slot] > 0 and not self.finished(slot)
+
+    def move_slots(self, slots, dst: "StreamConverter", dst_slots) -> None:
+        """Move the streams in ``slots`` into ``dst_slots`` of ``dst`` -- this converter or another one of the same model, of
+        any batch size and hop -- in ONE export and ONE import call, and leave the slots they came from idle
+        (``free_slot``).  Feed the streams into ``dst`` from the next call on.  The snapshots stay on the device; the two
+        side streams are ordered by ``wait_stream``.  ValueError, before anything is launched, as ``import_slot``."""
+        from .engine import aligned_empty
+        slots, dst_slots = [self._check_slot(s) for s in slots], [dst._check_slot(s) for s in dst_slots]
+        if len(slots) != len(dst_slots) or len(set(slots)) != len(slots) or len(set(dst_slots)) != len(dst_slots):
+            raise ValueError(f"move_slots needs as many distinct destination slots as distinct source slots, got {slots} -> {dst_slots}")
+        dst._check_origin(self.snapshot_tag(), self._rng)
+        if not slots or (dst is self and slots == dst_slots):
+            return
+        dev = self.engine.device
+        if dst.engine.device != dev:
+            raise ValueError("move_slots stays on one device: between devices use export_slot, StreamSnapshot.to and import_slot")
+        with torch.cuda.stream(self._stream):
+            data = aligned_empty(len(slots) * self.engine.stream_snapshot_bytes(), dev)
+            self.engine.stream_export_slots(self._state, self.streams, self.hop, slots, self._pos, self._len, data)
+            g, keys = self._g[slots], self._keys[slots]                     # copies: a move inside one converter may overlap
+        if dst is not self:
+            dst._stream.wait_stream(self._stream)
+            for t in (data, g, keys):
+                t.record_stream(dst._stream)
+        with torch.cuda.stream(dst._stream):
+            dst.engine.stream_import_slots(dst._state, dst.streams, dst.hop, dst_slots, dst._pos, dst._len, data)
+            dst._g[dst_slots] = g
+            dst._keys[dst_slots] = keys
+        moved = [(self._keys_host[s], self._pos_host[s], self._len_host[s]) for s in slots]
+        for s, (key, position, length) in zip(dst_slots, moved):
+            dst._keys_host[s], dst._pos_host[s], dst._len_host[s] = key, position, length
+        for s in slots:
+            if dst is not self or s not in dst_slots:
+                self.free_slot(s)
+
+    def move_slot(self, slot: int, dst: "StreamConverter", dst_slot: int) -> None:
+        """``move_slots`` for one stream."""
+        self.move_slots([slot], dst, [dst_slot])
+
+    def rebuilt(self, streams: Optional[int] = None, hop_frames: Optional[int] = None) -> "StreamConverter":
+        """A new converter of the same class, model, seed and graph setting with ``streams`` slots and ``hop_frames`` per
+        call (default: this converter's); every occupied slot is carried over into the same slot number, the others are
+        idle.  The elastic batch and the change of hop: the streams go on where they were, nothing is cut.  ValueError
+        if ``streams`` is too small for the occupied slots."""
+        streams = self.streams if streams is None else int(streams)
+        carried = [s for s in range(self.streams) if self.occupied(s)]
+        if carried and carried[-1] >= streams:
+            raise ValueError(f"slot {carried[-1]} carries a stream: {streams} slots are too few")
+        seed, scale = self._rng if self._rng is not None else (None, 1.0)
+        new = type(self)(self.model, streams, self.hop if hop_frames is None else int(hop_frames), use_graph=self._use_graph, seed=seed,
+                         noise_scale=scale)
+        self.move_slots(carried, new, carried)
+        for s in range(min(streams, self.streams)):
+            if s not in carried:
+                new.free_slot(s)
+        return new
 
     def position(self, slot: int) -> int:
         """First frame the NEXT step feeds into ``slot`` (host mirror of the device counter)."""
@@ -303,6 +486,7 @@ class StreamConverter:
                 raise ValueError(f"{S} streams need {S} keys, got {len(u64)}")
             with torch.cuda.stream(self._stream):
                 self._keys.copy_(torch.tensor([k - (1 << 64) if k >> 63 else k for k in u64], dtype=torch.int64))
+            self._keys_host = list(u64)
         else:
             pad_n = torch.nn.functional.pad(noise.to(dev, torch.float32), (nl, h + lag))   # frame f of the noise sits at column f + nl
         steps = -(-(T + lag) // h)
@@ -401,6 +585,14 @@ class LiveConverter(StreamConverter):
 
     def _engine_reset_slot(self, slot: int, length: int) -> None:
         self.engine.live_reset_slot(self._state, self.streams, self.hop, self.look_ahead, slot, length, self._pos, self._len)
+
+    # the window's state is the caller's own last context + look_ahead input frames: there is nothing computed to carry
+    def _no_snapshots(self, *_args, **_kw):
+        raise ValueError(f"{type(self).__name__} has no slot snapshots: its state is not covered, it is the caller's last C + L input frames "
+                         "(context + look_ahead), which the caller can feed again; snapshots cover the segment rings "
+                         "(StreamConverter, StreamTickConverter)")
+
+    export_slot = import_slot = move_slot = move_slots = rebuilt = snapshot_tag = _no_snapshots
 
 
 class TickConverter(_Ticks, LiveConverter):

@@ -9,7 +9,8 @@
 // oracle/_build/libqvc_emu_twin.so and loaded only by the tests.  The same backend states kStreamTick and adds the host
 // version of the count-aware batched copy (csrc/qvc_small.hip: copy_counted_kernel), on which stream_tick is instantiated.
 // RecordingBackend derives from CountingBackend and writes down every copy_batch / copy_counted call of one stream_step
-// or stream_tick, descriptor by descriptor (qvc_emu_stream_moves; tests/test_stream_moves_host.py).  The emulation's
+// or stream_tick, descriptor by descriptor (qvc_emu_stream_moves; tests/test_stream_moves_host.py).  The slot snapshots
+// (snapshot_slots: qvc_emu_stream_export_slots / _import_slots) run on the same host copy_batch.  The emulation's
 // backend has no single-band tail and no generator form of the noise: band-synthesis decoders, pointer form only.
 // TraceBackend stands alone: it computes nothing and writes down every backend call of a Path, field by field
 // (qvc_emu_path_trace; tests/test_path_trace_host.py) -- every decoder and every form, since nothing is run.
@@ -621,6 +622,21 @@ int qvc_emu_stream_reset_slot(const qvc_config* cfg, void* state, int64_t state_
   }, [](char* p, size_t n) { std::memset(p, 0, n); });
   if (st == QVC_OK) { pos[slot] = 0; lens[slot] = length; }
   return st;
+}
+
+// Same signatures as qvc_stream_export_slots / qvc_stream_import_slots, host pointers, no stream: the same checks and the
+// same descriptors (snapshot_slots of csrc/qvc_stream.h), run by the host copy_batch.
+int qvc_emu_stream_export_slots(const qvc_config* cfg, const void* state, int64_t state_bytes, int32_t batch, int32_t hop,
+                                const int32_t* slots, int32_t n_slots, const int32_t* pos, const int32_t* lens, void* snap, int64_t snap_bytes) {
+  CountingBackend be;
+  return qvc::snapshot_slots(false, be, cfg, const_cast<void*>(state), state_bytes, batch, hop, slots, n_slots, const_cast<int32_t*>(pos),
+                             const_cast<int32_t*>(lens), snap, snap_bytes);
+}
+
+int qvc_emu_stream_import_slots(const qvc_config* cfg, void* state, int64_t state_bytes, int32_t batch, int32_t hop, const int32_t* slots,
+                                int32_t n_slots, int32_t* pos, int32_t* lens, const void* snap, int64_t snap_bytes) {
+  CountingBackend be;
+  return qvc::snapshot_slots(true, be, cfg, state, state_bytes, batch, hop, slots, n_slots, pos, lens, const_cast<void*>(snap), snap_bytes);
 }
 
 // Ring `ring` of the segment rings' table for slot `slot`: v = {offset of the slot's rows in the state, their bytes

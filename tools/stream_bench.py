@@ -12,7 +12,11 @@ copied into the converter's count tensor on the device in front of every replay 
 tick rows).
 With --ring-ticks, ONLY (f): per hop the lockstep StreamConverter.step -- the yardstick -- against StreamTickConverter --
 the tick form of the segment rings, qvc_stream_tick -- under the same three patterns, timed the same way.
-usage: python tools/stream_bench.py [--live L[,L...]] [--ticks | --ring-ticks] [streams] [hop_frames ...]"""
+With --migrate, ONLY (g): slot snapshots (qvc_stream_export_slots / _import_slots) between two StreamConverters of
+`streams` slots, hop 16 -> 16 and hop 16 -> 320: the device time of one export call plus one import call for 1 slot and for
+all slots (events on one stream, median of rounds), the wall time of StreamConverter.move_slot slot by slot and of
+move_slots in one call (synchronised at both ends; the freeing of the source slots included), and the step times beside them.
+usage: python tools/stream_bench.py [--live L[,L...]] [--ticks | --ring-ticks | --migrate] [streams] [hop_frames ...]"""
 import json
 import os
 import random
@@ -158,8 +162,60 @@ def tick_rows(model, streams, hop, looks, rounds=5, n=20):
     return out
 
 
+def migrate_rows(model, streams, src_hop=16, dst_hops=(16, 320), rounds=7, n=10):
+    """ms to move 1 slot and all `streams` slots from a hop-`src_hop` converter into converters of `dst_hops`."""
+    import time
+    from quickvc_official_amd.engine import aligned_empty
+    eng = model.engine()
+    src = StreamConverter(model, streams, hop_frames=src_hop)
+    n_snap = eng.stream_snapshot_bytes()
+    res = {"snapshot_bytes_per_slot": n_snap, "snapshot_tag": f"{eng.stream_snapshot_tag():#018x}", "source_hop": src_hop,
+           "source_ms_per_step": timed_replays(src)}
+    snap = aligned_empty(streams * n_snap, eng.device)
+    mid = lambda v: sorted(v)[len(v) // 2]
+    for hop in dst_hops:
+        dst = StreamConverter(model, streams, hop_frames=hop)
+        row = {"dest_ms_per_step": timed_replays(dst)}
+        for label, slots in (("1_slot", [streams // 2]), ("all_slots", list(range(streams)))):
+            dev_ms, wall_ms, call_ms = [], [], []
+            for _ in range(rounds):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                with torch.cuda.stream(src._stream):
+                    e0.record(src._stream)
+                    for _i in range(n):
+                        eng.stream_export_slots(src._state, streams, src_hop, slots, src._pos, src._len, snap)
+                        eng.stream_import_slots(dst._state, streams, hop, slots, dst._pos, dst._len, snap)
+                    e1.record(src._stream)
+                src._stream.synchronize()
+                dev_ms.append(e0.elapsed_time(e1) / n)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for b in slots:
+                    src.move_slot(b, dst, b)
+                torch.cuda.synchronize()
+                wall_ms.append((time.perf_counter() - t0) * 1e3)
+                src.reset()                      # the moved slots were freed: all slots live again for the next round
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                src.move_slots(slots, dst, slots)
+                torch.cuda.synchronize()
+                call_ms.append((time.perf_counter() - t0) * 1e3)
+                src.reset()
+            row[label] = {"export_plus_import_device_ms": mid(dev_ms), "device_ms_rounds": [round(v, 4) for v in dev_ms],
+                          "move_slot_one_by_one_wall_ms": mid(wall_ms), "one_by_one_wall_ms_rounds": [round(v, 4) for v in wall_ms],
+                          "move_slots_one_call_wall_ms": mid(call_ms), "one_call_wall_ms_rounds": [round(v, 4) for v in call_ms],
+                          "bytes_moved": len(slots) * n_snap}
+        res[f"hop_{src_hop}_to_{hop}"] = row
+        del dst
+        torch.cuda.empty_cache()
+    return res
+
+
 def main():
     argv = sys.argv[1:]
+    migrate = "--migrate" in argv
+    if migrate:
+        argv.remove("--migrate")
     looks = None
     ticks = "--ticks" in argv
     if ticks:
@@ -177,6 +233,9 @@ def main():
     model.load_state_dict(make_synthetic_state_dict(model, 1234))
     model = model.cuda().eval()
     spf = model.samples_per_frame
+    if migrate:
+        print(json.dumps({"streams": streams, "migrate": migrate_rows(model, streams)}))
+        return
     if ring_ticks:
         res = {"streams": streams, "ring_ticks": {}}
         for hop in hops:
