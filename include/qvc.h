@@ -348,14 +348,16 @@ int qvc_live_reset_slot(const qvc_config* cfg, void* state, int64_t state_bytes,
  *   pos_dev    advanced on the device by the call: pos[b] += n (hence not const)
  * A slot with n = 0 leaves no trace: ring rows and pos bit for bit as they were, a row of zeros in `out`, its tiles
  * return at once.  One captured graph of the call replays for any tick pattern: only the contents of n_new_dev,
- * pos_dev, len_dev, unit_new and noise_new change between replays.  With every n = hop the outputs are bit for bit
- * qvc_live_step's.  With L = C the concatenated output of a stream is its whole-utterance conversion however the
+ * pos_dev, len_dev, unit_new and noise_new change between replays.  With every n = hop the outputs, and the ring bytes
+ * a later call can read, are bit for bit qvc_live_step's.  With L = C the concatenated output of a stream is its whole-utterance conversion however the
  * stream was cut into ticks; with L < C a frame is delivered with between L and L + n - 1 frames of look-ahead, so the
  * output legitimately depends on the cut.
- *   state      caller-owned device buffer of qvc_live_tick_state_bytes(), started per slot with
- *              qvc_live_tick_reset_slot.  Between ticks ring row r of slot b holds frame pos[b] - W + r: the last W
- *              frames RIGHT-aligned (qvc_live_step keeps W - hop frames left-aligned).  The two states are therefore
- *              never exchanged: a tick state is never passed to qvc_live_step, a lockstep state never to these calls.
+ *   state      the state of qvc_live_step: qvc_live_state_bytes(), started per slot with qvc_live_reset_slot
+ *              (qvc_live_tick_state_bytes and qvc_live_tick_reset_slot are other names for the same two calls).  Between
+ *              calls, ring row r of slot b holds frame pos[b] - (W - hop) + r for r in [0, W - hop): the last W - hop
+ *              frames, left-aligned; the hop rows behind them are rewritten before they are read.  Both calls leave the
+ *              rings like that, so a server may switch between qvc_live_step and qvc_live_tick on one state at any call
+ *              (the caller advances pos after a step; a tick advances it itself).
  *   workspace  qvc_live_tick_workspace_bytes() (more than qvc_live_workspace_bytes())
  * Errors as qvc_live_step; n_new_dev == NULL: QVC_ERR_BAD_ARG.  The segment rings have a tick form of their own:
  * qvc_stream_tick, below. */

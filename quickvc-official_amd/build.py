@@ -110,7 +110,7 @@ def build_emu(force: bool = False) -> str:
 
 def build_emu_twin(force: bool = False) -> str:
     """The CPU twin of qvc_live_step and qvc_live_tick (tests only): tools/emu_twin.cpp includes the frozen
-    oracle/qvc_emu.cpp, derives a backend with host versions of the tick's ring update and delivery from its EmuBackend
+    oracle/qvc_emu.cpp, derives a backend with the host version of the count-aware batched copy from its EmuBackend
     and adds qvc_emu_live_step / qvc_emu_live_tick / qvc_emu_stream_tick -- a library of its own, the emulation library stays as it was."""
     os.makedirs(EMU_DIR, exist_ok=True)
     srcs = [os.path.join(ROOT, "tools", "emu_twin.cpp"), os.path.join(CSRC, "qvc_pack.cpp")]

@@ -74,10 +74,7 @@ struct HipBackend {
   int post_tail(const ConvDesc& d, const PostTailArgs& a, int batch, int dtype) { return launch_post_tail(d, a, batch, dtype, stream); }
   int zero(void* p, size_t bytes) { return hipMemsetAsync(p, 0, bytes, stream) == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH; }
   int copy_batch(const CopyDesc* d, int n) { return launch_copy_batch(d, n, stream); }
-  static constexpr bool kLiveTick = true;         // live_tick: the ring update and the delivery driven by device counts
-  int tick_rings(const TickRingsArgs& a) { return launch_tick_rings(a, stream); }
-  int tick_deliver(const TickDeliverArgs& a) { return launch_tick_deliver(a, stream); }
-  static constexpr bool kStreamTick = true;       // stream_tick: copy_batch's job with the bytes per slot taken from device counts
+  static constexpr bool kStreamTick = true;       // stream_tick, live_tick: copy_batch's job with the bytes per slot taken from device counts
   int copy_counted(const CountedHead& h, const CountedDesc* d, int n) { return launch_copy_counted(h, d, n, stream); }
 };
 using Ctx = Path<HipBackend>;
@@ -666,8 +663,7 @@ int qvc_live_reset_slot(const qvc_config* cfg, void* state, int64_t state_bytes,
   });
 }
 
-// The tick state is carved as the lockstep state (one unit ring and one noise ring of W frames per stream); what differs
-// is what the rings hold between calls (right-aligned, qvc_stream.h), so the two are never exchanged.
+// The tick state IS the lockstep state (qvc_stream.h: live_rings, SHARED): the two names below are kept as aliases.
 int64_t qvc_live_tick_state_bytes(const qvc_config* cfg, int32_t batch, int32_t hop, int32_t look_ahead) {
   return qvc_live_state_bytes(cfg, batch, hop, look_ahead);
 }
@@ -697,7 +693,6 @@ int qvc_live_tick_rng(const qvc_config* cfg, const void* blob_dev, void* state, 
 
 int qvc_live_tick_reset_slot(const qvc_config* cfg, void* state, int64_t state_bytes, int32_t batch, int32_t hop, int32_t look_ahead,
                              int32_t slot, int32_t length, int32_t* pos_dev, int32_t* len_dev, void* stream) {
-  // the slot's ring rows zeroed, pos = 0: row r holds frame r - W < 0, which every launch masks -- the invariant holds
   return qvc_live_reset_slot(cfg, state, state_bytes, batch, hop, look_ahead, slot, length, pos_dev, len_dev, stream);
 }
 

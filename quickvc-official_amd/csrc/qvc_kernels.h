@@ -448,38 +448,15 @@ struct CopyDesc {
 constexpr int kCopyBatchMax = 12;
 int launch_copy_batch(const CopyDesc* d, int n, void* stream);
 
-// ---- the tick form of the windowed step (qvc_stream.h: live_tick): slot b brings n = clamp(n_new[b], 0, hop) frames,
-//      the counts in device memory, so what moves is decided on the device.  One definition of the clamp for the
-//      kernels and the host twin.
+// ---- the tick forms (qvc_stream.h: stream_tick, live_tick): slot b brings n = clamp(n_new[b], 0, hop) frames, the counts
+//      in device memory, so what moves is decided on the device.  One definition of the clamp for the kernel and the
+//      host twin.
 QVC_HD int tick_count(const int32_t* n_new, int b, int hop) {
   const int n = n_new[b];
   return n < 0 ? 0 : (n < hop ? n : hop);
 }
-// Opens a tick.  Every ring row (fp32, W frames; unit: B * UC rows, noise: B * NC rows or none) of a slot with n > 0 is
-// shifted left by n frames in place and the first n columns of the slot's row of unit_new / noise_new (pitch hop)
-// appended: the ring keeps the last W frames right-aligned.  A slot with n == 0 is not touched.  The same launch writes
-// the position and length the path's launches see in this tick:
-//     n > 0:  pos_eff[b] = pos[b] + n - hop (buffer row W - hop is that absolute frame; negative early in a stream),
-//             len_eff[b] = lens[b]
-//     n == 0: pos_eff[b] = W, len_eff[b] = 0 -- an empty sequence in every segment: its tiles return at once
-struct TickRingsArgs {
-  float* unit_ring = nullptr; const float* unit_new = nullptr;
-  float* noise_ring = nullptr; const float* noise_new = nullptr;   // both null: the generator form keeps no noise ring
-  int32_t B = 0, UC = 0, NC = 0, W = 0, hop = 0;
-  const int32_t* n_new = nullptr; const int32_t* pos = nullptr; const int32_t* lens = nullptr;
-  int32_t* pos_eff = nullptr; int32_t* len_eff = nullptr;
-};
-// Closes a tick.  out[b] (hop * spf floats) = the slot's last n delivered frames -- rows [first + hop - n, first + hop)
-// of wave (B, rows * spf) -- then zeros; pos[b] += n.  A slot with n == 0 gets zeros and keeps its pos; wave is not read.
-struct TickDeliverArgs {
-  const float* wave = nullptr; float* out = nullptr;
-  int32_t B = 0, rows = 0, first = 0, hop = 0, spf = 0;
-  const int32_t* n_new = nullptr; int32_t* pos = nullptr;
-};
-int launch_tick_rings(const TickRingsArgs& a, void* stream);
-int launch_tick_deliver(const TickDeliverArgs& a, void* stream);
 
-// ---- the tick form of the segment rings (qvc_stream.h: stream_tick): copy_batch's job -- several independent strided
+// ---- the mover of a tick (qvc_stream.h: CountedQueue): copy_batch's job -- several independent strided
 //      copies / zero fills in ONE launch -- with what moves per slot decided on the device by n = tick_count(n_new, slot,
 //      hop).  A descriptor covers `slots` slots of `rows` rows each; slot s starts s * rows * dpitch bytes into dst and
 //      s * rows * spitch bytes into src.  Of every row of a slot it writes `width` bytes:
@@ -503,6 +480,8 @@ constexpr uint32_t kCountedIdleZero = 1u;
 //   pos_eff / len_eff (with pos and lens; all four or none): what the segments' launches see in this tick --
 //       n > 0: pos[b], lens[b];   n == 0: idle_pos, 0 -- an empty sequence in every segment (idle_pos >= every segment's
 //       Ragged::off), so an idle slot's tiles return at once
+//       len_cap (the window, live_tick): n > 0: len_eff[b] = min(lens[b], pos[b] + n) -- the sequence ends behind the
+//       slot's n new frames, so the zero-filled rows behind them are past its end and not frames of it
 //   pos_add: pos_add[b] += n (nothing else in the same launch may read it)
 struct CountedHead {
   const int32_t* n_new = nullptr;
@@ -511,7 +490,13 @@ struct CountedHead {
   int32_t* pos_eff = nullptr; int32_t* len_eff = nullptr;
   int32_t idle_pos = 0;
   int32_t* pos_add = nullptr;
+  bool len_cap = false;
 };
+// len_eff of a slot with n > 0 new frames: one definition for the kernel and the host twin
+QVC_HD int counted_len(const CountedHead& h, int b, int n) {
+  const int len = h.lens[b], end = h.pos[b] + n;
+  return h.len_cap && end < len ? end : len;
+}
 int launch_copy_counted(const CountedHead& h, const CountedDesc* d, int n, void* stream);
 int launch_sample(const SampleArgs& a, void* stream);
 int launch_sample_rows(const SampleRowsArgs& a, void* stream);

@@ -461,81 +461,6 @@ int launch_copy_batch(const CopyDesc* d, int n, void* stream) {
   return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
 }
 
-// ------------------------------------------------------------------ the tick form's ring update and delivery (qvc_stream.h)
-// One wave per ring row.  A row is W floats and the shift is n floats -- 4-byte aligned only --, so the row moves as
-// scalar floats: a pass of 64 * kTickPer of them is read (frame r + n, or the new frame r - (W - n)) before any of the
-// pass is written.  A pass writes [base, base + 256) and every later pass reads from base + 256 + n on, so one barrier
-// per pass orders everything.  n is uniform in the workgroup: the early return and the barrier are not divergent.
-constexpr int kTickPer = 4;
-__global__ __launch_bounds__(64) void tick_rings_kernel(const TickRingsArgs a) {
-  const int urows = a.B * a.UC;
-  const bool is_unit = (int)blockIdx.x < urows;
-  const int row = is_unit ? (int)blockIdx.x : (int)blockIdx.x - urows;
-  const int ch = is_unit ? a.UC : a.NC;
-  const int b = row / ch;
-  const int n = tick_count(a.n_new, b, a.hop);
-  if (is_unit && row == b * ch && threadIdx.x == 0) {
-    a.pos_eff[b] = n > 0 ? a.pos[b] + n - a.hop : a.W;
-    a.len_eff[b] = n > 0 ? a.lens[b] : 0;
-  }
-  if (n == 0) return;
-  float* ring = (is_unit ? a.unit_ring : a.noise_ring) + (size_t)row * a.W;
-  const float* fresh = (is_unit ? a.unit_new : a.noise_new) + (size_t)row * a.hop;
-  const int keep = a.W - n;
-  for (int base = 0; base < a.W; base += 64 * kTickPer) {
-    float v[kTickPer];
-#pragma unroll
-    for (int k = 0; k < kTickPer; ++k) {
-      const int r = base + k * 64 + (int)threadIdx.x;
-      v[k] = 0.f;
-      if (r < a.W) v[k] = r < keep ? ring[r + n] : fresh[r - keep];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < kTickPer; ++k) {
-      const int r = base + k * 64 + (int)threadIdx.x;
-      if (r < a.W) ring[r] = v[k];
-    }
-  }
-}
-
-int launch_tick_rings(const TickRingsArgs& a, void* stream) {
-  if (!a.unit_ring || !a.unit_new || !a.n_new || !a.pos || !a.lens || !a.pos_eff || !a.len_eff) return QVC_ERR_BAD_ARG;
-  if ((a.noise_ring == nullptr) != (a.noise_new == nullptr)) return QVC_ERR_BAD_ARG;
-  if (a.B < 1 || a.UC < 1 || a.hop < 1 || a.W <= a.hop || (a.noise_ring && a.NC < 1)) return QVC_ERR_BAD_ARG;
-  const int64_t rows = (int64_t)a.B * (a.UC + (a.noise_ring ? a.NC : 0));
-  if (rows >= (1ll << 31)) return QVC_ERR_BAD_ARG;
-  hipLaunchKernelGGL(tick_rings_kernel, dim3((unsigned)rows), dim3(64), 0, static_cast<hipStream_t>(stream), a);
-  return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
-}
-
-// out[b] = the last n delivered frames, then zeros (scalar floats: the source starts (first + hop - n) * spf floats
-// into the slot's waveform); pos[b] += n by one thread, after which nothing in the tick reads it.
-constexpr int kDeliverPer = 4;
-__global__ __launch_bounds__(256) void tick_deliver_kernel(const TickDeliverArgs a) {
-  const int b = blockIdx.y;
-  const int n = tick_count(a.n_new, b, a.hop);
-  const int total = a.hop * a.spf, valid = n * a.spf;
-  const float* src = a.wave + ((size_t)b * a.rows + (size_t)(a.first + a.hop - n)) * a.spf;
-  float* dst = a.out + (size_t)b * total;
-#pragma unroll
-  for (int k = 0; k < kDeliverPer; ++k) {
-    const int e = ((int)blockIdx.x * kDeliverPer + k) * 256 + (int)threadIdx.x;
-    if (e < total) dst[e] = e < valid ? src[e] : 0.f;
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0 && n > 0) a.pos[b] += n;
-}
-
-int launch_tick_deliver(const TickDeliverArgs& a, void* stream) {
-  if (!a.wave || !a.out || !a.n_new || !a.pos) return QVC_ERR_BAD_ARG;
-  if (a.B < 1 || a.B > 65535 || a.hop < 1 || a.spf < 1 || a.first < 0 || a.first + a.hop > a.rows) return QVC_ERR_BAD_ARG;
-  const int64_t total = (int64_t)a.hop * a.spf;
-  if (total >= (1ll << 31) - 256 * kDeliverPer) return QVC_ERR_BAD_ARG;     // 32-bit element index in the kernel
-  const unsigned gx = (unsigned)((total + 256 * kDeliverPer - 1) / (256 * kDeliverPer));
-  hipLaunchKernelGGL(tick_deliver_kernel, dim3(gx, (unsigned)a.B), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
-}
-
 // ------------------------------------------------------------------ count-aware batched copies (qvc_stream.h: stream_tick)
 // copy_batch_kernel's job with the bytes per slot taken from n_new on the device.  A workgroup serves one chunk of ONE
 // slot of one descriptor, so n is uniform in it: the early return of an idle slot and the choice of the vector width
@@ -583,7 +508,7 @@ __global__ __launch_bounds__(256) void copy_counted_kernel(const CopyCountedArgs
       const int nb = tick_count(a.h.n_new, b, a.h.hop);
       if (a.h.pos_eff) {
         a.h.pos_eff[b] = nb > 0 ? a.h.pos[b] : a.h.idle_pos;
-        a.h.len_eff[b] = nb > 0 ? a.h.lens[b] : 0;
+        a.h.len_eff[b] = nb > 0 ? counted_len(a.h, b, nb) : 0;
       }
       if (a.h.pos_add && nb > 0) a.h.pos_add[b] += nb;
     }

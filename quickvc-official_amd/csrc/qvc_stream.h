@@ -21,9 +21,9 @@
 // Sequence starts and ends inside a window are exact: every kernel masks its input rows by the absolute position
 // of the window (Ragged: pos / lens), i.e. each conv zero-pads at the sequence's own ends.
 //
-// Three bodies share this file: stream_run (the segment rings above -- stream_step and stream_tick, the step with per-slot
-// frame counts on the same state, are that ONE body on two movers), live_step (one window over the whole path, below) and
-// live_tick (live_step with per-slot frame counts).  What they share is stated once:
+// Two bodies share this file, each ONE body on two movers -- the step, and the tick: the step with per-slot frame counts on
+// the same state: stream_run (the segment rings above: stream_step and stream_tick) and live_run (one window over the
+// whole path, below: live_step and live_tick).  What they share is stated once:
 //   Rings         the ring table of a driver (stream_rings / live_rings): where every ring lies in the state and its
 //                 geometry.  The state size, the slide buffers of the scratch, the slide loops and the per-slot reset
 //                 (reset_slot, slot_range) all read the table, so a ring is added or resized in ONE place.  So do the
@@ -36,7 +36,8 @@
 //                   zeros   a zero fill
 //                   append / slide_out / slide_back   a ring's new frames behind its kept ones; the kept parts out to the
 //                           slide buffers and back in (RingMoves: written once on fresh / slid / kept)
-//                   open    the pos / lens arrays the segments' launches read;  advance: the stream positions move on
+//                   open    the pos / lens arrays the segments' launches read (prefix: a tick's sequence ends behind the
+//                           slot's new frames);  advance: the stream positions move on
 //                   flush   what was queued since the last flush runs as ONE launch;  ok / st: the first error
 //   Segments      the factory of a step's Path segments.
 //   stream_checks the pure-host checks of an entry point (the C ABI's scaffold in qvc_api.hip and the CPU twin call it).
@@ -179,7 +180,7 @@ struct CopyQueue : RingMoves<CopyQueue<Backend_>> {
     kept(dst, dpitch, static_cast<const char*>(src) + hop * frame, spitch, bytes, rows);
   }
   void zeros(void* dst, size_t dpitch, size_t width, size_t rows) { add(dst, dpitch, nullptr, 0, width, B * rows); }
-  StreamPos open(const int32_t* pos, const int32_t* lens, int, int32_t*, int32_t*) { return {pos, lens}; }
+  StreamPos open(const int32_t* pos, const int32_t* lens, int, int32_t*, int32_t*, bool = false) { return {pos, lens}; }
   void advance(const int32_t*) {}
 };
 
@@ -205,7 +206,7 @@ struct CountedQueue : RingMoves<CountedQueue<Backend_>> {
   void flush() {
     if (n) ok(be.copy_counted(head, cd, n));
     n = 0;
-    head.pos = head.lens = nullptr; head.pos_eff = head.len_eff = head.pos_add = nullptr;
+    head.pos = head.lens = nullptr; head.pos_eff = head.len_eff = head.pos_add = nullptr; head.len_cap = false;
   }
   // per slot `rows` rows: `fixed + n * unit` bytes from src (read from byte n * shift of the row on), zeros up to width
   void add(void* dst, size_t dpitch, const void* src, size_t spitch, size_t fixed, size_t unit, size_t shift, size_t width, size_t rows,
@@ -224,9 +225,10 @@ struct CountedQueue : RingMoves<CountedQueue<Backend_>> {
     add(dst, dpitch, src, spitch, bytes, 0, frame, bytes, rows);
   }
   void zeros(void* dst, size_t dpitch, size_t width, size_t rows) { add(dst, dpitch, nullptr, 0, 0, 0, 0, width, rows); }
-  // the next launch writes what the segments see: n > 0: pos[b], lens[b];  n == 0: idle_pos, 0 (an empty sequence)
-  StreamPos open(const int32_t* pos, const int32_t* lens, int idle_pos, int32_t* pos_eff, int32_t* len_eff) {
-    head.pos = pos; head.lens = lens; head.pos_eff = pos_eff; head.len_eff = len_eff; head.idle_pos = idle_pos;
+  // the next launch writes what the segments see: n > 0: pos[b], lens[b];  n == 0: idle_pos, 0 (an empty sequence).
+  // prefix: the sequence ends behind the slot's new frames, min(lens[b], pos[b] + n) (the window: live_run)
+  StreamPos open(const int32_t* pos, const int32_t* lens, int idle_pos, int32_t* pos_eff, int32_t* len_eff, bool prefix = false) {
+    head.pos = pos; head.lens = lens; head.pos_eff = pos_eff; head.len_eff = len_eff; head.idle_pos = idle_pos; head.len_cap = prefix;
     return {pos_eff, len_eff};
   }
   void advance(int32_t* pos) { head.pos_add = pos; }   // the next launch: pos[b] += n
@@ -667,9 +669,12 @@ inline int live_plan(const qvc_config* cfg, int hop, int look_ahead, Plan& P, Li
   return QVC_OK;
 }
 
-// The window's rings, live_step's and live_tick's alike (what they hold between calls differs: see live_tick):
+// The window's rings, live_step's and live_tick's alike:
 //   unit    fp32 (B, unit_channels, W), the reference's (B, C, T) layout
 //   noise   fp32 (B, inter_channels, W): the noise of the same frames (pointer form only)
+//     INVARIANT  between calls both are left-aligned: row r of slot b holds frame pos[b] - (W - hop) + r, for r in
+//                [0, W - hop); the hop rows behind are rewritten before they are read.
+//     SHARED     live_step and live_tick both keep it, so a server may switch between the two calls on one state.
 inline Rings live_rings(const Plan& P, const LiveGeom& G, int B) {
   Rings R;
   const int64_t keep = (int64_t)(G.W - G.hop) * 4, hopb = (int64_t)G.hop * 4;
@@ -763,24 +768,26 @@ int live_window(const Plan& P, const LiveGeom& G, const LiveScratch& X, const ch
   return q.st;
 }
 
-// One step (G from live_plan).  Backend: as stream_step.  The rings are kept LEFT-aligned between steps: the W - hop
-// kept frames in front, slid by copy_batch.
+// One call of the window, step or tick (G from live_plan): as in stream_run, what moves per slot is the mover's business
+// and everything else is written here once -- the new frames behind the kept ones, the path over the window, the delivery
+// and the two slide launches.  Arguments for a step (live_tick states what a tick changes):
 //   unit_new  (B, unit_channels, hop) fp32: unit frames [pos, pos + hop) of every stream
 //   noise_new (B, inter, hop) fp32:         the N(0,1) draw of models.py:94 for the SAME frames (no noise lag)
 //   out       (B, hop * samples_per_frame): waveform of frames [pos - L, pos - L + hop); zeros where that is outside
 //                                           [0, lens[b])
-//   pos, lens, rng: as stream_step (rng: the draw at the absolute frame of every window row; the noise ring stays untouched)
+//   pos, lens, rng: as stream_run (rng: the draw at the absolute frame of every window row; the noise ring stays untouched)
 //   trim      false: the plain form (one Path over the window)
-template <class Backend>
-int live_step(const Plan& P, const LiveGeom& G, const char* blob, char* state, char* ws, const float* unit_new, const float* g,
-              const float* noise_new, float* out, int B, const int32_t* pos, const int32_t* lens, Backend& be,
-              const NoiseRng* rng = nullptr, bool trim = true) {
+template <class Moves>
+int live_run(Moves& q, const Plan& P, const LiveGeom& G, const char* blob, char* state, char* ws, const float* unit_new, const float* g,
+             const float* noise_new, float* out, int B, typename Moves::Pos* pos, const int32_t* lens, const NoiseRng* rng, bool trim) {
   if (G.usable() != QVC_OK) return G.usable();
   const LiveState S = carve_live_state(P, G, B);
-  const LiveScratch X = carve_live_scratch(P, G, B);
+  const LiveScratch X = carve_live_scratch(P, G, B, Moves::kTick);
   const size_t h = (size_t)G.hop, spf = (size_t)samples_per_frame(P);
   const int nrings = noise_new ? 2 : 1;                            // the generator form leaves the noise ring alone
-  CopyQueue<Backend> q(be, B, G.hop);
+  // the positions and lengths the window's launches read; a tick's are written by the launch that appends (an idle slot:
+  // an empty sequence at W, past every segment's off) and end the sequence behind the slot's new frames
+  const StreamPos at = q.open(pos, lens, G.W, reinterpret_cast<int32_t*>(ws + X.pos_eff), reinterpret_cast<int32_t*>(ws + X.len_eff), true);
   // ---- append the new frames behind the kept ones
   q.append(state, S.rings.r[0], unit_new);
   if (noise_new) q.append(state, S.rings.r[1], noise_new);
@@ -788,9 +795,11 @@ int live_step(const Plan& P, const LiveGeom& G, const char* blob, char* state, c
   const float* unit = reinterpret_cast<const float*>(state + S.unit);
   const float* noise = noise_new ? reinterpret_cast<const float*>(state + S.noise) : nullptr;
   size_t wave_rows = 0, first = 0;                                 // rows of X.wave, and the first delivered one
-  q.ok(live_window(P, G, X, blob, ws, unit, g, noise, B, pos, lens, be, rng, trim, wave_rows, first));
-  // ---- deliver rows [first, first + hop) and slide the rings by one hop: kept parts out, then back in
-  q.fresh(out, h * spf * 4, ws + X.wave + first * spf * 4, wave_rows * spf * 4, spf * 4, 1);
+  q.ok(live_window(P, G, X, blob, ws, unit, g, noise, B, at.pos, at.lens, q.be, rng, trim, wave_rows, first));
+  // ---- deliver the slot's new frames of rows [first, first + hop) (an idle slot of a tick gets a row of zeros), move the
+  //      positions on and slide the rings: kept parts out, then back in
+  q.fresh(out, h * spf * 4, ws + X.wave + first * spf * 4, wave_rows * spf * 4, spf * 4, 1, 0, kCountedIdleZero);
+  q.advance(pos);
   q.slide_out(state, ws, S.rings, X.tmp, nrings);
   q.flush();
   q.slide_back(state, ws, S.rings, X.tmp, nrings);
@@ -798,69 +807,46 @@ int live_step(const Plan& P, const LiveGeom& G, const char* blob, char* state, c
   return q.st;
 }
 
-// ---------------------------------------------------------------- the tick form: per-slot frame counts per step (live_tick)
+// One step: every slot moves by hop frames (arguments: live_run).  pos is only read; the caller advances it.
+template <class Backend>
+int live_step(const Plan& P, const LiveGeom& G, const char* blob, char* state, char* ws, const float* unit_new, const float* g,
+              const float* noise_new, float* out, int B, const int32_t* pos, const int32_t* lens, Backend& be,
+              const NoiseRng* rng = nullptr, bool trim = true) {
+  CopyQueue<Backend> q(be, B, G.hop);
+  return live_run(q, P, G, blob, state, ws, unit_new, g, noise_new, out, B, pos, lens, rng, trim);
+}
+
+// ---------------------------------------------------------------- the tick form of the window (live_tick)
 // live_step moves every slot by exactly `hop` frames.  A tick lets slot b bring n = clamp(n_new[b], 0, hop) frames, the
-// counts in device memory: a late packet (n = 0), a client catching up, a last chunk shorter than hop.  The windowed
-// step makes that well defined -- a window whose last row is the newest frame is a sequence that ends there, however
-// many frames were appended to get there -- provided the ring is kept RIGHT-aligned:
-//
-//     INVARIANT  between ticks, ring row r of slot b holds frame pos[b] - W + r (the last W frames; live_step's ring
-//                keeps W - hop frames LEFT-aligned between steps).
-//     EXCLUSIVE  the two layouts differ, so a tick state is never passed to live_step, nor a lockstep state to live_tick.
-//
-// A tick is  tick_rings -> the window (live_window, unchanged) -> tick_deliver:
-//   tick_rings    shifts every ring row of a slot left by n and appends its n new frames, in place, and writes the
-//                 position the window's launches see, pos_eff[b] = pos[b] + n - hop: buffer row W - hop is then that
-//                 absolute frame, exactly as live_step's segments assume, so they run unchanged.
-//                 pos_eff is negative early in a stream (first tick with n = 1: 1 - hop); ragged_lo / ragged_len and
-//                 the generator's frame counter only ever use pos - off, which is negative for a young stream in
-//                 live_step too.  A slot with n == 0 gets an empty sequence (len_eff = 0, pos_eff = W: hi = 0 in every
-//                 segment), so its tiles return at once and its ring rows and pos are not touched.
-//   tick_deliver  the delivered rows [first, first + hop) hold the n frames [pos - L, pos - L + n) at their END:
-//                 those go to the front of out[b], zeros behind them, and pos[b] += n.
-// With every n == hop: pos_eff = pos, len_eff = lens and the window's launches and bits are live_step's.
+// counts in device memory: a late packet (n = 0), a client catching up, a last chunk shorter than hop -- on the SAME state
+// (live_rings: INVARIANT, SHARED), through the same body on CountedQueue, as stream_tick does for the segment rings.
+// A tick writes a slot's n new frames behind the kept W - hop and zero-fills rows [W - hop + n, W).  The window's launches
+// see pos_eff = pos -- buffer row W - hop is that absolute frame, as in a step -- and len_eff = min(lens, pos + n): a
+// sequence that ends behind the newest frame, which is what the window is (the zero-filled rows are past its end, not
+// frames of it).  So the delivered frames [pos - L, pos - L + n), the FIRST n of the hop central rows, are those of the
+// offline conversion of the prefix [0, min(lens, pos + n)); the rows behind them are never handed on.  The slides move a
+// slot's kept part by n rows and pos[b] += n.  A slot with n == 0 gets an empty sequence (len_eff = 0, pos_eff = W: hi = 0
+// in every segment), so its tiles return at once, and no copy touches its rings, its scratch rows or its pos; only its
+// row of `out` is written (zeros).
+// With every n == hop: pos_eff = pos, len_eff = min(lens, pos + hop) -- the buffer end, where a step's sequence ends
+// anyway -- every copy moves what live_step's moves, and out and the kept ring bytes are live_step's bit for bit.
 // Delivered frame f was computed with the frames up to pos + n - 1 in the window: L + n - 1 - (f - (pos - L)) frames of
 // look-ahead, between L and L + n - 1.  With L = C every frame has its whole receptive field whatever n was, so the
 // output does not depend on how the stream was cut into ticks; with L < C it legitimately does.
-// Backend adds:  static constexpr bool kLiveTick = true  with  int tick_rings(const TickRingsArgs&);
-//                int tick_deliver(const TickDeliverArgs&);   -- one that does not say so gets QVC_ERR_BAD_CONFIG.
-template <class B, class = void> constexpr bool live_tick_backend = false;
-template <class B> constexpr bool live_tick_backend<B, std::void_t<decltype(B::kLiveTick)>> = B::kLiveTick;
-
-// One tick (G from live_plan; state and scratch are carved as live_step's, the scratch with tick = true; the state holds
-// the right-aligned rings).
-//   unit_new  (B, unit_channels, hop) fp32: columns [0, n) of row b are frames [pos[b], pos[b] + n); the rest is not read
-//   noise_new (B, inter, hop) fp32:         the same rule, the draw for the same frames
-//   out       (B, hop * samples_per_frame): n * spf samples of frames [pos - L, pos - L + n) of the offline conversion
-//                                           of the prefix [0, min(lens, pos + n)), zeros outside [0, lens[b]); then zeros
+// Backend: as stream_tick (kStreamTick with copy_counted) -- one that does not say so gets QVC_ERR_BAD_CONFIG.
+//
+// One tick.  State as live_step's; scratch carved with tick = true.  Arguments as live_step's, except:
+//   unit_new  columns [0, n) of row b are frames [pos[b], pos[b] + n); columns [n, hop) are never read
+//   noise_new the same rule, the draw for the same frames
+//   out       the first n * spf samples of row b: frames [pos - L, pos - L + n) of the prefix conversion; then zeros
 //   n_new     (B,) int32 in the backend's memory, clamped to [0, hop] there; pos is advanced by n there too
 template <class Backend>
 int live_tick(const Plan& P, const LiveGeom& G, const char* blob, char* state, char* ws, const float* unit_new, const float* g,
               const float* noise_new, float* out, int B, const int32_t* n_new, int32_t* pos, const int32_t* lens, Backend& be,
               const NoiseRng* rng = nullptr, bool trim = true) {
-  if constexpr (live_tick_backend<Backend>) {
-    if (G.usable() != QVC_OK) return G.usable();
-    const LiveState S = carve_live_state(P, G, B);
-    const LiveScratch X = carve_live_scratch(P, G, B, true);
-    int st = QVC_OK;
-    auto ok = [&](int rc) { if (st == QVC_OK && rc != QVC_OK) st = rc; };
-    float* uring = reinterpret_cast<float*>(state + S.unit);
-    float* nring = noise_new ? reinterpret_cast<float*>(state + S.noise) : nullptr;
-    int32_t* pos_eff = reinterpret_cast<int32_t*>(ws + X.pos_eff);
-    int32_t* len_eff = reinterpret_cast<int32_t*>(ws + X.len_eff);
-    TickRingsArgs ra;
-    ra.unit_ring = uring; ra.unit_new = unit_new; ra.noise_ring = nring; ra.noise_new = noise_new;
-    ra.B = B; ra.UC = P.cfg.unit_channels; ra.NC = P.cfg.inter_channels; ra.W = G.W; ra.hop = G.hop;
-    ra.n_new = n_new; ra.pos = pos; ra.lens = lens; ra.pos_eff = pos_eff; ra.len_eff = len_eff;
-    ok(be.tick_rings(ra));
-    size_t wave_rows = 0, first = 0;
-    ok(live_window(P, G, X, blob, ws, uring, g, nring, B, pos_eff, len_eff, be, rng, trim, wave_rows, first));
-    TickDeliverArgs da;
-    da.wave = reinterpret_cast<const float*>(ws + X.wave); da.out = out;
-    da.B = B; da.rows = (int32_t)wave_rows; da.first = (int32_t)first; da.hop = G.hop; da.spf = samples_per_frame(P);
-    da.n_new = n_new; da.pos = pos;
-    ok(be.tick_deliver(da));
-    return st;
+  if constexpr (stream_tick_backend<Backend>) {
+    CountedQueue<Backend> q(be, n_new, B, G.hop);
+    return live_run(q, P, G, blob, state, ws, unit_new, g, noise_new, out, B, pos, lens, rng, trim);
   } else {
     return QVC_ERR_BAD_CONFIG;
   }

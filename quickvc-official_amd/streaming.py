@@ -566,7 +566,8 @@ class LiveConverter(StreamConverter):
     [pos - look_ahead, pos - look_ahead + hop) of the OFFLINE conversion of the stream's prefix [0, min(length, pos + hop))
     -- the result is defined exactly, whatever the look-ahead.  ``look_ahead == context`` is exact streaming: the
     concatenated outputs equal the whole-utterance conversion, also for the single-band decoder and decoders with one
-    up-sampler, which StreamConverter refuses.  A frame costs ``window / hop`` of its offline cost.
+    up-sampler, which StreamConverter refuses.  A frame costs ``window / hop`` of its offline cost.  Between steps the
+    ring keeps its last ``window - hop`` frames left-aligned -- the layout TickConverter keeps too, so the state is shared.
     The noise tensor of ``step(unit_new, noise_new)`` is for the frames of ``unit_new`` (``noise_lag == 0``)."""
 
     def __init__(self, model, streams: int, hop_frames: int, look_ahead: int, use_graph: bool = True, seed: Optional[int] = None,
@@ -603,7 +604,8 @@ class TickConverter(_Ticks, LiveConverter):
     ``position`` / ``reset`` / ``end`` / ``set_seed``) and one graph replay per tick; the counts travel in a device
     tensor the captured call reads, the positions advance on the device by the clamped counts and the host mirror
     follows them.  A slot that brings nothing leaves no trace: its ring, its position and the other slots' outputs are
-    what they would have been without it.
+    what they would have been without it.  The state is LiveConverter's, ring layout included (qvc_live_step and
+    qvc_live_tick may alternate on one state); only the workspace is larger.
 
     ``tick`` returns frames [pos - look_ahead, pos - look_ahead + n) of the offline conversion of the prefix
     [0, min(length, pos + n)).  With ``look_ahead == context`` the concatenated output is the whole-utterance conversion

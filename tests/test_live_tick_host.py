@@ -1,7 +1,7 @@
 """CPU tests (no GPU) of the tick form of the windowed step (include/qvc.h: qvc_live_tick*; csrc/qvc_stream.h:
 live_tick): per call, slot b brings n = clamp(n_new[b], 0, hop) frames.  The C ABI's surface, sizes and error codes on
 the product library, and -- through the CPU twin of the driver (tools/emu_twin.cpp: live_tick on a backend derived from
-the frozen emulation's, with host versions of the ring update and the delivery) -- the properties that define it:
+the frozen emulation's, with the host version of the count-aware batched copy) -- the properties that define it:
 
   T1  the first n * spf samples of a tick's row are frames [pos - L, pos - L + n) of the OFFLINE conversion of the
       stream's first min(len, pos + n) frames, zeros outside [0, len); the rest of the row is 0.0; pos += n; a slot with

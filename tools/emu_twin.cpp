@@ -1,13 +1,12 @@
 // emu_twin.cpp -- TEST INFRASTRUCTURE: the CPU twin of qvc_live_step, qvc_live_tick and qvc_stream_tick.
 //
 // The host emulation under oracle/ is frozen, and its backend sits in an unnamed namespace of oracle/qvc_emu.cpp, so this
-// translation unit includes that file.  The frozen EmuBackend does not state kLiveTick; TickEmuBackend derives from it,
-// states the constant and adds host versions of the two launches a tick brackets the window with (csrc/qvc_small.hip:
-// tick_rings_kernel, tick_deliver_kernel).  CountingBackend derives from that and counts the launches that move data
-// (copy_batch, tick_rings, tick_deliver): live_step, live_tick and stream_step (csrc/qvc_stream.h) are instantiated on
+// translation unit includes that file.  The frozen EmuBackend does not state kStreamTick; TickEmuBackend derives from it,
+// states the constant and adds the host version of the count-aware batched copy both ticks move their data with
+// (csrc/qvc_small.hip: copy_counted_kernel).  CountingBackend derives from that and counts the launches that move data
+// (copy_batch, copy_counted): live_step, live_tick, stream_step and stream_tick (csrc/qvc_stream.h) are instantiated on
 // it, so a host test can pin how a step groups its copies into launches.  Built by build.py into
-// oracle/_build/libqvc_emu_twin.so and loaded only by the tests.  The same backend states kStreamTick and adds the host
-// version of the count-aware batched copy (csrc/qvc_small.hip: copy_counted_kernel), on which stream_tick is instantiated.
+// oracle/_build/libqvc_emu_twin.so and loaded only by the tests.
 // RecordingBackend derives from CountingBackend and writes down every copy_batch / copy_counted call of one stream_step
 // or stream_tick, descriptor by descriptor (qvc_emu_stream_moves; tests/test_stream_moves_host.py).  The slot snapshots
 // (snapshot_slots: qvc_emu_stream_export_slots / _import_slots) run on the same host copy_batch.  The emulation's
@@ -23,44 +22,6 @@
 namespace {
 
 struct TickEmuBackend : EmuBackend {
-  static constexpr bool kLiveTick = true;
-  // a row is read whole before it is written, as the kernel's passes are
-  static void shift_row(float* ring, const float* fresh, int W, int n) {
-    std::vector<float> v((size_t)W);
-    for (int r = 0; r < W; ++r) v[(size_t)r] = r < W - n ? ring[r + n] : fresh[r - (W - n)];
-    std::memcpy(ring, v.data(), (size_t)W * 4);
-  }
-  int tick_rings(const qvc::TickRingsArgs& a) {
-    if (!a.unit_ring || !a.unit_new || !a.n_new || !a.pos || !a.lens || !a.pos_eff || !a.len_eff) return QVC_ERR_BAD_ARG;
-    if ((a.noise_ring == nullptr) != (a.noise_new == nullptr) || a.W <= a.hop || a.hop < 1) return QVC_ERR_BAD_ARG;
-    for (int b = 0; b < a.B; ++b) {
-      const int n = qvc::tick_count(a.n_new, b, a.hop);
-      a.pos_eff[b] = n > 0 ? a.pos[b] + n - a.hop : a.W;
-      a.len_eff[b] = n > 0 ? a.lens[b] : 0;
-      if (n == 0) continue;
-      for (int c = 0; c < a.UC; ++c) {
-        const size_t row = (size_t)b * a.UC + c;
-        shift_row(a.unit_ring + row * a.W, a.unit_new + row * a.hop, a.W, n);
-      }
-      for (int c = 0; a.noise_ring && c < a.NC; ++c) {
-        const size_t row = (size_t)b * a.NC + c;
-        shift_row(a.noise_ring + row * a.W, a.noise_new + row * a.hop, a.W, n);
-      }
-    }
-    return QVC_OK;
-  }
-  int tick_deliver(const qvc::TickDeliverArgs& a) {
-    if (!a.wave || !a.out || !a.n_new || !a.pos || a.first < 0 || a.first + a.hop > a.rows) return QVC_ERR_BAD_ARG;
-    const size_t total = (size_t)a.hop * a.spf;
-    for (int b = 0; b < a.B; ++b) {
-      const int n = qvc::tick_count(a.n_new, b, a.hop);
-      const float* src = a.wave + ((size_t)b * a.rows + (size_t)(a.first + a.hop - n)) * a.spf;
-      float* dst = a.out + (size_t)b * total;
-      for (size_t e = 0; e < total; ++e) dst[e] = e < (size_t)n * a.spf ? src[e] : 0.f;
-      a.pos[b] += n;
-    }
-    return QVC_OK;
-  }
   // csrc/qvc_small.hip copy_counted_kernel: the bookkeeping, then every descriptor slot by slot
   static constexpr bool kStreamTick = true;
   int copy_counted(const qvc::CountedHead& h, const qvc::CountedDesc* d, int n) {
@@ -75,7 +36,7 @@ struct TickEmuBackend : EmuBackend {
     }
     for (int b = 0; b < h.slots; ++b) {
       const int nb = qvc::tick_count(h.n_new, b, h.hop);
-      if (h.pos_eff) { h.pos_eff[b] = nb > 0 ? h.pos[b] : h.idle_pos; h.len_eff[b] = nb > 0 ? h.lens[b] : 0; }
+      if (h.pos_eff) { h.pos_eff[b] = nb > 0 ? h.pos[b] : h.idle_pos; h.len_eff[b] = nb > 0 ? qvc::counted_len(h, b, nb) : 0; }
       if (h.pos_add && nb > 0) h.pos_add[b] += nb;
     }
     for (int i = 0; i < n; ++i) {
@@ -95,14 +56,13 @@ struct TickEmuBackend : EmuBackend {
   }
 };
 
-// calls of copy_batch, descriptors in them, calls of tick_rings, calls of tick_deliver -- since qvc_emu_twin_counts
+// calls of copy_batch, descriptors in them, and two words that stay 0 (the launches of a mechanism that is gone: the
+// recorded rows keep their four-word shape) -- since qvc_emu_twin_counts
 int64_t g_counts[4] = {0, 0, 0, 0};
 int64_t g_counted[2] = {0, 0};      // calls of copy_counted, descriptors in them -- since qvc_emu_stream_tick_counts
 
 struct CountingBackend : TickEmuBackend {
   int copy_batch(const qvc::CopyDesc* d, int n) { ++g_counts[0]; g_counts[1] += n; return TickEmuBackend::copy_batch(d, n); }
-  int tick_rings(const qvc::TickRingsArgs& a) { ++g_counts[2]; return TickEmuBackend::tick_rings(a); }
-  int tick_deliver(const qvc::TickDeliverArgs& a) { ++g_counts[3]; return TickEmuBackend::tick_deliver(a); }
   int copy_counted(const qvc::CountedHead& h, const qvc::CountedDesc* d, int n) { ++g_counted[0]; g_counted[1] += n; return TickEmuBackend::copy_counted(h, d, n); }
 };
 
@@ -547,7 +507,7 @@ int qvc_emu_live_tick_reset_slot(const qvc_config* cfg, void* state, int64_t sta
 }
 
 // Byte offset and size of slot `slot`'s unit ring (which = 0) / noise ring (1) in the state: the tests compare an idle
-// slot's ring bytes before and after a tick.
+// slot's ring bytes before and after a tick, and the kept W - hop frames of a slot's rows after a step and after a tick.
 int qvc_emu_live_tick_ring(const qvc_config* cfg, int32_t batch, int32_t hop, int32_t look_ahead, int32_t slot, int32_t which,
                            int64_t* offset, int64_t* bytes) {
   if (!offset || !bytes || batch <= 0 || slot < 0 || slot >= batch || which < 0 || which > 1) return QVC_ERR_BAD_ARG;
@@ -611,6 +571,15 @@ int qvc_emu_stream_tick_frozen(const qvc_config* cfg, int32_t batch, int32_t hop
   return qvc::stream_tick(P, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, batch, hop, nullptr, nullptr, nullptr, be);
 }
 
+// ... and its sibling for the window.
+int qvc_emu_live_tick_frozen(const qvc_config* cfg, int32_t batch, int32_t hop, int32_t look_ahead) {
+  qvc::Plan P; qvc::LiveGeom G;
+  const int gs = qvc::live_plan(cfg, hop, look_ahead, P, G);
+  if (gs != QVC_OK) return gs;
+  EmuBackend be;
+  return qvc::live_tick(P, G, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, batch, nullptr, nullptr, nullptr, be);
+}
+
 // Same signature as qvc_stream_reset_slot, host pointers, no stream.
 int qvc_emu_stream_reset_slot(const qvc_config* cfg, void* state, int64_t state_bytes, int32_t batch, int32_t hop, int32_t slot,
                               int32_t length, int32_t* pos, int32_t* lens) {
@@ -658,8 +627,7 @@ void qvc_emu_stream_tick_counts(int64_t* counts) {
   for (int i = 0; i < 2; ++i) { if (counts) counts[i] = g_counted[i]; g_counted[i] = 0; }
 }
 
-// counts[4] = calls of copy_batch, descriptors in them, calls of tick_rings, calls of tick_deliver since the last call
-// of this function; the counts are cleared.
+// counts[4] = calls of copy_batch, descriptors in them, 0, 0 since the last call of this function; the counts are cleared.
 void qvc_emu_twin_counts(int64_t* counts) {
   for (int i = 0; i < 4; ++i) { if (counts) counts[i] = g_counts[i]; g_counts[i] = 0; }
 }

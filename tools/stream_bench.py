@@ -141,7 +141,7 @@ def tick_rows(model, streams, hop, looks, rounds=5, n=20):
     pats, dev_pats = tick_patterns(streams, hop, n)
     out = {"context_frames": context,
            "launches_beside_the_path": {"lockstep_step": "3 copy_batch (append; deliver + rings out; rings back)",
-                                        "tick": "2 (tick_rings, tick_deliver)"},
+                                        "tick": "3 copy_counted (the same three, per-slot counts)"},
            "mean_frames_per_slot_and_tick": {k: sum(map(sum, v[12:])) / (n * streams) for k, v in pats.items()}}
     for look in looks:
         L = context if look == "C" else int(look)
