@@ -31,7 +31,7 @@ SOURCES = ["qvc_conv_f16.hip", "qvc_conv_bf16.hip", "qvc_wn2.hip", "qvc_chain.hi
 # translation units whose gfx950 assembly is kept next to the resource remarks (tests/test_pair_kloop_waits.py reads the
 # wait counts of the pair kernels' K loops from it)
 ASM_SOURCES = ["qvc_conv_f16.hip", "qvc_conv_bf16.hip"]
-HEADERS = ["qvc_plan.h", "qvc_kernels.h", "qvc_conv_impl.h", "qvc_wn2_impl.h", "qvc_chain_impl.h", "qvc_post_tail_impl.h", "qvc_tail_impl.h", "qvc_path.h", "qvc_stream.h", "qvc_pack_util.h", "qvc_launch_util.h"]
+HEADERS = ["qvc_plan.h", "qvc_kernels.h", "qvc_select.h", "qvc_conv_impl.h", "qvc_wn2_impl.h", "qvc_chain_impl.h", "qvc_post_tail_impl.h", "qvc_tail_impl.h", "qvc_path.h", "qvc_stream.h", "qvc_pack_util.h", "qvc_launch_util.h"]
 
 
 def _newer(target: str, deps) -> bool:

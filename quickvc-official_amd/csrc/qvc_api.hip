@@ -80,7 +80,8 @@ struct HipBackend {
 using Ctx = Path<HipBackend>;
 
 // Same launches, each bracketed by events on the stream (diagnostics only).  Every method: the launch, then the
-// record's name and its algorithmic flops / bytes.
+// record's name -- from the launch's LaunchChoice (qvc_select.h) where a chooser picked the kernel -- and its algorithmic
+// flops / bytes.
 struct TimedBackend {
   static constexpr bool kSingleBandTail = true;
   void fork(int) {} void branch(int) {} void branch_done(int) {} void join(int) {}
@@ -99,8 +100,8 @@ struct TimedBackend {
   }
   static const char* tn(int dtype) { return dtype == QVC_F16 ? "f16" : (dtype == QVC_BF16X ? "bf16x" : "bf16"); }
   int conv(const ConvDesc& d, const ConvArgs& a, int batch, int epi, int dtype) {
-    int nf = 0;
-    const int st = timed([&] { return launch_conv(d, a, batch, epi, dtype, stream, &nf); });
+    LaunchChoice c;
+    const int st = timed([&] { return launch_conv(d, a, batch, epi, dtype, stream, c); });
     // algorithmic work: a transposed conv does k MACs per (input frame, ci, co), a conv taps MACs per output
     const double macs = d.up_s > 1 ? (double)batch * a.T_in * d.Cin * d.Cout * (double)d.ksize
                                    : (double)batch * a.Nq * (double)d.M * d.taps * d.Cin;
@@ -116,13 +117,13 @@ struct TimedBackend {
       if (a.res16) out_b += outs * 2;
       if (a.y32b) out_b += (double)batch * a.Nq * (d.M - a.split) * 8;
     }
-    note(2.0 * macs, in_b + out_b + (double)d.w_bytes(), "conv<%s,MF%d,NF%d,WM%d,%s>", tn(dtype), d.MF, nf, d.WM,
+    note(2.0 * macs, in_b + out_b + (double)d.w_bytes(), "conv<%s,MF%d,NF%d,WM%d,%s>", tn(dtype), d.MF, c.NF, d.WM,
          epi == EPI_GAU ? "gau" : (epi == EPI_SAMPLE ? "smp" : "std"));
     return st;
   }
   int pair3(const ConvDesc* d1, const ConvDesc* d2, const PairArgs3& a, int batch, int dtype) {
-    int nf = 0;
-    const int st = timed([&] { return launch_pair3(d1, d2, a, batch, dtype, stream, &nf); });
+    LaunchChoice c;
+    const int st = timed([&] { return launch_pair3(d1, d2, a, batch, dtype, stream, c); });
     // one kernel symbol serves 1..3 chains per launch; the record's flops / bytes are those of the whole launch
     double fl = 0, by = 0;
     for (int i = 0; i < a.n; ++i) {
@@ -130,36 +131,37 @@ struct TimedBackend {
       fl += 2.0 * 2.0 * outs * a.p[i].C * a.p[i].k;
       by += outs * 2 * 2 + (double)d1[i].w_bytes() + (double)d2[i].w_bytes();   // algorithmic: the stream read once, written once (the kernel's second read of x for the residual is NOT counted: it shows up as traffic / algorithmic > 1)
     }
-    note(fl, by, "rbpair<%s,MF%d,NF%d,WM%d>", tn(dtype), d1[0].MF, nf, d1[0].WM);
+    note(fl, by, "rbpair<%s,MF%d,NF%d,WM%d>", tn(dtype), d1[0].MF, c.NF, d1[0].WM);
     return st;
   }
   bool chain_ok(const ConvDesc* d1, const ConvDesc* d2, int n) const { return debug_get(DBG_PAIR_CHAIN3) != 0 && chain_supported(d1, d2, n); }
   int chain(const ConvDesc* d1, const ConvDesc* d2, const ChainArgs& a, int batch, int dtype) {
-    int nf = 0;
-    const int st = timed([&] { return launch_chain(d1, d2, a, batch, dtype, stream, &nf); });
+    LaunchChoice c;
+    const int st = timed([&] { return launch_chain(d1, d2, a, batch, dtype, stream, c); });
     const double outs = (double)batch * a.p[0].T * a.p[0].C;
     note(a.n * 2.0 * 2.0 * outs * a.p[0].C * a.p[0].k, outs * 2 * 2 + a.n * ((double)d1[0].w_bytes() + (double)d2[0].w_bytes()),
-         "rbchain<%s,MF%d,NF%d,WM%d,k%d>", tn(dtype), d1[0].MF, nf, d1[0].WM, d1[0].taps);
+         "rbchain<%s,MF%d,NF%d,WM%d,k%d>", tn(dtype), d1[0].MF, c.NF, d1[0].WM, d1[0].taps);
     return st;
   }
   int wn(const ConvDesc& din, const ConvDesc& drs, const WnArgs& a, int batch, int dtype) {
-    int nf = 0;
-    const int st = timed([&] { return launch_wn(din, a, batch, dtype, stream, &nf); });
+    LaunchChoice c;
+    const int st = timed([&] { return launch_wn(din, a, batch, dtype, stream, c); });
     const double cols = (double)batch * a.T;
     note(2.0 * cols * a.H * (2.0 * a.H * a.taps + (double)drs.M), cols * a.H * 4 * (a.last ? 3 : 5) + (double)din.w_bytes() + (double)drs.w_bytes(),
-         "wn_layer<%s,W%d,NF%d%s>", tn(dtype), din.WM, nf, a.last ? ",last" : "");
+         "wn_layer<%s,W%d,NF%d%s>", tn(dtype), din.WM, c.NF, a.last ? ",last" : "");
     return st;
   }
   int wn_stack_chunk(int layers) const { return wn_chunk(layers); }
   int wn_stack(const ConvDesc& din, const ConvDesc& drs, const ConvDesc& drs_last, const WnStackArgs& a, int batch, int dtype,
                const ConvDesc* dpre, const ConvDesc* dpost) {
-    const int st = timed([&] { return launch_wn_stack(din, a, batch, dtype, stream); });
-    const int v = wn_stack_variant(din, a, batch);
+    LaunchChoice c;
+    const int st = timed([&] { return launch_wn_stack(din, a, batch, dtype, stream, c); });
     const double cols = (double)batch * a.T;
     const double fl = 2.0 * cols * a.H * (a.layers * 2.0 * a.H * a.taps + (a.layers - (a.final_layer ? 1 : 0)) * (double)drs.M + (a.final_layer ? (double)drs_last.M : 0.0));
     const double fuse_fl = (dpre ? 2.0 * cols * dpre->M * dpre->Cin : 0.0) + (dpost ? 2.0 * cols * dpost->M * dpost->Cin : 0.0);
     note(fl + fuse_fl, cols * a.H * 8 + a.layers * ((double)din.w_bytes() + (double)drs.w_bytes()), "%s<%s,W%d,L%d%s%s>",
-         v >= 2 ? "wn_stack2" : "wn_stack", tn(dtype), din.WM, a.layers, dpre ? ",pre+post" : "", v == 3 ? ",64f" : "");
+         c.family == LF_WN_STACK2 ? "wn_stack2" : "wn_stack", tn(dtype), din.WM, a.layers, dpre ? ",pre+post" : "",
+         c.family == LF_WN_STACK2 && c.NF == 5 ? ",64f" : "");
     return st;
   }
   int gemv(const GemvArgs& a) {

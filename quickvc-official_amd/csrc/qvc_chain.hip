@@ -2,9 +2,9 @@
 // of its own so that it compiles beside the conv kernels.
 #include "qvc_chain_impl.h"
 namespace qvc {
-template int launch_chain_typed<_Float16, _Float16>(const ConvDesc*, const ConvDesc*, ChainArgs, int, void*, int*);
-template int launch_chain_typed<__bf16, __bf16>(const ConvDesc*, const ConvDesc*, ChainArgs, int, void*, int*);
-template int launch_chain_typed<__bf16, _Float16>(const ConvDesc*, const ConvDesc*, ChainArgs, int, void*, int*);
+template int dispatch_chain<_Float16, _Float16>(const LaunchChoice&, const ChainArgs&, void*);
+template int dispatch_chain<__bf16, __bf16>(const LaunchChoice&, const ChainArgs&, void*);
+template int dispatch_chain<__bf16, _Float16>(const LaunchChoice&, const ChainArgs&, void*);
 }  // namespace qvc
 #ifdef QVC_SATCOUNT
 namespace qvc { QVC_SAT_READER(sat_count_chain) }

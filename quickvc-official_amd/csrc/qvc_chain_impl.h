@@ -133,40 +133,18 @@ __global__ __launch_bounds__(NWV * 64) void rbchain_kernel(const ChainArgs A) {
   }
 }
 
-template <typename T, int MF, int NF, int NWV, typename TS>
-inline int launch_chain_one(const ChainArgs& a, int batch, size_t lds, hipStream_t stream) {
-  const dim3 grid((unsigned)ceil_div(a.p[0].T, a.NT), (unsigned)batch);
-  return launch_big_lds<rbchain_kernel<T, MF, NF, NWV, TS>>(grid, dim3(NWV * 64), lds, stream, a);
-}
-
-template <typename T, int MF, int NWV, typename TS>
-inline int launch_chain_nf(int NF, const ChainArgs& a, int batch, size_t lds, hipStream_t stream) {
-  switch (NF) {
-    case 9: if constexpr (MF * 9 * 4 <= 96) return launch_chain_one<T, MF, 9, NWV, TS>(a, batch, lds, stream); break;
-    case 8: if constexpr (MF * 8 * 4 <= 96) return launch_chain_one<T, MF, 8, NWV, TS>(a, batch, lds, stream); break;
-    case 6: if constexpr (MF * 6 * 4 <= (MF > 2 ? 80 : 96)) return launch_chain_one<T, MF, 6, NWV, TS>(a, batch, lds, stream); break;
-    case 5: return launch_chain_one<T, MF, 5, NWV, TS>(a, batch, lds, stream);
-    case 4: return launch_chain_one<T, MF, 4, NWV, TS>(a, batch, lds, stream);
-    default: break;
-  }
-  return QVC_ERR_BAD_CONFIG;
-}
-
+// a.halo / margin / NT: the choice's (launch_chain copies them in)
 template <typename T, typename TS>
-int launch_chain_typed(const ConvDesc* d1, const ConvDesc* d2, ChainArgs a, int batch, void* stream_v, int* nf_out) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_v);
-  if (!chain_supported(d1, d2, a.n)) return QVC_ERR_BAD_CONFIG;
-  ChainGeom g;
-  const int NF = chain_pick_nf(d1, a.n, &g);
-  a.halo = g.halo; a.margin = g.margin; a.NT = g.NT;
-  if (nf_out) *nf_out = NF;
-  switch (d1[0].WM * 10 + d1[0].MF) {
-    case 42: return launch_chain_nf<T, 2, 4, TS>(NF, a, batch, g.lds, stream);
-    case 44: return launch_chain_nf<T, 4, 4, TS>(NF, a, batch, g.lds, stream);
-    case 82: return launch_chain_nf<T, 2, 8, TS>(NF, a, batch, g.lds, stream);
-    case 84: return launch_chain_nf<T, 4, 8, TS>(NF, a, batch, g.lds, stream);
-    default: return QVC_ERR_BAD_CONFIG;
-  }
+int dispatch_chain(const LaunchChoice& c, const ChainArgs& a, void* stream) {
+  return lift<2, 4>(c.MF, [&](auto MF) {
+    return lift<4, 8>(c.waves, [&](auto NWV) {
+      return lift<9, 8, 6, 5, 4>(c.NF, [&](auto NF) -> int {
+        if constexpr (chain_built(QVC_V(MF), QVC_V(NF), QVC_V(NWV)))
+          return launch_chosen<rbchain_kernel<T, QVC_V(MF), QVC_V(NF), QVC_V(NWV), TS>>(c, a, stream);
+        else return QVC_ERR_BAD_CONFIG;
+      });
+    });
+  });
 }
 
 }  // namespace qvc

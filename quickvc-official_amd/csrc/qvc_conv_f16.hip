@@ -2,11 +2,11 @@
 // types compile in parallel).
 #include "qvc_conv_impl.h"
 #include "qvc_post_tail_impl.h"
-namespace qvc { template int launch_conv_typed<_Float16>(const ConvDesc&, const ConvArgs&, int, int, void*, int*);
-template int launch_post_tail_typed<_Float16>(const ConvDesc&, const PostTailArgs&, int, void*);
-template int launch_wn_stack_typed<_Float16>(const ConvDesc&, const WnStackArgs&, int, void*);
-template int launch_wn_typed<_Float16>(const ConvDesc&, const WnArgs&, int, void*, int*);
-template int launch_pair_typed<_Float16, _Float16>(const ConvDesc*, const PairArgs3&, int, void*, int*); }
+namespace qvc { template int dispatch_conv<_Float16>(const LaunchChoice&, const ConvArgs&, void*);
+template int dispatch_post_tail<_Float16>(const LaunchChoice&, const PostTailArgs&, void*);
+template int dispatch_wn_stack<_Float16>(const LaunchChoice&, const WnStackArgs&, void*);
+template int dispatch_wn<_Float16>(const LaunchChoice&, const WnArgs&, void*);
+template int dispatch_pair<_Float16, _Float16>(const LaunchChoice&, const PairArgs3&, void*); }
 #ifdef QVC_SATCOUNT
 namespace qvc { QVC_SAT_READER(sat_count_conv_f16) }
 #endif

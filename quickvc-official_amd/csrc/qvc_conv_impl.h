@@ -21,7 +21,7 @@
 #include <algorithm>
 #include <type_traits>
 #include <cstdlib>
-#include "qvc_kernels.h"
+#include "qvc_select.h"
 #include "qvc_launch_util.h"
 
 #ifndef QVC_SWZ_ROT
@@ -422,10 +422,7 @@ __device__ __forceinline__ void stage_stream_tile(const TS* xb, int C, int cpr, 
   }
 }
 
-// Kernel-side variant of EPI_SAMPLE, chosen by launch_conv_typed when the launch carries a generator instead of a noise
-// tensor (ConvArgs::rng); callers and backends only ever name EPI_SAMPLE.
-constexpr int EPI_SAMPLE_RNG = 16;
-
+// (EPI_SAMPLE_RNG, the kernel-side variant of EPI_SAMPLE with the draw computed in the epilogue: qvc_select.h)
 // WM waves along M, WN = 4/WM along the frames; block tile = [WM*MF*16 rows] x [WN*NF*16 frames].
 // CL ("chunk loop"): the workgroup stages its tile once and walks all the row chunks itself (grid z = 1) instead of
 // one workgroup per chunk each staging the same tile -- for convs whose staging is the expensive part (up-sampler 1:
@@ -1436,275 +1433,70 @@ __global__ __launch_bounds__(WV * 64) void wn_stack_kernel(const WnStackArgs a) 
 #endif
 }
 
-// ------------------------------------------------------------------ launch-side tile selection
-struct TileChoice { int NF; int blocks; size_t lds; };
-
-inline TileChoice choose_tile(const ConvDesc& d, int Nq, int batch, const int* nf_list, int n_nf) {
-  const int halo = (d.taps - 1) * d.dil;
-  const int rowbytes = d.CinP * 2;
-  const int WN = kWaves / d.WM;
-  TileChoice best{0, 0, 0};
-  double best_cost = 1e300;
-  for (int i = 0; i < n_nf; ++i) {
-    const int NF = nf_list[i];
-#ifdef QVC_FORCE_NF
-    if (NF != QVC_FORCE_NF) continue;                           // developer sweep (tools/conv_bench)
-#endif
-    if (d.MF * NF * 4 > 160) continue;                          // accumulator registers
-    // polyphase up-samplers have s * Cout rows = many row chunks, and every workgroup streams its chunk's whole K:
-    // with 32-frame tiles up-sampler 0 pulls 4.9 MB of weights into every CU (45 us at the ~50 B/clk a CU takes in) --
-    // 64-frame tiles halve that while the launch still has two workgroups per CU (57.9 -> 50.3 us, bit-identical)
-    if (d.up_s > 1 && NF < 4 && (long)ceil_div(Nq, WN * 4 * 16) * batch * d.nchunk >= 512) continue;
-    const int NT = WN * NF * 16;
-    const size_t lds = (size_t)(NT + halo) * rowbytes;
-    if (lds > 160 * 1024) continue;
-    const int tiles = ceil_div(Nq, NT);
-    const long blocks = (long)tiles * batch * d.nchunk;
-    // workgroups that can share a CU (LDS, and the ~512 registers/lane of a SIMD): with >= 2 the
-    // staging / epilogue of one overlaps the MFMA phase of another
-    const int regs = d.MF * NF * 4 + 16 * d.MF + 8 * NF + 40;
-    const int bpc = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(3, (160 * 1024) / lds), (size_t)(512 / regs)));
-    const long rounds = (blocks + 256L * bpc - 1) / (256L * bpc);
-    // work per block ~ frames computed + a fixed overhead (staging, launch, epilogue), in frame units
-    const double work = NT + 0.35 * halo + 24.0;
-    const double cost = (double)rounds * bpc * work * (bpc == 1 ? 1.3 : 1.0);
-    if (cost < best_cost) { best_cost = cost; best = TileChoice{NF, (int)blocks, lds}; }
-#ifndef QVC_FORCE_NF
-    // latency-sized launch: even the smallest tile gives every workgroup a CU of its own -- take it (each workgroup
-    // streams the same weights whatever its tile, so fewer frames per workgroup is less serial MFMA work behind them;
-    // batch 1, up-sampler 0: 35 -> 22 us)
-    if (i == 0 && blocks <= 256) return best;
-#endif
-  }
-  return best;
-}
-
-template <typename T, int MF, int NF, int WM, int EPI, bool CL = false>
-inline int launch_one_cl(const ConvArgs& a, int batch, size_t lds, hipStream_t stream) {
-  constexpr int NT = (kWaves / WM) * NF * 16;
-  const dim3 grid((unsigned)ceil_div(a.Nq, NT), (unsigned)batch, (unsigned)(CL ? 1 : a.nchunk));
-  return launch_big_lds<conv_mfma_kernel<T, MF, NF, WM, EPI, CL>>(grid, dim3(256), lds, stream, a);
-}
-template <typename T, int MF, int NF, int WM, int EPI>
-inline int launch_one(const ConvArgs& a, int batch, size_t lds, hipStream_t stream) {
-  // chunk loop: built for the 4 x 4-fragment layout; taken when the tile is the mean of three streams (expensive to
-  // stage) and the launch still has two workgroups for every CU without the chunk dimension
-  if constexpr (EPI == EPI_STD && MF == 4 && WM == 4 && NF <= 5) {
-    constexpr int NT = (kWaves / WM) * NF * 16;
-    if (debug_get(DBG_CONV_CL) && a.nchunk >= 2 && a.x2 && (long)ceil_div(a.Nq, NT) * batch >= 512)
-      return launch_one_cl<T, MF, NF, WM, EPI, true>(a, batch, lds, stream);
-  }
-  return launch_one_cl<T, MF, NF, WM, EPI, false>(a, batch, lds, stream);
-}
-
-template <typename T, int MF, int WM, int EPI>
-inline int launch_nf(const ConvDesc& d, const ConvArgs& a, int batch, hipStream_t stream, int* nf_out) {
-  static const int nfs[] = {2, 4, 5, 8, 10};
-  // (the generator epilogue is not built at NF 10: at MF 4 its 160 accumulators plus the generator's temporaries spill,
-  //  656 B of scratch per lane; the tile changes no bit of the result)
-  constexpr bool kRng = EPI == EPI_SAMPLE_RNG;
-  const TileChoice tc = choose_tile(d, a.Nq, batch, nfs, kRng ? 4 : 5);
-  if (nf_out) *nf_out = tc.NF;
-  switch (tc.NF) {
-    case 2: return launch_one<T, MF, 2, WM, EPI>(a, batch, tc.lds, stream);
-    case 4: return launch_one<T, MF, 4, WM, EPI>(a, batch, tc.lds, stream);
-    case 5: if constexpr (MF * 5 * 4 <= 160) return launch_one<T, MF, 5, WM, EPI>(a, batch, tc.lds, stream); break;
-    case 8: if constexpr (MF * 8 * 4 <= 160) return launch_one<T, MF, 8, WM, EPI>(a, batch, tc.lds, stream); break;
-    case 10: if constexpr (MF * 10 * 4 <= 160 && !kRng) return launch_one<T, MF, 10, WM, EPI>(a, batch, tc.lds, stream); break;
-    default: break;
-  }
-  return QVC_ERR_BAD_CONFIG;                                 // no tile fits LDS / registers
+// ------------------------------------------------------------------ dispatch: a LaunchChoice (qvc_select.h) -> its kernel
+// Nothing is decided here: the choice's integers become template arguments (lift), the family's *_built predicate says
+// which tuples exist, and the launch takes grid, block and LDS size from the choice.
+#define QVC_V(x) decltype(x)::value
+template <auto kern, typename Args>
+inline int launch_chosen(const LaunchChoice& c, const Args& a, void* stream) {
+  return launch_big_lds<kern>(dim3(c.grid[0], c.grid[1], c.grid[2]), dim3(c.block), (size_t)c.lds, static_cast<hipStream_t>(stream), a,
+                              (size_t)c.optin_above);
 }
 
 template <typename T>
-int launch_conv_typed(const ConvDesc& d, const ConvArgs& a, int batch, int epi, void* stream_v, int* nf_out) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_v);
-  if (epi == EPI_GAU) {
-    if (d.WM != 4) return QVC_ERR_BAD_CONFIG;
-    switch (d.MF) {
-      case 2: return launch_nf<T, 2, 4, EPI_GAU>(d, a, batch, stream, nf_out);
-      case 4: return launch_nf<T, 4, 4, EPI_GAU>(d, a, batch, stream, nf_out);
-      case 6: return launch_nf<T, 6, 4, EPI_GAU>(d, a, batch, stream, nf_out);
-      default: return QVC_ERR_BAD_CONFIG;
-    }
-  }
-  if (epi == EPI_SAMPLE && !a.noise && a.rng.keys) {          // the draw computed in the epilogue (ConvArgs::rng)
-    if (d.WM != 4 || !d.gau || !a.y32 || !a.bias || a.rg.mul != 1) return QVC_ERR_BAD_CONFIG;
-    switch (d.MF) {
-      case 2: return launch_nf<T, 2, 4, EPI_SAMPLE_RNG>(d, a, batch, stream, nf_out);
-      case 4: return launch_nf<T, 4, 4, EPI_SAMPLE_RNG>(d, a, batch, stream, nf_out);
-      case 6: return launch_nf<T, 6, 4, EPI_SAMPLE_RNG>(d, a, batch, stream, nf_out);
-      default: return QVC_ERR_BAD_CONFIG;
-    }
-  }
-  if (epi == EPI_SAMPLE) {
-    if (d.WM != 4 || !d.gau || !a.noise || !a.y32 || !a.bias) return QVC_ERR_BAD_CONFIG;
-    switch (d.MF) {
-      case 2: return launch_nf<T, 2, 4, EPI_SAMPLE>(d, a, batch, stream, nf_out);
-      case 4: return launch_nf<T, 4, 4, EPI_SAMPLE>(d, a, batch, stream, nf_out);
-      case 6: return launch_nf<T, 6, 4, EPI_SAMPLE>(d, a, batch, stream, nf_out);
-      default: return QVC_ERR_BAD_CONFIG;
-    }
-  }
-  if (epi == EPI_STATS) {
-    if (d.WM != 4 || !d.gau || !a.y32 || !a.bias) return QVC_ERR_BAD_CONFIG;
-    switch (d.MF) {
-      case 2: return launch_nf<T, 2, 4, EPI_STATS>(d, a, batch, stream, nf_out);
-      case 4: return launch_nf<T, 4, 4, EPI_STATS>(d, a, batch, stream, nf_out);
-      case 6: return launch_nf<T, 6, 4, EPI_STATS>(d, a, batch, stream, nf_out);
-      default: return QVC_ERR_BAD_CONFIG;
-    }
-  }
-  if (d.WM > kWaves) return QVC_ERR_BAD_CONFIG;            // 8-wave layouts exist for the fused pair kernel only
-  switch (d.WM * 10 + d.MF) {
-    case 41: return launch_nf<T, 1, 4, EPI_STD>(d, a, batch, stream, nf_out);
-    case 42: return launch_nf<T, 2, 4, EPI_STD>(d, a, batch, stream, nf_out);
-    case 43: return launch_nf<T, 3, 4, EPI_STD>(d, a, batch, stream, nf_out);
-    case 44: return launch_nf<T, 4, 4, EPI_STD>(d, a, batch, stream, nf_out);
-    case 23: return launch_nf<T, 3, 2, EPI_STD>(d, a, batch, stream, nf_out);
-    case 24: return launch_nf<T, 4, 2, EPI_STD>(d, a, batch, stream, nf_out);
-    case 14: return launch_nf<T, 4, 1, EPI_STD>(d, a, batch, stream, nf_out);
-    default: return QVC_ERR_BAD_CONFIG;
-  }
-}
-
-// ---- fused pair: tile choice + dispatch
-inline TileChoice choose_pair_tile(const ConvDesc* ds, int n, int T, int batch) {
-  static const int nfs[] = {2, 4, 5, 8, 10}; // measured at B=32, MF 4: NF 5 (2 workgroups/CU) beats 4 and 8 by 7-35 %
-  const ConvDesc& d = ds[0];
-  const int NWV = block_waves(d);
-  const int WN = NWV / d.WM;
-  int halo1 = 0;                              // the chains of a launch share one tile shape: size it for the widest halo
-  for (int i = 0; i < n; ++i) halo1 = std::max(halo1, (ds[i].taps - 1) * ds[i].dil);
-  const int rowbytes = d.CinP * 2;
-  TileChoice best{0, 0, 0};
-  double best_cost = 1e300;
-  for (int NF : nfs) {
-#ifdef QVC_FORCE_NF
-    if (NF != QVC_FORCE_NF) continue;
-#endif
-    if (d.MF * (NF + 1) * 4 > 160 || (NF == 10 && d.MF > 2)) continue;
-    const size_t lds = (size_t)(WN * (NF + 1) * 16 + halo1) * rowbytes;
-    if (lds > 160 * 1024) continue;
-    const int NT = WN * NF * 16;
-    const long blocks = (long)ceil_div(T, NT) * batch * n;
-    // workgroups that can share a CU: 2 x 4 waves or 1 x 8 waves (two waves per SIMD either way)
-    const int bpc = NWV == 8 ? 1 : (int)std::min<size_t>(2, (160 * 1024) / lds);
-    const long rounds = (blocks + 256L * bpc - 1) / (256L * bpc);
-    // per-workgroup work in frame units: both GEMMs + staging/epilogue; a single 4-wave workgroup per CU
-    // cannot overlap its memory phases with another one's MFMA phases
-    const double work = WN * (NF + 1) * 16 + NT + 0.35 * halo1 + 32.0;
-    const double cost = rounds * bpc * work * ((bpc == 1 && NWV == 4) ? 1.3 : 1.0);
-    if (cost < best_cost) { best_cost = cost; best = TileChoice{NF, (int)blocks, lds}; }
-  }
-  return best;
-}
-
-template <typename T, int MF, int NF, int WM, int NWV, typename TS>
-inline int launch_pair_one(const PairArgs3& a, int batch, size_t lds, hipStream_t stream) {
-  constexpr int NT = (NWV / WM) * NF * 16;
-  const unsigned tiles = (unsigned)ceil_div(a.p[0].T, NT);
-  const dim3 grid = a.chain_major ? dim3(tiles, (unsigned)batch, (unsigned)a.n) : dim3(tiles * (unsigned)a.n, (unsigned)batch, 1);
-  return launch_big_lds<rbpair_kernel<T, MF, NF, WM, NWV, TS>>(grid, dim3(NWV * 64), lds, stream, a);
-}
-
-template <typename T, int MF, int WM, int NWV, typename TS>
-inline int launch_pair_nf(const ConvDesc* ds, const PairArgs3& a, int batch, hipStream_t stream, int* nf_out) {
-  const TileChoice tc = choose_pair_tile(ds, a.n, a.p[0].T, batch);
-  if (nf_out) *nf_out = tc.NF;
-  switch (tc.NF) {
-    case 2: return launch_pair_one<T, MF, 2, WM, NWV, TS>(a, batch, tc.lds, stream);
-    case 4: return launch_pair_one<T, MF, 4, WM, NWV, TS>(a, batch, tc.lds, stream);
-    case 5: return launch_pair_one<T, MF, 5, WM, NWV, TS>(a, batch, tc.lds, stream);
-    case 8: if constexpr (MF * 9 * 4 <= 160) return launch_pair_one<T, MF, 8, WM, NWV, TS>(a, batch, tc.lds, stream); break;
-    case 10: if constexpr (MF * 11 * 4 <= 96) return launch_pair_one<T, MF, 10, WM, NWV, TS>(a, batch, tc.lds, stream); break;
-    default: break;
-  }
-  return QVC_ERR_BAD_CONFIG;
+int dispatch_conv(const LaunchChoice& c, const ConvArgs& a, void* stream) {
+  return lift<EPI_STD, EPI_GAU, EPI_SAMPLE, EPI_STATS, EPI_SAMPLE_RNG>(c.epi, [&](auto EPI) {
+    return lift<1, 2, 3, 4, 6>(c.MF, [&](auto MF) {
+      return lift<1, 2, 4>(c.WM, [&](auto WM) {
+        return lift<2, 4, 5, 8, 10>(c.NF, [&](auto NF) {
+          return lift<0, 1>(c.cl, [&](auto CL) -> int {
+            if constexpr (conv_built(QVC_V(EPI), QVC_V(MF), QVC_V(NF), QVC_V(WM), QVC_V(CL)))
+              return launch_chosen<conv_mfma_kernel<T, QVC_V(MF), QVC_V(NF), QVC_V(WM), QVC_V(EPI), QVC_V(CL) == 1>>(c, a, stream);
+            else return QVC_ERR_BAD_CONFIG;
+          });
+        });
+      });
+    });
+  });
 }
 
 template <typename T, typename TS>
-int launch_pair_typed(const ConvDesc* ds, const PairArgs3& a, int batch, void* stream_v, int* nf_out) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_v);
-  const ConvDesc& d = ds[0];
-  switch (d.WM * 10 + d.MF) {
-    case 41: return launch_pair_nf<T, 1, 4, 4, TS>(ds, a, batch, stream, nf_out);
-    case 42: return launch_pair_nf<T, 2, 4, 4, TS>(ds, a, batch, stream, nf_out);
-    case 43: return launch_pair_nf<T, 3, 4, 4, TS>(ds, a, batch, stream, nf_out);
-    case 44: return launch_pair_nf<T, 4, 4, 4, TS>(ds, a, batch, stream, nf_out);
-    case 23: return launch_pair_nf<T, 3, 2, 4, TS>(ds, a, batch, stream, nf_out);
-    case 24: return launch_pair_nf<T, 4, 2, 4, TS>(ds, a, batch, stream, nf_out);
-    case 14: return launch_pair_nf<T, 4, 1, 4, TS>(ds, a, batch, stream, nf_out);
-    case 82: return launch_pair_nf<T, 2, 8, 8, TS>(ds, a, batch, stream, nf_out);
-    case 83: return launch_pair_nf<T, 3, 8, 8, TS>(ds, a, batch, stream, nf_out);
-    case 84: return launch_pair_nf<T, 4, 8, 8, TS>(ds, a, batch, stream, nf_out);
-    default: return QVC_ERR_BAD_CONFIG;
-  }
-}
-
-// ---- fused WaveNet layer dispatch
-inline int wn_wave_bucket(int waves) { return waves <= 4 ? 4 : (waves <= 8 ? 8 : (waves <= 12 ? 12 : 16)); }
-
-template <typename T, int NF, int WV>
-inline int launch_wn_one(const WnArgs& a, int waves, int batch, hipStream_t stream) {
-  const size_t lds = (size_t)(NF * 16 + a.taps - 1 + NF * 16) * a.HP * 2;
-  dim3 grid((unsigned)ceil_div(a.T, NF * 16), (unsigned)batch), block((unsigned)waves * 64);
-  // hidden = 256 with 64-frame tiles needs (64 + taps-1 + 64) * 512 B > 64 KiB of dynamic LDS: only then the opt-in
-  return a.last ? launch_big_lds<wn_layer_kernel<T, NF, true, WV>>(grid, block, lds, stream, a, 64 * 1024)
-                : launch_big_lds<wn_layer_kernel<T, NF, false, WV>>(grid, block, lds, stream, a, 64 * 1024);
-}
-
-template <typename T, int NF>
-inline int launch_wn_nf(const WnArgs& a, int waves, int batch, hipStream_t stream) {
-  switch (wn_wave_bucket(waves)) {
-    case 4: return launch_wn_one<T, NF, 4>(a, waves, batch, stream);
-    case 8: return launch_wn_one<T, NF, 8>(a, waves, batch, stream);
-    case 12: return launch_wn_one<T, NF, 12>(a, waves, batch, stream);
-    default: return launch_wn_one<T, NF, 16>(a, waves, batch, stream);
-  }
+int dispatch_pair(const LaunchChoice& c, const PairArgs3& a, void* stream) {
+  return lift<1, 2, 3, 4>(c.MF, [&](auto MF) {
+    return lift<1, 2, 4, 8>(c.WM, [&](auto WM) {
+      return lift<4, 8>(c.waves, [&](auto NWV) {
+        return lift<2, 4, 5, 8, 10>(c.NF, [&](auto NF) -> int {
+          if constexpr (pair_built(QVC_V(MF), QVC_V(NF), QVC_V(WM), QVC_V(NWV)))
+            return launch_chosen<rbpair_kernel<T, QVC_V(MF), QVC_V(NF), QVC_V(WM), QVC_V(NWV), TS>>(c, a, stream);
+          else return QVC_ERR_BAD_CONFIG;
+        });
+      });
+    });
+  });
 }
 
 template <typename T>
-int launch_wn_typed(const ConvDesc& din, const WnArgs& a, int batch, void* stream_v, int* nf_out) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_v);
-  // 32-frame tiles unless that leaves most CUs without a workgroup anyway and 64 halves the weight traffic
-  const long blocks32 = (long)ceil_div(a.T, 32) * batch;
-  const int NF = blocks32 >= 512 ? 4 : 2;
-  if (nf_out) *nf_out = NF;
-  if (!wn_layout_ok(din)) return QVC_ERR_BAD_CONFIG;
-  return NF == 4 ? launch_wn_nf<T, 4>(a, din.WM, batch, stream) : launch_wn_nf<T, 2>(a, din.WM, batch, stream);
-}
-
-// ---- whole-stack WaveNet dispatch
-template <typename T, int NF, int PM, int WV>
-inline int launch_wn_stack_pm(const WnStackArgs& a, int waves, int batch, hipStream_t stream) {
-  const size_t lds = (size_t)(NF * 16 + a.taps - 1 + NF * 16) * a.HP * 2;
-  const dim3 grid((unsigned)ceil_div(a.T, NF == 2 ? 16 : kWnOutFrames), (unsigned)batch);
-  return launch_big_lds<wn_stack_kernel<T, NF, PM, WV>>(grid, dim3((unsigned)waves * 64), lds, stream, a);
-}
-
-template <typename T, int NF, int PM>
-inline int launch_wn_stack_wv(const WnStackArgs& a, int waves, int batch, hipStream_t stream) {
-  switch (wn_wave_bucket(waves)) {
-    case 4: return launch_wn_stack_pm<T, NF, PM, 4>(a, waves, batch, stream);
-    case 8: return launch_wn_stack_pm<T, NF, PM, 8>(a, waves, batch, stream);
-    case 12: return launch_wn_stack_pm<T, NF, PM, 12>(a, waves, batch, stream);
-    default: return launch_wn_stack_pm<T, NF, PM, 16>(a, waves, batch, stream);
-  }
+int dispatch_wn(const LaunchChoice& c, const WnArgs& a, void* stream) {
+  return lift<2, 4>(c.NF, [&](auto NF) {
+    return lift<0, 1>(c.last, [&](auto LAST) {
+      return lift<4, 8, 12, 16>(c.waves, [&](auto WV) -> int {
+        static_assert(wn_layer_built(QVC_V(NF), QVC_V(WV)), "not instantiated");
+        return launch_chosen<wn_layer_kernel<T, QVC_V(NF), QVC_V(LAST) == 1, QVC_V(WV)>>(c, a, stream);
+      });
+    });
+  });
 }
 
 template <typename T>
-int launch_wn_stack_typed(const ConvDesc& din, const WnStackArgs& a, int batch, void* stream_v) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_v);
-  if (!wn_stack_ok(din, a.layers)) return QVC_ERR_BAD_CONFIG;
-  int nf = wn_stack_nf(a.taps, a.layers);
-  const int pm = a.w_post ? a.post_mf : 0;
-  if (pm > 1) return QVC_ERR_BAD_CONFIG;
-  // tiny batches (<= 64 of the 32-frame tiles: a quarter of the CUs): 16-frame tiles, when the halo fits a 32-column window
-  if (nf == 3 && 16 + (a.taps - 1) * a.layers <= 32 && (long)batch * ceil_div(a.T, kWnOutFrames) <= 64)
-    return pm ? launch_wn_stack_wv<T, 2, 1>(a, din.WM, batch, stream) : launch_wn_stack_wv<T, 2, 0>(a, din.WM, batch, stream);
-  if (nf == 3) return pm ? launch_wn_stack_wv<T, 3, 1>(a, din.WM, batch, stream) : launch_wn_stack_wv<T, 3, 0>(a, din.WM, batch, stream);
-  return pm ? launch_wn_stack_wv<T, 6, 1>(a, din.WM, batch, stream) : launch_wn_stack_wv<T, 6, 0>(a, din.WM, batch, stream);
+int dispatch_wn_stack(const LaunchChoice& c, const WnStackArgs& a, void* stream) {
+  return lift<2, 3, 6>(c.NF, [&](auto NF) {
+    return lift<0, 1>(c.pm, [&](auto PM) {
+      return lift<4, 8, 12, 16>(c.waves, [&](auto WV) -> int {
+        static_assert(wn_stack_built(QVC_V(NF), QVC_V(PM), QVC_V(WV)), "not instantiated");
+        return launch_chosen<wn_stack_kernel<T, QVC_V(NF), QVC_V(PM), QVC_V(WV)>>(c, a, stream);
+      });
+    });
+  });
 }
 
 }  // namespace qvc

@@ -170,53 +170,13 @@ struct PairArgs3 {
 // A whole ResBlock1 -- n chained pairs (dilations d_0 .. d_{n-1}) -- in ONE launch (qvc_chain_impl.h), for chains whose
 // receptive field is short: p[0].x is read once (tile + halo), p[n-1].y written once, the stream stays on chip in
 // between.  p[q].x / p[q].y of the inner pairs are the buffers the pair-by-pair path would use (the host emulation
-// replays the chain that way).  halo / margin / NT are filled by the launcher (chain_geom).
+// replays the chain that way).  halo / margin / NT are filled by the launcher (qvc_select.h: chain_geom).
 struct ChainArgs {
   PairArgs p[3];
   int32_t n = 3;
   Ragged rg;
   int32_t halo = 0, margin = 0, NT = 0;
 };
-
-struct ChainGeom { int halo, margin, NT; size_t lds; };
-// tile of NF fragments (NF * 16 rows): halo rows per side are recomputed, NT = rows - 2 * halo frames come out
-inline ChainGeom chain_geom(const ConvDesc* d1, int n, int NF) {
-  ChainGeom g{0, 0, 0, 0};
-  for (int q = 0; q < n; ++q) {
-    const int h = (d1[q].taps - 1) / 2;
-    g.halo += h * (d1[q].dil + 1);
-    g.margin = std::max(g.margin, h * d1[q].dil);
-  }
-  g.NT = NF * 16 - 2 * g.halo;
-  g.lds = (size_t)(NF * 16 + 2 * g.margin + NF * 16) * d1[0].CinP * 2;
-  return g;
-}
-
-// Tile choice: the largest tile (fewest recomputed halo frames per produced frame) whose LDS fits the occupancy the
-// layout's pair kernel has -- two 4-wave workgroups or one 8-wave workgroup per CU.
-inline int chain_pick_nf(const ConvDesc* d1, int n, ChainGeom* out) {
-  const int nwv = block_waves(d1[0]);
-  const size_t budget = nwv == 8 ? 160 * 1024 : 80 * 1024;
-  static const int nfs[] = {9, 8, 6, 5, 4};
-  for (int NF : nfs) {
-    if (d1[0].MF * NF * 4 > (d1[0].MF > 2 ? 80 : 96)) continue;  // accumulator registers (+ as many for the B double buffer)
-    const ChainGeom g = chain_geom(d1, n, NF);
-    if (g.lds <= budget && g.NT >= 64 && 4 * 2 * g.halo <= NF * 16) { *out = g; return NF; }   // <= 25 % of the tile recomputed ...
-  }
-  return 0;
-}
-
-inline bool chain_supported(const ConvDesc* d1, const ConvDesc* d2, int n) {
-  if (n < 2 || n > 3) return false;
-  for (int q = 0; q < n; ++q) {
-    if (!pair_supported(d1[q], d2[q]) || !d1[q].lp || !d2[q].lp) return false;
-    if (d1[q].MF != d1[0].MF || d1[q].WM != d1[0].WM || d1[q].CinP != d1[0].CinP || d1[q].taps != d1[0].taps || d1[q].M != d1[0].M) return false;
-  }
-  const int nwv = block_waves(d1[0]);
-  if (d1[0].MF % 2 || nwv != d1[0].WM) return false;             // all waves along the rows, 16-byte epilogue pieces
-  ChainGeom g;
-  return chain_pick_nf(d1, n, &g) != 0;
-}
 
 // One fused WaveNet layer (modules.py:87-112): k-tap conv h->2h + conditioning + tanh*sigmoid gate, then the
 // 1x1 h->2h whose first half is added to the residual stream x and second half to the skip accumulator
@@ -255,7 +215,7 @@ struct WnStackArgs {
   float* z = nullptr; int64_t z_bs = 0; int32_t z_ts = 0;
   float post_sign = -1.f;   // -1: reverse flow, x1 - m (modules.py:217); +1: forward flow, m + x1
   Ragged rg;
-  int32_t wide = 0;          // the 64-frame tile of the continuous-stream kernel may be used (launch_wn_stack decides)
+  int32_t wide = 0;          // the 64-frame tile of the continuous-stream kernel may be used (choose_wn_stack decides)
 #ifdef QVC_STAMP
   unsigned long long* stamps = nullptr;   // developer build only (tools/conv_bench): [workgroup][16 waves][32] phase stamps
 #endif
@@ -299,6 +259,7 @@ struct SampleRowsArgs {
   NoiseRng rng = {};        // noise == nullptr and rng.keys set: drawn in the kernel for key rng.keys[r] at the source's frame t
 };
 
+constexpr int kBands = 4, kBins = 9, kPostC = kBands * 2 * kBins, kTaps = 63;   // tail geometry: sub-bands, bins per band, post-conv channels, FIR taps
 struct TailArgs {     // models.py:394-406 / pqmf.py:106-117; single band: models.py:171-176
   const float* post;  // [B][F][subbands*18]
   const float* fir;   // [subbands][63], gain folded (unused for one band)
@@ -424,16 +385,16 @@ inline std::atomic<int32_t>& debug_launch_steps() {
   return n;
 }
 
-// Launchers return a QVC_* status.  `stream` is a hipStream_t.
-int launch_conv(const ConvDesc& d, ConvArgs a, int batch, int epi, int dtype, void* stream, int* nf_out = nullptr);
+// Launchers return a QVC_* status.  `stream` is a hipStream_t.  The six kernel families below are chosen in qvc_select.h
+// (choose_*: instantiation, tile, grid, LDS) and dispatched by the device translation units (dispatch_*).
+int launch_conv(const ConvDesc& d, ConvArgs a, int batch, int epi, int dtype, void* stream);
 // n pairs (1..3) of equal shape class in one launch; d1[i] / d2[i] are chain i's convs
-int launch_pair3(const ConvDesc* d1, const ConvDesc* d2, const PairArgs3& a, int batch, int dtype, void* stream, int* nf_out = nullptr);
+int launch_pair3(const ConvDesc* d1, const ConvDesc* d2, const PairArgs3& a, int batch, int dtype, void* stream);
 // the n pairs of one ResBlock chained in one launch (chain_supported() says when); d1[q] / d2[q] are pair q's convs
-int launch_chain(const ConvDesc* d1, const ConvDesc* d2, const ChainArgs& a, int batch, int dtype, void* stream, int* nf_out = nullptr);
+int launch_chain(const ConvDesc* d1, const ConvDesc* d2, const ChainArgs& a, int batch, int dtype, void* stream);
 bool wn_stack_supported(const ConvDesc& din, int layers);
 int launch_wn_stack(const ConvDesc& din, const WnStackArgs& a, int batch, int dtype, void* stream);
-int wn_stack_variant(const ConvDesc& din, const WnStackArgs& a, int batch);   // 3 / 2: the continuous-stream kernel (qvc_wn2_impl.h) in its 64- / 32-frame tile, 1: the generic one
-int launch_wn(const ConvDesc& din, WnArgs a, int batch, int dtype, void* stream, int* nf_out = nullptr);
+int launch_wn(const ConvDesc& din, WnArgs a, int batch, int dtype, void* stream);
 int launch_gemv(const GemvArgs& a, void* stream);
 
 // ---- several strided copies / zero fills in ONE launch (the streaming step's ring hand-offs and slides: ~35 strided
@@ -504,13 +465,5 @@ int launch_sample_rows(const SampleRowsArgs& a, void* stream);
 int launch_noise_fill(const NoiseRng& rng, int rows, int channels, int frames, int frame0, float* out, void* stream);
 int launch_tail(const TailArgs& a, void* stream);
 int launch_post_tail(const ConvDesc& d, PostTailArgs a, int batch, int dtype, void* stream);   // bands = post_tail_bands(d)
-
-// Instantiation entry (one translation unit per operand dtype).
-template <typename T> int launch_conv_typed(const ConvDesc& d, const ConvArgs& a, int batch, int epi, void* stream, int* nf_out);
-template <typename T> int launch_wn_stack_typed(const ConvDesc& din, const WnStackArgs& a, int batch, void* stream);
-template <typename T> int launch_wn_typed(const ConvDesc& din, const WnArgs& a, int batch, void* stream, int* nf_out);
-template <typename T> int launch_post_tail_typed(const ConvDesc& d, const PostTailArgs& a, int batch, void* stream);
-template <typename T, typename TS> int launch_chain_typed(const ConvDesc* d1, const ConvDesc* d2, ChainArgs a, int batch, void* stream, int* nf_out);
-template <typename T, typename TS> int launch_pair_typed(const ConvDesc* d1, const PairArgs3& a, int batch, void* stream, int* nf_out);   // TS: stream type
 
 }  // namespace qvc

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <cstdint>
+#include <type_traits>
 #include "../../include/qvc.h"
 
 namespace qvc {
@@ -29,6 +30,15 @@ inline int launch_big_lds(dim3 grid, dim3 block, size_t lds, hipStream_t stream,
   if (lds > optin_above && !allow_big_lds(lds_ok, reinterpret_cast<const void*>(kern))) return QVC_ERR_LAUNCH;
   hipLaunchKernelGGL(kern, grid, block, lds, stream, args);
   return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
+}
+
+// lift<V...>(v, f): f(std::integral_constant<int, V>{}) for the V that equals v -- a run-time integer becomes a template
+// argument.  QVC_ERR_BAD_CONFIG when v is none of them.
+template <int... V, class F>
+inline int lift(int v, F&& f) {
+  int st = QVC_ERR_BAD_CONFIG;
+  (void)((v == V && ((st = f(std::integral_constant<int, V>{})), true)) || ...);
+  return st;
 }
 
 }  // namespace qvc

@@ -34,7 +34,7 @@
 #include <climits>
 #include <cstdlib>
 #include <type_traits>
-#include "qvc_kernels.h"
+#include "qvc_select.h"
 
 namespace qvc {
 
@@ -78,7 +78,7 @@ struct Path {
   bool unit_fm = false;
   // streaming: stage-0 ResBlock outputs handed over from a previous window instead of this call's own (dec_back)
   const void* s0_override[3] = {nullptr, nullptr, nullptr};
-  // the WaveNet stacks may run in the continuous-stream kernel's 64-frame tile (launch_wn_stack picks it where the grid
+  // the WaveNet stacks may run in the continuous-stream kernel's 64-frame tile (choose_wn_stack picks it where the grid
   // is large); the streaming windows keep the 32-frame tile, not measured there
   bool wn_wide = true;
   // the N(0,1) draw of models.py:94 computed at its draw site (NoiseRng) -- used where a call passes noise == nullptr

@@ -23,26 +23,7 @@
 
 namespace qvc {
 
-template <int NF, int NB = kBands> struct PostTailGeom {
-  static constexpr int MF = NB == 1 ? 2 : 3;    // row fragments per wave in conv_post's packed stream
-  static constexpr int WM = NB == 1 ? 1 : 2;    // waves of this kernel along the rows (the other 4/WM split the frames);
-                                                // one band: every wave reads the packing's wave-0 stream (rows 0..31)
-  static constexpr int NT = (4 / WM) * NF * 16; // post-conv frames of the tile
-  static constexpr int HL = NB == 1 ? 2 : 3;    // post-conv frames in front of the first output frame
-  static constexpr int OF = NT - (NB == 1 ? 4 : 7);   // output frames owned
-  static constexpr int SPF = NB == 1 ? 4 : 16;  // output samples per frame
-  static constexpr int OT = OF * SPF;           // output samples owned
-  static constexpr int NY = NB == 1 ? 0 : OT / 4 + 15;   // band samples needed (band synthesis only)
-  static constexpr int PC = NB * 2 * kBins;     // post-conv channels
-  static constexpr int PS = NB == 1 ? 20 : PC;  // LDS floats per post-conv frame (one band: 16-byte rows)
-};
-template <int NF, int NB = kBands>
-inline size_t post_tail_lds(int taps, int CinP) {
-  using G = PostTailGeom<NF, NB>;
-  const size_t tile = std::max<size_t>((size_t)(G::NT + taps - 1) * CinP * 2, (size_t)G::NT * G::PS * 4);
-  return align_up((int64_t)tile, 16) + (size_t)NB * (G::NY + 1) * 4 * (NB > 1 ? 1 : 0);
-}
-
+// (PostTailGeom<NF, NB>, the tile geometry, and post_tail_lds: qvc_select.h -- the chooser sizes the launch from them)
 template <typename T, int NF, int NB = kBands>
 // (three workgroups per CU at NF 4, four at NF 2: the phases of one workgroup are serial -- memory, MFMA, VALU/LDS
 //  in turn -- so it is the neighbours that fill each unit; measured 94 -> 78 us going from two to three)
@@ -218,25 +199,14 @@ void post_tail_kernel(const PostTailArgs A) {
   }
 }
 
-template <typename T, int NF, int NB>
-inline int launch_post_tail_nf(const ConvDesc& d, const PostTailArgs& a, int batch, hipStream_t stream) {
-  const size_t lds = post_tail_lds<NF, NB>(d.taps, d.CinP);
-  if (lds > 160 * 1024) return QVC_ERR_BAD_CONFIG;
-  const int n_out = NB * 4 * (a.F - 1);
-  const dim3 grid((unsigned)ceil_div(n_out, PostTailGeom<NF, NB>::OT), (unsigned)batch);
-  return launch_big_lds<post_tail_kernel<T, NF, NB>>(grid, dim3(256), lds, stream, a);
-}
-
 template <typename T>
-int launch_post_tail_typed(const ConvDesc& d, const PostTailArgs& a, int batch, void* stream_v) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_v);
-  const int nb = post_tail_bands(d);
-  if (!nb || a.F < 2 || !a.c.x2 || !a.c.x3 || a.c.x_kind != XK_OP_FM) return QVC_ERR_BAD_CONFIG;
-  // one band: 4 waves along the frames at NF 2 = the same 128-frame tile as the four-band default
-  if (nb == 1) return launch_post_tail_nf<T, 2, 1>(d, a, batch, stream);
-  if (!a.fir) return QVC_ERR_BAD_CONFIG;
-  if (debug_get(DBG_POST_TAIL_NF) == 2) return launch_post_tail_nf<T, 2, kBands>(d, a, batch, stream);
-  return launch_post_tail_nf<T, 4, kBands>(d, a, batch, stream);
+int dispatch_post_tail(const LaunchChoice& c, const PostTailArgs& a, void* stream) {
+  return lift<2, 4>(c.NF, [&](auto NF) {
+    return lift<1, kBands>(c.bands, [&](auto NB) -> int {
+      if constexpr (post_tail_built(QVC_V(NF), QVC_V(NB))) return launch_chosen<post_tail_kernel<T, QVC_V(NF), QVC_V(NB)>>(c, a, stream);
+      else return QVC_ERR_BAD_CONFIG;
+    });
+  });
 }
 
 }  // namespace qvc

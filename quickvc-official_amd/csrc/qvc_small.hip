@@ -14,7 +14,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "qvc_launch_util.h"
-#include "qvc_kernels.h"
+#include "qvc_select.h"
 #include "qvc_tail_impl.h"
 
 namespace qvc {
@@ -558,79 +558,59 @@ int launch_copy_counted(const CountedHead& h, const CountedDesc* d, int n, void*
   return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
 }
 
-// ------------------------------------------------------------------ conv dispatcher
-int launch_conv(const ConvDesc& d, ConvArgs a, int batch, int epi, int dtype, void* stream, int* nf_out) {
+// ------------------------------------------------------------------ the launchers of the six chosen families
+// choose_* (qvc_select.h) decides, dispatch_* (the translation unit that holds the kernels) launches; here the choice's
+// operand / stream type picks the instantiation entry.
+int launch_conv(const ConvDesc& d, ConvArgs a, int batch, int epi, int dtype, void* stream, LaunchChoice& c) {
   conv_geometry(a, d);
-  if (d.lp && (epi != EPI_STD || !a.y16 || a.y32 || a.y32b || a.res || a.res16 || d.MF % 2)) return QVC_ERR_BAD_CONFIG;
-  if (dtype == QVC_F16) return launch_conv_typed<_Float16>(d, a, batch, epi, stream, nf_out);
-  if (dtype == QVC_BF16) return launch_conv_typed<__bf16>(d, a, batch, epi, stream, nf_out);
-  return QVC_ERR_BAD_ARG;
+  c = choose_conv(d, a, batch, epi, dtype);
+  if (c.status != QVC_OK) return c.status;
+  return c.op == QVC_F16 ? dispatch_conv<_Float16>(c, a, stream) : dispatch_conv<__bf16>(c, a, stream);
 }
 
-int launch_post_tail(const ConvDesc& d, PostTailArgs a, int batch, int dtype, void* stream) {
+int launch_post_tail(const ConvDesc& d, PostTailArgs a, int batch, int dtype, void* stream, LaunchChoice& c) {
   conv_geometry(a.c, d);
-  if (dtype == QVC_F16) return launch_post_tail_typed<_Float16>(d, a, batch, stream);
-  if (dtype == QVC_BF16) return launch_post_tail_typed<__bf16>(d, a, batch, stream);
-  return QVC_ERR_BAD_ARG;
+  c = choose_post_tail(d, a, batch, dtype);
+  if (c.status != QVC_OK) return c.status;
+  return c.op == QVC_F16 ? dispatch_post_tail<_Float16>(c, a, stream) : dispatch_post_tail<__bf16>(c, a, stream);
 }
 
 bool wn_stack_supported(const ConvDesc& din, int layers) { return wn_stack_ok(din, layers); }
 
-// qvc_wn2.hip: the continuous-stream stack kernel for the shipped shape, in a 32- and a 64-frame tile.  The 64-frame
-// tile where the caller allows it (a.wide: not the streaming windows) and the 32-frame grid would fill the chip: there
-// it takes the same time per layer on half the CUs.  Smaller grids keep the 32-frame tile: their CUs are
-// free anyway, and a tile twice as wide takes longer per layer.  Debug switch "wn_kernel": 1 = the generic kernel,
-// 2 = always the 32-frame tile, 3 = always the 64-frame tile (where the kernel applies).
-template <typename T> int launch_wn_stack2_typed(const ConvDesc& din, const WnStackArgs& a, int batch, void* stream, bool wide);
-bool wn_stack2_supported(const ConvDesc& din, const WnStackArgs& a);
-constexpr long kWnWideMinTiles = 256;        // 32-frame workgroups (one per CU) from which the 64-frame tile is used
-int wn_stack_variant(const ConvDesc& din, const WnStackArgs& a, int batch) {
-  const int sw = debug_get(DBG_WN_KERNEL);
-  if (sw == 1 || !wn_stack2_supported(din, a)) return 1;
-  if (sw == 2) return 2;
-  if (sw == 3) return 3;
-  return a.wide && (long)batch * ceil_div(a.T, kWnOutFrames) >= kWnWideMinTiles ? 3 : 2;
+int launch_wn_stack(const ConvDesc& din, const WnStackArgs& a, int batch, int dtype, void* stream, LaunchChoice& c) {
+  c = choose_wn_stack(din, a, batch, dtype);
+  if (c.status != QVC_OK) return c.status;
+  if (c.family == LF_WN_STACK2) return c.op == QVC_F16 ? dispatch_wn_stack2<_Float16>(c, a, stream) : dispatch_wn_stack2<__bf16>(c, a, stream);
+  return c.op == QVC_F16 ? dispatch_wn_stack<_Float16>(c, a, stream) : dispatch_wn_stack<__bf16>(c, a, stream);
 }
 
-int launch_wn_stack(const ConvDesc& din, const WnStackArgs& a, int batch, int dtype, void* stream) {
-  const int v = wn_stack_variant(din, a, batch);
-  if (v >= 2) {
-    if (dtype == QVC_F16) return launch_wn_stack2_typed<_Float16>(din, a, batch, stream, v == 3);
-    if (dtype == QVC_BF16) return launch_wn_stack2_typed<__bf16>(din, a, batch, stream, v == 3);
-    return QVC_ERR_BAD_ARG;
-  }
-  if (dtype == QVC_F16) return launch_wn_stack_typed<_Float16>(din, a, batch, stream);
-  if (dtype == QVC_BF16) return launch_wn_stack_typed<__bf16>(din, a, batch, stream);
-  return QVC_ERR_BAD_ARG;
+int launch_wn(const ConvDesc& din, const WnArgs& a, int batch, int dtype, void* stream, LaunchChoice& c) {
+  c = choose_wn(din, a, batch, dtype);
+  if (c.status != QVC_OK) return c.status;
+  return c.op == QVC_F16 ? dispatch_wn<_Float16>(c, a, stream) : dispatch_wn<__bf16>(c, a, stream);
 }
 
-int launch_wn(const ConvDesc& din, WnArgs a, int batch, int dtype, void* stream, int* nf_out) {
-  if (dtype == QVC_F16) return launch_wn_typed<_Float16>(din, a, batch, stream, nf_out);
-  if (dtype == QVC_BF16) return launch_wn_typed<__bf16>(din, a, batch, stream, nf_out);
-  return QVC_ERR_BAD_ARG;
+int launch_pair3(const ConvDesc* d1, const ConvDesc* d2, const PairArgs3& a, int batch, int dtype, void* stream, LaunchChoice& c) {
+  c = choose_pair(d1, d2, a, batch, dtype);
+  if (c.status != QVC_OK) return c.status;
+  if (c.op == QVC_F16) return dispatch_pair<_Float16, _Float16>(c, a, stream);
+  return c.ts == QVC_BF16 ? dispatch_pair<__bf16, __bf16>(c, a, stream) : dispatch_pair<__bf16, _Float16>(c, a, stream);   // QVC_BF16X: f16 stream
 }
 
-int launch_pair3(const ConvDesc* d1, const ConvDesc* d2, const PairArgs3& a, int batch, int dtype, void* stream, int* nf_out) {
-  if (a.n < 1 || a.n > 3) return QVC_ERR_BAD_ARG;
-  for (int i = 0; i < a.n; ++i) {
-    if (!pair_supported(d1[i], d2[i]) || !d1[i].lp || !d2[i].lp) return QVC_ERR_BAD_CONFIG;
-    if (d1[i].MF != d1[0].MF || d1[i].WM != d1[0].WM || d1[i].CinP != d1[0].CinP) return QVC_ERR_BAD_CONFIG;
-    if (a.p[i].T != a.p[0].T || a.p[i].C != a.p[0].C || a.p[i].CP != a.p[0].CP) return QVC_ERR_BAD_ARG;
-  }
-  if (dtype == QVC_F16) return launch_pair_typed<_Float16, _Float16>(d1, a, batch, stream, nf_out);
-  if (dtype == QVC_BF16) return launch_pair_typed<__bf16, __bf16>(d1, a, batch, stream, nf_out);
-  if (dtype == QVC_BF16X) return launch_pair_typed<__bf16, _Float16>(d1, a, batch, stream, nf_out);   // bf16 operands, f16 stream
-  return QVC_ERR_BAD_ARG;
+int launch_chain(const ConvDesc* d1, const ConvDesc* d2, ChainArgs a, int batch, int dtype, void* stream, LaunchChoice& c) {
+  c = choose_chain(d1, d2, a, batch, dtype);
+  if (c.status != QVC_OK) return c.status;
+  a.halo = c.halo; a.margin = c.margin; a.NT = c.NT;
+  if (c.op == QVC_F16) return dispatch_chain<_Float16, _Float16>(c, a, stream);
+  return c.ts == QVC_BF16 ? dispatch_chain<__bf16, __bf16>(c, a, stream) : dispatch_chain<__bf16, _Float16>(c, a, stream);
 }
 
-int launch_chain(const ConvDesc* d1, const ConvDesc* d2, const ChainArgs& a, int batch, int dtype, void* stream, int* nf_out) {
-  if (!chain_supported(d1, d2, a.n)) return QVC_ERR_BAD_CONFIG;
-  for (int q = 1; q < a.n; ++q)
-    if (a.p[q].T != a.p[0].T || a.p[q].C != a.p[0].C || a.p[q].CP != a.p[0].CP || a.p[q].bs != a.p[0].bs) return QVC_ERR_BAD_ARG;
-  if (dtype == QVC_F16) return launch_chain_typed<_Float16, _Float16>(d1, d2, a, batch, stream, nf_out);
-  if (dtype == QVC_BF16) return launch_chain_typed<__bf16, __bf16>(d1, d2, a, batch, stream, nf_out);
-  if (dtype == QVC_BF16X) return launch_chain_typed<__bf16, _Float16>(d1, d2, a, batch, stream, nf_out);
-  return QVC_ERR_BAD_ARG;
-}
+// the forms of qvc_kernels.h: the choice is not handed back
+int launch_conv(const ConvDesc& d, ConvArgs a, int batch, int epi, int dtype, void* stream) { LaunchChoice c; return launch_conv(d, a, batch, epi, dtype, stream, c); }
+int launch_post_tail(const ConvDesc& d, PostTailArgs a, int batch, int dtype, void* stream) { LaunchChoice c; return launch_post_tail(d, a, batch, dtype, stream, c); }
+int launch_wn_stack(const ConvDesc& din, const WnStackArgs& a, int batch, int dtype, void* stream) { LaunchChoice c; return launch_wn_stack(din, a, batch, dtype, stream, c); }
+int launch_wn(const ConvDesc& din, WnArgs a, int batch, int dtype, void* stream) { LaunchChoice c; return launch_wn(din, a, batch, dtype, stream, c); }
+int launch_pair3(const ConvDesc* d1, const ConvDesc* d2, const PairArgs3& a, int batch, int dtype, void* stream) { LaunchChoice c; return launch_pair3(d1, d2, a, batch, dtype, stream, c); }
+int launch_chain(const ConvDesc* d1, const ConvDesc* d2, const ChainArgs& a, int batch, int dtype, void* stream) { LaunchChoice c; return launch_chain(d1, d2, a, batch, dtype, stream, c); }
 
 }  // namespace qvc

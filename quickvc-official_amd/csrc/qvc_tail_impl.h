@@ -6,10 +6,9 @@
 //   output        out[o], o in [0, 16(F-1)): out[o] = sum_k sum_n fir[k][4n - o + 31] * y_k[n]
 #pragma once
 #include <hip/hip_runtime.h>
+#include "qvc_kernels.h"      // kBands, kBins, kPostC, kTaps
 
 namespace qvc {
-
-constexpr int kBands = 4, kBins = 9, kPostC = kBands * 2 * kBins, kTaps = 63;
 
 // cos / sin(2*pi*j/16), j = 0..15
 #define QVC_C16 {1.f, 0.92387953251128674f, 0.70710678118654752f, 0.38268343236508977f, 0.f, -0.38268343236508977f,   \

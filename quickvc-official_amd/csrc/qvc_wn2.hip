@@ -2,9 +2,8 @@
 // that it compiles beside the conv kernels.
 #include "qvc_wn2_impl.h"
 namespace qvc {
-template int launch_wn_stack2_typed<_Float16>(const ConvDesc&, const WnStackArgs&, int, void*, bool);
-template int launch_wn_stack2_typed<__bf16>(const ConvDesc&, const WnStackArgs&, int, void*, bool);
-bool wn_stack2_supported(const ConvDesc& din, const WnStackArgs& a) { return wn2_supported(din, a); }
+template int dispatch_wn_stack2<_Float16>(const LaunchChoice&, const WnStackArgs&, void*);
+template int dispatch_wn_stack2<__bf16>(const LaunchChoice&, const WnStackArgs&, void*);
 }  // namespace qvc
 #ifdef QVC_SATCOUNT
 namespace qvc { QVC_SAT_READER(sat_count_wn2) }

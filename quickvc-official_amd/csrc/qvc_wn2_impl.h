@@ -36,16 +36,7 @@ __device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make
 #ifndef QVC_WN2_SYNC
 #define QVC_WN2_SYNC 0
 #endif
-// register ring depth (k-steps) of the 64-frame tile; must divide a layer's 36 k-steps
-#ifndef QVC_WN2_WIDE_RING
-#define QVC_WN2_WIDE_RING 4
-#endif
-
-// the shapes this kernel is built for
-inline bool wn2_supported(const ConvDesc& din, const WnStackArgs& a) {
-  return wn_layout_ok(din) && din.CinP == 192 && din.taps == 5 && a.layers >= 1 && a.layers <= 4 && wn_stack_nf(din.taps, a.layers) == 3 &&
-         a.HP == 192 && a.H <= 192 && a.KS == 6 && a.nIt1 == 30 && (!a.w_post || a.post_mf == 1) && (!a.w_pre || a.pre_KS <= 6);
-}
+// (QVC_WN2_WIDE_RING, the register ring depth of the 64-frame tile, wn2_supported and wn2_lds_bytes: qvc_select.h)
 
 // Window of NF x 16 columns: NB - 16 produced frames + up to 2 x 8 halo (4 layers of a k-5 conv).  NF = 3 (32 frames
 // per workgroup) is the kernel above; NF = 5 is the wide tile (64 frames, half the workgroups at batch 32): each weight
@@ -54,12 +45,6 @@ inline bool wn2_supported(const ConvDesc& din, const WnStackArgs& a) {
 // wide tile writes the gated activations over the x tile (x is dead after GEMM1 and rebuilt from the fp32 residual
 // slots after GEMM2), which costs two barriers per layer: before the gate's stores and before put_x.  RING: k-steps in
 // flight per wave (at five MFMAs per fragment four of them hold as many bytes in flight per CU-cycle as six at three).
-template <int KS, int TAPS, int NF>
-constexpr size_t wn2_lds_bytes() {
-  constexpr int RB = KS * 64, R = NF * 16 + TAPS - 1, NTH = KS * 2 * 64;
-  return (size_t)(NF > 3 ? R : R + NF * 16) * RB + (size_t)2 * NF * NTH * 16;    // x (+ gated) tile, fp32 residual + skip slots
-}
-
 template <typename T, int KS, int TAPS, int PM, int NF = 3, int RING = 6>
 __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArgs a) {
   using O = Op<T>;
@@ -83,7 +68,7 @@ __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArg
   // fp32 residual stream and skip sum of the window: lane-private 16-byte slots in LDS ([n][thread]), touched only in a
   // layer's epilogue -- in registers (24 per lane) they pushed the K loops' ring into scratch memory
   constexpr int XRES = ALIAS ? R * RB : ACTS + NB * RB, OACC = XRES + NF * NTH * 16;
-  static_assert(OACC + NF * NTH * 16 == (int)wn2_lds_bytes<KS, TAPS, NF>(), "LDS layout");
+  static_assert(OACC + NF * NTH * 16 == (int)wn2_lds_bytes(KS, TAPS, NF), "LDS layout");
   const Swz sm{0, 7, 0};
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -474,22 +459,19 @@ __global__ __launch_bounds__(KS * 2 * 64) void wn_stack2_kernel(const WnStackArg
 #endif
 }
 
-template <typename T, int NF, int RING>
-int launch_wn_stack2_nf(const WnStackArgs& a, int batch, hipStream_t stream) {
-  constexpr int KS = 6, TAPS = 5;
-  constexpr size_t lds = wn2_lds_bytes<KS, TAPS, NF>();
-  static_assert(lds <= 160 * 1024, "one workgroup per CU");
-  const dim3 grid((unsigned)ceil_div(a.T, NF * 16 - 16), (unsigned)batch), block(KS * 2 * 64);
-  return a.w_post ? launch_big_lds<wn_stack2_kernel<T, KS, TAPS, 1, NF, RING>>(grid, block, lds, stream, a)
-                  : launch_big_lds<wn_stack2_kernel<T, KS, TAPS, 0, NF, RING>>(grid, block, lds, stream, a);
-}
-
-// wide: the 64-frame tile (NF = 5), else the 32-frame one
 template <typename T>
-int launch_wn_stack2_typed(const ConvDesc& din, const WnStackArgs& a, int batch, void* stream_v, bool wide) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_v);
-  if (!wn2_supported(din, a)) return QVC_ERR_BAD_CONFIG;
-  return wide ? launch_wn_stack2_nf<T, 5, QVC_WN2_WIDE_RING>(a, batch, stream) : launch_wn_stack2_nf<T, 3, 6>(a, batch, stream);
+int dispatch_wn_stack2(const LaunchChoice& c, const WnStackArgs& a, void* stream) {
+  constexpr int KS = 6, TAPS = 5;
+  return lift<0, 1>(c.pm, [&](auto PM) {
+    return lift<3, 5>(c.NF, [&](auto NF) {
+      return lift<6, QVC_WN2_WIDE_RING>(c.ring, [&](auto RING) -> int {
+        static_assert(wn2_lds_bytes(KS, TAPS, QVC_V(NF)) <= 160 * 1024, "one workgroup per CU");
+        if constexpr (wn_stack2_built(QVC_V(PM), QVC_V(NF), QVC_V(RING)))
+          return launch_chosen<wn_stack2_kernel<T, KS, TAPS, QVC_V(PM), QVC_V(NF), QVC_V(RING)>>(c, a, stream);
+        else return QVC_ERR_BAD_CONFIG;
+      });
+    });
+  });
 }
 
 }  // namespace qvc

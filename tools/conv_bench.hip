@@ -6,7 +6,7 @@
 #include <cstring>
 #include <vector>
 #include <string>
-#include "../quickvc-official_amd/csrc/qvc_kernels.h"
+#include "../quickvc-official_amd/csrc/qvc_select.h"
 #include "../quickvc-official_amd/csrc/qvc_pack_util.h"
 using namespace qvc;
 
@@ -64,16 +64,16 @@ int main(int argc, char** argv) {
     if (s.kind == 1) { a.x = x16; a.x_kind = XK_OP_FM; a.x_bs = bs_in; a.x_ts = s.Cin; a.res = res; a.res_bs = bs_out; a.res_ts = s.M; a.y32 = y32; a.y32_bs = bs_out; a.y32_ts = s.M; }
     if (s.kind == 2) { a.x = x32; a.x_kind = XK_F32_FM; a.x_bs = bs_in; a.x_ts = s.Cin; a.bbias = bb; a.bbias_bs = 0; a.gau_H = s.M / 2; a.y16 = y16; a.y16_bs = (int64_t)s.T * s.M / 2; a.y16_ts = s.M / 2; epi = EPI_GAU; }
     if (s.kind == 3) { a.x = x16; a.x_kind = XK_OP_FM; a.x_bs = bs_in; a.x_ts = s.Cin; a.split = s.M / 2; a.res = res; a.res_bs = (int64_t)s.T * s.M / 2; a.res_ts = s.M / 2; a.y32 = res; a.y32b = y32; a.y32_bs = (int64_t)s.T * s.M / 2; a.y32_ts = s.M / 2; }
-    int nf = 0;
-    for (int i = 0; i < 3; ++i) if (launch_conv(d, a, B, epi, QVC_F16, st, &nf) != QVC_OK) { printf("%s: launch failed\n", s.name); break; }
+    LaunchChoice lc;
+    for (int i = 0; i < 3; ++i) if (launch_conv(d, a, B, epi, QVC_F16, st, lc) != QVC_OK) { printf("%s: launch failed\n", s.name); break; }
     CK(hipStreamSynchronize(st));
     CK(hipEventRecord(e0, st));
-    for (int i = 0; i < reps; ++i) launch_conv(d, a, B, epi, QVC_F16, st, &nf);
+    for (int i = 0; i < reps; ++i) launch_conv(d, a, B, epi, QVC_F16, st, lc);
     CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));
     float ms; CK(hipEventElapsedTime(&ms, e0, e1));
     const double us = ms * 1e3 / reps;
     const double flops = 2.0 * B * s.T * (double)s.M * s.k * s.Cin;
-    printf("%-14s MF%d WM%d NF%-2d chunks%d  %8.1f us  %7.1f TF  (%.1f%% of 2.5PF)\n", s.name, d.MF, d.WM, nf, d.nchunk, us, flops / us * 1e-6, flops / us * 1e-6 / 25.0);
+    printf("%-14s MF%d WM%d NF%-2d chunks%d  %8.1f us  %7.1f TF  (%.1f%% of 2.5PF)\n", s.name, d.MF, d.WM, lc.NF, d.nchunk, us, flops / us * 1e-6, flops / us * 1e-6 / 25.0);
     CK(hipFree(dw));
   }
   if (!only_pairs && !only_wn) {  // ---- polyphase up-samplers, conv_pre (weight-heavy, few frames)
@@ -95,11 +95,11 @@ int main(int argc, char** argv) {
       if (u.kind == 0) { a.x = x16; a.x_kind = XK_OP_FM; } else { a.x = x32; a.x_kind = XK_F32_FM; a.slope_in = 0.1f; }
       a.x_bs = (int64_t)u.T * u.Cin; a.x_ts = u.Cin;
       a.y16 = y16; a.y16_bs = (int64_t)t_out * u.Cout; a.y16_ts = u.Cout;
-      int nf = 0;
-      for (int i = 0; i < 3; ++i) if (launch_conv(d, a, B, EPI_STD, QVC_F16, st, &nf) != QVC_OK) { printf("%s: launch failed\n", u.name); break; }
+      LaunchChoice lc;
+      for (int i = 0; i < 3; ++i) if (launch_conv(d, a, B, EPI_STD, QVC_F16, st, lc) != QVC_OK) { printf("%s: launch failed\n", u.name); break; }
       CK(hipStreamSynchronize(st));
       CK(hipEventRecord(e0, st));
-      for (int i = 0; i < reps; ++i) launch_conv(d, a, B, EPI_STD, QVC_F16, st, &nf);
+      for (int i = 0; i < reps; ++i) launch_conv(d, a, B, EPI_STD, QVC_F16, st, lc);
       CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));
       float ms; CK(hipEventElapsedTime(&ms, e0, e1));
       const double us_ = ms * 1e3 / reps;
@@ -107,7 +107,7 @@ int main(int argc, char** argv) {
       uint64_t sum = 0;   // checksum of the output: tile variants (QVC_WIDE_CONV=0/2, QVC_WIDE_NF, QVC_WIDE_CL) must agree bit for bit
       { std::vector<uint16_t> hy((size_t)B * t_out * u.Cout); CK(hipMemcpy(hy.data(), y16, hy.size() * 2, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < hy.size(); ++i) sum = sum * 1000003u + hy[i]; }
-      printf("%-16s MF%d WM%d NF%-3d chunks%d %8.1f us  %7.1f TF  sum %016llx\n", u.name, d.MF, d.WM, nf, d.nchunk, us_, flops / us_ * 1e-6, (unsigned long long)sum);
+      printf("%-16s MF%d WM%d NF%-3d chunks%d %8.1f us  %7.1f TF  sum %016llx\n", u.name, d.MF, d.WM, lc.NF, d.nchunk, us_, flops / us_ * 1e-6, (unsigned long long)sum);
       CK(hipFree(dw));
     }
   }
@@ -123,10 +123,10 @@ int main(int argc, char** argv) {
     // evict caches between timed loops with a big memset
     WnArgs a; a.bs = (int64_t)T * H; a.T = T; a.H = H; a.HP = din.CinP; a.bbias = bb; a.bbias_bs = 0;
     a.taps = 5; a.KS = din.KS(); a.nIt1 = din.nIt(); a.last = 0; a.oacc = y32;
-    int nf = 0;
+    LaunchChoice lc;
     auto run = [&]() { for (int l = 0; l < L; ++l) { a.x_in = l % 2 ? res : x32; a.x_out = l % 2 ? x32 : res;
         a.w_in = (char*)dw + per * l; a.w_rs = (char*)dw + per * l + drs.w_off; a.b_rs = (const float*)((char*)dw + per * l + drs.b_off);
-        launch_wn(din, a, B, QVC_F16, st, &nf); } };
+        launch_wn(din, a, B, QVC_F16, st, lc); } };
     run(); CK(hipStreamSynchronize(st));
     CK(hipEventRecord(e0, st));
     for (int i = 0; i < reps; ++i) run();
@@ -134,7 +134,7 @@ int main(int argc, char** argv) {
     float ms; CK(hipEventElapsedTime(&ms, e0, e1));
     const double us = ms * 1e3 / reps / L;
     const double flops = 2.0 * B * T * (double)H * (2.0 * H * 5 + 2.0 * H);
-    printf("%-14s W%-2d NF%-2d               %8.1f us/layer  %7.1f TF  (%.1f%% of 2.5PF)\n", "wn layer x16", din.WM, nf, us, flops / us * 1e-6, flops / us * 1e-6 / 25.0);
+    printf("%-14s W%-2d NF%-2d               %8.1f us/layer  %7.1f TF  (%.1f%% of 2.5PF)\n", "wn layer x16", din.WM, lc.NF, us, flops / us * 1e-6, flops / us * 1e-6 / 25.0);
     CK(hipFree(dw));
   }
   if (!only_pairs) {  // ---- whole-stack WaveNet launches: 4 layers per launch, 8 distinct weight sets (cold weights)
@@ -255,38 +255,38 @@ int main(int argc, char** argv) {
         a.w1 = dws[c]; a.b1 = (const float*)((char*)dws[c] + d1.b_off); a.w2 = dws[c]; a.b2 = a.b1;
         a.k = ks[c]; a.dil = dils[q]; a.KS = d1.KS(); a.nIt = d1.nIt(); a.y = (char*)y16 + c * slice * 2;
         d1s[c] = d1; d2s[c] = d2; a3.p[c] = a;
-        int nf = 0;
+        LaunchChoice lc;
         PairArgs3 a1; a1.p[0] = a;                     // the chain alone: a launch of one pair
-        for (int i = 0; i < 3; ++i) if (launch_pair3(&d1, &d2, a1, B, QVC_F16, st, &nf) != QVC_OK) { printf("%s: launch failed\n", sg.name); break; }
+        for (int i = 0; i < 3; ++i) if (launch_pair3(&d1, &d2, a1, B, QVC_F16, st, lc) != QVC_OK) { printf("%s: launch failed\n", sg.name); break; }
         CK(hipStreamSynchronize(st));
         CK(hipEventRecord(e0, st));
-        for (int i = 0; i < reps; ++i) launch_pair3(&d1, &d2, a1, B, QVC_F16, st, &nf);
+        for (int i = 0; i < reps; ++i) launch_pair3(&d1, &d2, a1, B, QVC_F16, st, lc);
         CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));
         const double us = ms * 1e3 / reps;
         const double flops = 2.0 * 2.0 * B * sg.T * (double)sg.C * ks[c] * sg.C;
         tot_us += us; tot_fl += flops;
-        printf("pair %s k%-2d d%d  MF%d WM%d NF%-2d          %8.1f us  %7.1f TF  (%.1f%% of 2.5PF)\n", sg.name, ks[c], dils[q], d1.MF, d1.WM, nf, us, flops / us * 1e-6, flops / us * 1e-6 / 25.0);
+        printf("pair %s k%-2d d%d  MF%d WM%d NF%-2d          %8.1f us  %7.1f TF  (%.1f%% of 2.5PF)\n", sg.name, ks[c], dils[q], d1.MF, d1.WM, lc.NF, us, flops / us * 1e-6, flops / us * 1e-6 / 25.0);
       }
       // one launch for the three chains: chains interleaved on the CUs (x % n) vs chain-major grid (longest chain first)
       for (int cm = 0; cm < 2; ++cm) {
         a3.chain_major = cm;
-        int nf = 0;
-        for (int i = 0; i < 3; ++i) if (launch_pair3(d1s, d2s, a3, B, QVC_F16, st, &nf) != QVC_OK) { printf("%s: launch3 failed\n", sg.name); break; }
+        LaunchChoice lc;
+        for (int i = 0; i < 3; ++i) if (launch_pair3(d1s, d2s, a3, B, QVC_F16, st, lc) != QVC_OK) { printf("%s: launch3 failed\n", sg.name); break; }
         CK(hipStreamSynchronize(st));
         CK(hipEventRecord(e0, st));
-        for (int i = 0; i < reps; ++i) launch_pair3(d1s, d2s, a3, B, QVC_F16, st, &nf);
+        for (int i = 0; i < reps; ++i) launch_pair3(d1s, d2s, a3, B, QVC_F16, st, lc);
         CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));
-        printf("pair3 %s d%d  %-12s NF%-3d %8.1f us  %7.1f TF\n", sg.name, dils[q], cm ? "chain-major" : "interleaved", nf, ms * 1e3 / reps, tot_fl / (ms * 1e3 / reps) * 1e-6);
+        printf("pair3 %s d%d  %-12s NF%-3d %8.1f us  %7.1f TF\n", sg.name, dils[q], cm ? "chain-major" : "interleaved", lc.NF, ms * 1e3 / reps, tot_fl / (ms * 1e3 / reps) * 1e-6);
 #ifdef QVC_STAMP
         if (cm == 1 && q == 0) {   // phase stamps of one chain-major launch (s_memtime cycles), wave 0 of every workgroup
-          const int NT = nf * 16 * (d1s[0].WM == block_waves(d1s[0]) ? 1 : block_waves(d1s[0]) / d1s[0].WM);
+          const int NT = lc.NF * 16 * (d1s[0].WM == block_waves(d1s[0]) ? 1 : block_waves(d1s[0]) / d1s[0].WM);
           const int tiles = ceil_div(sg.T, NT);
           const size_t nwg = (size_t)tiles * B * 3;
           unsigned long long* dst; CK(hipMalloc(&dst, nwg * 64 * 8)); CK(hipMemset(dst, 0, nwg * 64 * 8));
           a3.stamps = dst;
-          launch_pair3(d1s, d2s, a3, B, QVC_F16, st, &nf);
+          launch_pair3(d1s, d2s, a3, B, QVC_F16, st, lc);
           CK(hipStreamSynchronize(st));
           a3.stamps = nullptr;
           std::vector<unsigned long long> hs(nwg * 64);

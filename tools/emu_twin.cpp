@@ -13,6 +13,8 @@
 // backend has no single-band tail and no generator form of the noise: band-synthesis decoders, pointer form only.
 // TraceBackend stands alone: it computes nothing and writes down every backend call of a Path, field by field
 // (qvc_emu_path_trace; tests/test_path_trace_host.py) -- every decoder and every form, since nothing is run.
+// SelectBackend walks the same calls and writes down, per launch, the choice its family's chooser returns
+// (csrc/qvc_select.h; qvc_emu_launch_trace; tests/test_launch_trace_host.py).
 #include "../oracle/qvc_emu.cpp"
 
 #include <array>
@@ -245,6 +247,11 @@ struct TraceBackend {
   void fields(const qvc::PairArgs& a) { PUT(a.x, a.bs, a.T, a.C, a.CP, a.w1, a.b1, a.w2, a.b2, a.k, a.dil, a.KS, a.nIt, a.slope, a.y); }
   // the ConvDesc fields the launchers read
   void fields(const qvc::ConvDesc& d) { PUT(d.MF, d.WM, d.nchunk, d.lp, d.gau, d.M, d.taps); }
+  static_assert(sizeof(qvc::LaunchChoice) == 104, "list the new field below");
+  void fields(const qvc::LaunchChoice& c) {
+    PUT(c.status, c.family, c.op, c.ts, c.MF, c.NF, c.WM, c.waves, c.epi, c.cl, c.last, c.pm, c.bands, c.ring, c.halo, c.margin, c.NT, c.grid, c.block,
+        c.lds, c.optin_above);
+  }
   // descriptors [0, n) of a launch of up to three chains / pairs; the rest as a default descriptor
   struct Descs { const qvc::ConvDesc* d; int n; };
   void fields(const Descs& v) {
@@ -313,17 +320,68 @@ struct TraceBackend {
   static_assert(sizeof(qvc::SpkMapArgs) == 72, "list the new field below");
   int spk_map(const qvc::SpkMapArgs& a) { open(17); PUT(a.frames, a.U, a.F, a.P, a.flen, a.poff, a.prow, a.pstart, a.psteps, a.phdr); return close(); }
 };
+
+// The recording backend of qvc_emu_launch_trace: the same walk, but what it writes down of a call is the CHOICE the
+// chooser of its kernel family returns (csrc/qvc_select.h: choose_*, every field of LaunchChoice), behind the few inputs
+// the rules read and the record names of the timed entry point are built from.  The calls that are not one of the six
+// families leave a record without words (tail: its bands), so that the list stays the list of launches.  The chooser is
+// asked, nothing is refused: a choice's status is a word of the record like any other.
+struct SelectBackend : TraceBackend {
+  // the choice, and whether its tuple is one the library instantiates (the family's *_built)
+  int chosen(const qvc::LaunchChoice& c) { const int built = qvc::choice_built(c); PUT(c, built); return close(); }
+  int conv(const qvc::ConvDesc& d, const qvc::ConvArgs& a, int batch, int epi, int dtype) {
+    const int up_s = d.up_s, nchunk = d.nchunk, Nq = a.Nq, mean3 = a.x2 != nullptr;
+    const qvc::LaunchChoice c = qvc::choose_conv(d, a, batch, epi, dtype);
+    open(0); PUT(batch, epi, dtype, up_s, nchunk, Nq, mean3); return chosen(c);
+  }
+  int pair3(const qvc::ConvDesc* d1, const qvc::ConvDesc* d2, const qvc::PairArgs3& a, int batch, int dtype) {
+    const int T = a.p[0].T;
+    const qvc::LaunchChoice c = qvc::choose_pair(d1, d2, a, batch, dtype);
+    open(1); PUT(batch, dtype, a.n, a.chain_major, T); return chosen(c);
+  }
+  int chain(const qvc::ConvDesc* d1, const qvc::ConvDesc* d2, const qvc::ChainArgs& a, int batch, int dtype) {
+    const int T = a.p[0].T, k = d1 ? d1[0].taps : 0;
+    const qvc::LaunchChoice c = d1 ? qvc::choose_chain(d1, d2, a, batch, dtype) : qvc::LaunchChoice();
+    open(2); PUT(batch, dtype, a.n, T, k); return chosen(c);
+  }
+  int wn(const qvc::ConvDesc& din, const qvc::ConvDesc&, const qvc::WnArgs& a, int batch, int dtype) {
+    const int W = din.WM;
+    const qvc::LaunchChoice c = qvc::choose_wn(din, a, batch, dtype);
+    open(3); PUT(batch, dtype, a.T, W); return chosen(c);
+  }
+  int wn_stack(const qvc::ConvDesc& din, const qvc::ConvDesc&, const qvc::ConvDesc&, const qvc::WnStackArgs& a, int batch, int dtype,
+               const qvc::ConvDesc* pre, const qvc::ConvDesc*) {
+    const int W = din.WM, fused = pre != nullptr;
+    const qvc::LaunchChoice c = qvc::choose_wn_stack(din, a, batch, dtype);
+    open(4); PUT(batch, dtype, a.T, a.layers, a.wide, fused, W); return chosen(c);
+  }
+  int gemv(const qvc::GemvArgs&) { open(5); return close(); }
+  int sample(const qvc::SampleArgs&) { open(6); return close(); }
+  int sample_rows(const qvc::SampleRowsArgs&) { open(7); return close(); }
+  int tail(const qvc::TailArgs& a) { open(8); PUT(a.bands); return close(); }
+  int post_tail(const qvc::ConvDesc& d, const qvc::PostTailArgs& a, int batch, int dtype) {
+    const qvc::LaunchChoice c = qvc::choose_post_tail(d, a, batch, dtype);
+    open(9); PUT(batch, dtype, a.F); return chosen(c);
+  }
+  int zero(void*, size_t) { open(10); return close(); }
+  void fork(int) { open(11); close(); }
+  void branch(int) { open(12); close(); }
+  void branch_done(int) { open(13); close(); }
+  void join(int) { open(14); close(); }
+  int lstm(const qvc::LstmArgs&, int, int) { open(15); return close(); }
+  int spk_embed(const qvc::SpkEmbedArgs&) { open(16); return close(); }
+  int spk_map(const qvc::SpkMapArgs&) { open(17); return close(); }
+};
 #undef PUT
 
 // the forms of qvc_emu_path_trace, in the order of its `form` argument
 enum TraceForm { TF_UNIFORM, TF_RAGGED_FM, TF_RAGGED_RNG, TF_FANOUT, TF_FANOUT_RNG, TF_ENC_Q, TF_FLOW_FORWARD, TF_ENC_P, TF_DEC_TRUNK, TF_STREAM_DEC,
                  TF_SPK, TF_SPK_RAGGED, TF_COUNT };
 constexpr int kTraceSwitches = 5;      // pair_chain3, post_tail, wn_chunk (the emulation's three), pair_cm4, pair_wide_launch
-constexpr int kTraceSwitch[kTraceSwitches] = {qvc::DBG_PAIR_CHAIN3, qvc::DBG_POST_TAIL, qvc::DBG_WN_CHUNK, qvc::DBG_PAIR_CM4, qvc::DBG_PAIR_WIDE_LAUNCH};
-
-}  // namespace
-
-extern "C" {
+// ... and, for the launch trace, the three the choosers read (csrc/qvc_select.h)
+constexpr int kSelectSwitches = 8;
+constexpr int kTraceSwitch[kSelectSwitches] = {qvc::DBG_PAIR_CHAIN3, qvc::DBG_POST_TAIL, qvc::DBG_WN_CHUNK, qvc::DBG_PAIR_CM4, qvc::DBG_PAIR_WIDE_LAUNCH,
+                                               qvc::DBG_CONV_CL, qvc::DBG_POST_TAIL_NF, qvc::DBG_WN_KERNEL};
 
 // One form of the path (TraceForm) for (cfg, B rows of T frames; U sources of a fan-out, U utterances of T mel frames of
 // the speaker forms) on the recording backend: rec[0, *used) receives every backend call in order (TraceBackend states the
@@ -331,8 +389,11 @@ extern "C" {
 // the entry points of include/qvc.h ask and never read or written.  switches (null: the defaults) = the values of
 // kTraceSwitch for the call, set in this library's own debug table and put back before it returns.
 // QVC_ERR_SMALL_BUFFER: more than `cap` words; kMoveOutside: a launch named a pointer outside every buffer of the call.
-int qvc_emu_path_trace(const qvc_config* cfg, int32_t form, int32_t B, int32_t T, int32_t U, const int32_t* switches, int64_t* rec, int64_t cap,
-                       int64_t* used) {
+// (the body of qvc_emu_path_trace and qvc_emu_launch_trace: Backend = what a call leaves in the record, n_sw = the first
+//  n_sw switches of kTraceSwitch come with the call)
+template <class Backend>
+int trace_form(const qvc_config* cfg, int32_t form, int32_t B, int32_t T, int32_t U, const int32_t* switches, int n_sw, int64_t* rec, int64_t cap,
+               int64_t* used) {
   using namespace qvc;
   if (!cfg || !rec || !used || form < 0 || form >= TF_COUNT || B <= 0 || T <= 1 || U <= 0) return QVC_ERR_BAD_ARG;
   const bool spk = form == TF_SPK || form == TF_SPK_RAGGED;
@@ -356,7 +417,7 @@ int qvc_emu_path_trace(const qvc_config* cfg, int32_t form, int32_t B, int32_t T
   bytes[TR_MEL] = rows * S.n_mel * T * 4;
   bytes[TR_Z] = rows * std::max<int64_t>(C, Q.spec_channels) * T * 4;
   bytes[TR_STATE] = spk ? 0 : 3 * rows * t0 * P.stages[0].ch * 2;
-  TraceBackend be;
+  Backend be;
   std::array<void*, TR_COUNT> buf = {};
   bool alloc_ok = true;
   for (int i = 0; i < TR_COUNT; ++i) {
@@ -366,8 +427,8 @@ int qvc_emu_path_trace(const qvc_config* cfg, int32_t form, int32_t B, int32_t T
   }
   auto f32 = [&](int r) { return static_cast<float*>(buf[(size_t)r]); };
   auto i32 = [&](int r) { return static_cast<int32_t*>(buf[(size_t)r]); };
-  int32_t saved[kTraceSwitches];
-  for (int i = 0; i < kTraceSwitches; ++i) {
+  int32_t saved[kSelectSwitches];
+  for (int i = 0; i < n_sw; ++i) {
     saved[i] = debug_get(kTraceSwitch[i]);
     if (switches) debug_table()[kTraceSwitch[i]].store(switches[i], std::memory_order_relaxed);
   }
@@ -383,11 +444,11 @@ int qvc_emu_path_trace(const qvc_config* cfg, int32_t form, int32_t B, int32_t T
     NoiseRng rng;
     rng.keys = static_cast<const uint64_t*>(buf[TR_KEYS]); rng.seed_lo = 0x1234567u; rng.seed_hi = 0x89abcdeu; rng.scale = 0.75f;
     auto path = [&] {
-      Path<TraceBackend> c{P, static_cast<const char*>(buf[TR_BLOB]), static_cast<char*>(buf[TR_WORKSPACE]), W, B, T, be};
+      Path<Backend> c{P, static_cast<const char*>(buf[TR_BLOB]), static_cast<char*>(buf[TR_WORKSPACE]), W, B, T, be};
       c.step_n = steps; c.step_kinds = kinds.data(); c.max_step_kinds = (int)kinds.size();
       return c;
     };
-    Path<TraceBackend> c = path();
+    Path<Backend> c = path();
     switch (form) {
       case TF_UNIFORM: c.infer(f32(TR_UNIT), f32(TR_G), f32(TR_NOISE), f32(TR_OUT)); break;
       case TF_RAGGED_FM: c.lens = i32(TR_LENS); c.unit_fm = true; c.infer(f32(TR_UNIT), f32(TR_G), f32(TR_NOISE), f32(TR_OUT)); break;
@@ -407,10 +468,10 @@ int qvc_emu_path_trace(const qvc_config* cfg, int32_t form, int32_t B, int32_t T
         c.lens = i32(TR_LENS); c.pos = i32(TR_POS); c.off = 7; c.wn_wide = false;
         c.dec_front(f32(TR_Z));
         st = c.status; steps = c.step_n;
-        Path<TraceBackend> d = path();
+        Path<Backend> d = path();
         d.lens = i32(TR_LENS); d.pos = i32(TR_POS); d.off = 11; d.wn_wide = false;
         for (int j = 0; j < 3; ++j) d.s0_override[j] = static_cast<char*>(buf[TR_STATE]) + (int64_t)j * rows * t0 * P.stages[0].ch * 2;
-        if (st == QVC_OK) { d.dec_back_wave(d.wsp<float>(d.W.post), f32(TR_OUT)); st = d.status; steps = d.step_n; }
+        if (st == QVC_OK) { d.dec_back_wave(d.template wsp<float>(d.W.post), f32(TR_OUT)); st = d.status; steps = d.step_n; }
         break;
       }
     }
@@ -420,7 +481,7 @@ int qvc_emu_path_trace(const qvc_config* cfg, int32_t form, int32_t B, int32_t T
     for (int i = 0; st == QVC_OK && i < steps; ++i) be.words.push_back(kinds[(size_t)i]);
     be.close();
   }
-  for (int i = 0; i < kTraceSwitches; ++i) debug_table()[kTraceSwitch[i]].store(saved[i], std::memory_order_relaxed);
+  for (int i = 0; i < n_sw; ++i) debug_table()[kTraceSwitch[i]].store(saved[i], std::memory_order_relaxed);
   for (void* p : buf) std::free(p);
   if (st != QVC_OK) return st;
   if (be.outside) return kMoveOutside;
@@ -430,13 +491,14 @@ int qvc_emu_path_trace(const qvc_config* cfg, int32_t form, int32_t B, int32_t T
   return QVC_OK;
 }
 
-// The layout of the records of qvc_emu_path_trace as text, one line per kind: "<kind> <name of word 0> <name of word 1> ..."
+// The layout of the records of a trace as text, one line per kind: "<kind> <name of word 0> <name of word 1> ..."
 // (a pointer is "<field>" "<field>+": region, offset).  Returns the bytes the text needs, the closing 0 included; the text
 // is written when `cap` holds it.
-int64_t qvc_emu_path_trace_layout(char* text, int64_t cap) {
+template <class Backend>
+int64_t trace_layout(char* text, int64_t cap) {
   using namespace qvc;
   std::vector<std::string> names;
-  TraceBackend be;
+  Backend be;
   be.names = &names;
   std::string out;
   auto line = [&](int kind) {
@@ -446,6 +508,7 @@ int64_t qvc_emu_path_trace_layout(char* text, int64_t cap) {
     names.clear();
   };
   ConvDesc d[3];
+  for (ConvDesc& x : d) x.CinP = kKStep;      // (a descriptor the choosers can size a tile for; the layout holds names only)
   int kind = 0;
   be.conv(d[0], ConvArgs(), 0, 0, 0); line(kind++);
   be.pair3(d, d, PairArgs3(), 0, 0); line(kind++);
@@ -470,6 +533,24 @@ int64_t qvc_emu_path_trace_layout(char* text, int64_t cap) {
   if (text && cap >= need) std::memcpy(text, out.c_str(), (size_t)need);
   return need;
 }
+
+}  // namespace
+
+extern "C" {
+
+int qvc_emu_path_trace(const qvc_config* cfg, int32_t form, int32_t B, int32_t T, int32_t U, const int32_t* switches, int64_t* rec, int64_t cap,
+                       int64_t* used) {
+  return trace_form<TraceBackend>(cfg, form, B, T, U, switches, kTraceSwitches, rec, cap, used);
+}
+int64_t qvc_emu_path_trace_layout(char* text, int64_t cap) { return trace_layout<TraceBackend>(text, cap); }
+
+// The same walk on SelectBackend: per launch-family call the choice its chooser returns.  switches: kSelectSwitches values,
+// the five of qvc_emu_path_trace and then conv_cl, post_tail_nf, wn_kernel.
+int qvc_emu_launch_trace(const qvc_config* cfg, int32_t form, int32_t B, int32_t T, int32_t U, const int32_t* switches, int64_t* rec, int64_t cap,
+                         int64_t* used) {
+  return trace_form<SelectBackend>(cfg, form, B, T, U, switches, kSelectSwitches, rec, cap, used);
+}
+int64_t qvc_emu_launch_trace_layout(char* text, int64_t cap) { return trace_layout<SelectBackend>(text, cap); }
 
 // The library's debug switch "live_trim" for the twin: 1 (default) the trimmed form, 0 the plain one.  One switch, two names.
 void qvc_emu_live_trim(int32_t on) { g_trim = on != 0; }
