@@ -449,6 +449,48 @@ int qvc_stream_import_slots(const qvc_config* cfg, void* state, int64_t state_by
                             const int32_t* slots_host, int32_t n_slots, int32_t* pos_dev, int32_t* len_dev,
                             const void* snap_dev, int64_t snap_bytes, void* stream);
 
+/* ---- exact windows over packed utterances: recordings of any length, offline -----------------------------------------
+ * Every whole-path call above sizes its buffers by rows x longest utterance, so one hour-long recording in a batch makes
+ * the batch unallocatable.  Here many WINDOWS ride one call as its rows, cut from utterances of any lengths that lie back
+ * to back in packed buffers and addressed through a table in device memory: memory is bounded by rows x window whatever
+ * the lengths, one long recording converts at batch rate, and every row has its own g row (a target speaker per region).
+ *   unit_fm_packed  [total_frames][unit_channels] fp32: the utterances as they are on disk (dataset/encode.py:38), back to back
+ *   noise_packed    (inter_channels, total_frames) fp32: frame f of an utterance is column base + f.  The _rng twin draws
+ *                   at the absolute frame of every window row instead; keys_dev holds one key per ROW (rows of one
+ *                   utterance carry that utterance's key)
+ *   win_dev         DEVICE qvc_window [rows], never read on the host
+ *   g               (rows, gin_channels)
+ *   out_packed      [total_frames * samples_per_frame] fp32, laid out as the units are
+ * With n = window_frames and C = qvc_live_context_frames(cfg), a row's window is the W = 2C + n frames
+ * [start - C, start + n + C) of its utterance (zeros outside [0, length)); the row delivers frames [start, start + count)
+ * to out_packed[(base + start) * samples_per_frame ...] and NOTHING else of out_packed is written.  The delivered frames
+ * are those of qvc_infer_batch_ragged[_rng] on the whole utterance with the same g and the same noise or (seed, key):
+ * the windowed step at look_ahead = C (qvc_live_step above), where prefix and whole-utterance conversion agree.  A frame
+ * costs (2C + n) / n of its offline cost in enc_p, less in the stages behind it.
+ * The table is clamped on the device: base and length to total_frames, start to [0, length], count to
+ * [0, min(n, length - start)]; no table content makes a launch touch memory outside the caller's buffers.  A row with
+ * count = 0 is idle: an empty sequence, nothing of it is read or delivered.  Rows that deliver overlapping ranges race.
+ * Asynchronous, allocation-free, no host read of any device array: a captured call replays with another table, other
+ * lengths and other packed contents.  Checks, in the order of qvc_live_step's: QVC_ERR_BAD_ARG for a null pointer,
+ * rows < 1 (or > 65535), window_frames < 1, total_frames < 1 or 2C + n > 1 << 24; QVC_ERR_BAD_CONFIG for a bad plan;
+ * QVC_ERR_SMALL_BUFFER for a small workspace; QVC_ERR_BAD_ARG for a workspace or blob that is not 256-byte aligned.  A
+ * refused call launches nothing; the size query returns the code as its value.  csrc/qvc_stream.h (infer_windows). */
+typedef struct qvc_window {   /* one row of a call; DEVICE memory; never read on the host */
+  int32_t base;    /* first frame of the row's utterance in the packed buffers          */
+  int32_t length;  /* that utterance's length in frames                                  */
+  int32_t start;   /* first delivered frame, relative to the utterance                   */
+  int32_t count;   /* delivered frames; 0 = idle row                                      */
+} qvc_window;
+int64_t qvc_windows_workspace_bytes(const qvc_config* cfg, int32_t rows, int32_t window_frames);
+int qvc_infer_windows_fm(const qvc_config* cfg, const void* blob_dev, const float* unit_fm_packed, const float* noise_packed,
+                         const qvc_window* win_dev, const float* g, float* out_packed,
+                         int32_t rows, int32_t window_frames, int32_t total_frames,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+int qvc_infer_windows_rng_fm(const qvc_config* cfg, const void* blob_dev, const float* unit_fm_packed, const qvc_noise_rng* rng,
+                             const qvc_window* win_dev, const float* g, float* out_packed,
+                             int32_t rows, int32_t window_frames, int32_t total_frames,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- optional fork/join resources: lets the three independent ResBlocks of an MRF stage
  * (models.py:378-384) run as parallel branches (two auxiliary non-blocking streams + events), so a
  * memory-bound k=3 launch overlaps a compute-bound k=11 launch.  Created/destroyed by the caller

@@ -11,9 +11,10 @@ library is loaded (and its absence reported loudly) the first time the hot path 
 from .config import HParams, get_hparams_from_file, DEFAULT_MODEL_CONFIG, DEFAULT_DATA_CONFIG, MINI_MODEL_CONFIG, ODD_MODEL_CONFIG, ISTFT_MODEL_CONFIG
 from .model import SynthesizerTrn, SpeakerEncoder
 from .checkpoint import load_checkpoint, save_checkpoint, latest_checkpoint_path
+from .windows import WindowConverter, plan_windows
 
 __all__ = [
     "HParams", "get_hparams_from_file", "DEFAULT_MODEL_CONFIG", "DEFAULT_DATA_CONFIG", "MINI_MODEL_CONFIG", "ISTFT_MODEL_CONFIG",
     "ODD_MODEL_CONFIG", "SynthesizerTrn", "SpeakerEncoder", "load_checkpoint", "save_checkpoint",
-    "latest_checkpoint_path",
+    "latest_checkpoint_path", "WindowConverter", "plan_windows",
 ]

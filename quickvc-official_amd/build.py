@@ -3,7 +3,7 @@
   libqvc_hip.so      -- the product: gfx950 kernels + C ABI + host packer (hipcc --offload-arch=gfx950)
   libqvc_io.so       -- the product's host-side batch file I/O (g++; include/qvc_io.h)
   oracle/_build/libqvc_emu.so -- TEST-ONLY host emulation of the launch sequence (g++/hipcc host code)
-  oracle/_build/libqvc_emu_twin.so -- TEST-ONLY CPU twin of qvc_live_step / qvc_live_tick / qvc_stream_tick on the same emulation (tools/emu_twin.cpp)
+  oracle/_build/libqvc_emu_twin.so -- TEST-ONLY CPU twin of qvc_live_step / qvc_live_tick / qvc_stream_tick / qvc_infer_windows_fm on the same emulation (tools/emu_twin.cpp)
 
 hipcc cross-compiles gfx950 without a GPU.  Translation units compile in parallel.
 """

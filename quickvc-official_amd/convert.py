@@ -9,7 +9,10 @@ launch), ``--seed`` (noise), ``--dtype``, ``--fanout`` (a source listed several 
 speaker, the usual any-to-many list -- is read, uploaded and encoded once: ``qvc_infer_fanout_ragged``), ``--noise``
 (``torch``: one ``torch.randn`` draw per batch, so an utterance's noise depends on how the list was batched and sharded;
 ``native``: the library's counter-based generator keyed by the utterance's position in the list, so its wav is the same
-whatever ``--batch``, ``--fanout``, the number of GPUs, or whether it is converted alone) and ``--noise-scale``.
+whatever ``--batch``, ``--fanout``, the number of GPUs, or whether it is converted alone), ``--noise-scale`` and
+``--max-frames N`` (with ``--noise native``: sources longer than N unit frames -- an audiobook chapter -- stay out of the
+batches, whose buffers are sized by ``batch x longest``, and are converted in exact windows of N frames at bounded
+memory, ``windows.WindowConverter``; the wav is the one the batch would have written).
 
 Corpus scale (BASELINE.json configs[3]): the per-line loop of the reference (convert.py:58-86: load, infer, write, one
 utterance at a time) becomes a three-stage pipeline (``CorpusPipeline``): a loader thread reads the next batches' unit
@@ -372,9 +375,16 @@ def main(argv=None):
                         "native: the library's counter-based generator keyed by the utterance's position in --txtpath "
                         "(blank lines not counted): the same wav however the list is batched, sharded or fanned out")
     p.add_argument("--noise-scale", type=float, default=1.0, help="noise_scale of the prior draw (needs --noise native); 0 = the mean conversion")
+    p.add_argument("--max-frames", type=int, default=0,
+                   help="sources longer than this many unit frames are converted in exact windows of that many frames "
+                        "(windows.WindowConverter) instead of riding a batch, so no buffer is sized by them; needs --noise native; 0 = off")
     args = p.parse_args(argv)
     if args.noise != "native" and args.noise_scale != 1.0:
         p.error("--noise-scale needs --noise native")
+    if args.max_frames < 0:
+        p.error("--max-frames must not be negative")
+    if args.max_frames and args.noise != "native":
+        p.error("--max-frames needs --noise native (a torch draw depends on the batch an utterance rides in)")
 
     os.makedirs(args.outdir, exist_ok=True)
     hps = get_hparams_from_file(args.hpfile)
@@ -398,14 +408,18 @@ def main(argv=None):
     print("Synthesizing...")
     return convert_items(net_g, hps.data, items, args.outdir, rank, world, args.batch, seed, args.use_timestamp, args.io_threads,
                          lanes=args.lanes, fanout=args.fanout != "off", noise=args.noise,
-                         noise_scale=args.noise_scale)                        # the pipeline's stats, for callers in-process
+                         noise_scale=args.noise_scale, max_frames=args.max_frames)   # the pipeline's stats, for callers in-process
 
 
 def convert_items(net_g, d, items, outdir: str, rank: int = 0, world: int = 1, batch: int = 32, seed: int = 0,
                   use_timestamp: bool = False, io_threads: int = 8, timings: dict = None, lanes: int = 2, fanout: bool = True,
-                  noise: str = "torch", noise_scale: float = 1.0):
+                  noise: str = "torch", noise_scale: float = 1.0, max_frames: int = 0, window_rows: int = 32):
     """Convert this rank's shard of ``items`` = [(title, src, tgt)] into ``outdir`` (the body of convert.py:58-86).
-    ``noise="native"``: the key of an utterance is its index in ``items`` -- taken before sharding and length-sorting."""
+    ``noise="native"``: the key of an utterance is its index in ``items`` -- taken before sharding and length-sorting.
+    ``max_frames`` > 0 (needs ``noise="native"``): this rank's sources longer than that stay out of the ragged pipeline --
+    whose buffers are then sized by the longest remaining source -- and are converted afterwards in exact windows of
+    ``max_frames`` frames, ``window_rows`` at a time (windows.WindowConverter), under the same keys and with the same writer;
+    a long source still belongs to one rank."""
     from .fileio import IoPool
     t0 = time.perf_counter()
     with torch.no_grad():
@@ -418,6 +432,13 @@ def convert_items(net_g, d, items, outdir: str, rank: int = 0, world: int = 1, b
             plan_pool.close()
         if not mine:
             return {"utterances": 0, "samples": 0, "batches": 0}
+        long_items = []
+        if max_frames:
+            if noise != "native":
+                raise ValueError("max_frames needs noise='native'")
+            long_items = [i for i in mine if lengths[i] > max_frames]
+            short = [i for i in mine if lengths[i] <= max_frames]
+            batches = [[short[i] for i in idxs] for idxs in plan_batches([lengths[i] for i in short], batch)]
         t1 = time.perf_counter()
         n_targets = [0]
 
@@ -478,7 +499,9 @@ def convert_items(net_g, d, items, outdir: str, rank: int = 0, world: int = 1, b
         def make_pipe():
             try:
                 with torch.cuda.device(dev_index):
-                    box["pipe"] = CorpusPipeline(net_g, min(batch, max(len(b) for b in batches)), max(lengths[i] for i in mine),
+                    if not batches:                                       # every source of this rank is a long one
+                        return
+                    box["pipe"] = CorpusPipeline(net_g, min(batch, max(len(b) for b in batches)), max(lengths[i] for b in batches for i in b),
                                                  d.sampling_rate, io_threads=io_threads, seed=seed, lanes=lanes, fanout=fanout,
                                                  noise=noise, noise_scale=noise_scale)
             except Exception as exc:                                      # noqa: BLE001 -- re-raised below
@@ -491,17 +514,47 @@ def convert_items(net_g, d, items, outdir: str, rank: int = 0, world: int = 1, b
         th.join()
         if "error" in box:
             raise box["error"]
-        pipe = box["pipe"]
-        try:
-            t2 = time.perf_counter()
-            pipe.run(batches, src_paths, out_paths, lengths, g_rows)
-            torch.cuda.synchronize()
-            t3 = time.perf_counter()
-        finally:
-            pipe.close()
+        pipe = box.get("pipe")
+        stats = pipe.stats if pipe is not None else {"utterances": 0, "samples": 0, "batches": 0}
+        t2 = time.perf_counter()
+        if pipe is not None:
+            try:
+                pipe.run(batches, src_paths, out_paths, lengths, g_rows)
+                torch.cuda.synchronize()
+            finally:
+                pipe.close()
+        if long_items:
+            stats["pipeline_max_frames"] = pipe.max_frames if pipe is not None else 0
+            stats["windowed"] = convert_long_items(net_g, long_items, src_paths, out_paths, lengths, g_rows, max_frames, window_rows, seed, noise_scale,
+                                                   d.sampling_rate, io_threads)
+            stats["utterances"] += len(long_items)
+            stats["samples"] += sum(int(lengths[i]) for i in long_items) * net_g.samples_per_frame
+        t3 = time.perf_counter()
     if timings is not None:
         timings.update(plan_s=t1 - t0, setup_and_embed_s=t2 - t1, pipeline_s=t3 - t2, targets=n_targets[0])
-    return pipe.stats
+    return stats
+
+
+def convert_long_items(net_g, idxs, src_paths, out_paths, lengths, g_rows, window_frames: int, rows: int, seed: int, noise_scale: float,
+                       rate: int, io_threads: int = 8) -> int:
+    """The sources ``--max-frames`` keeps out of the ragged pipeline, one at a time through ONE WindowConverter (its
+    buffers grow to the longest of them; its workspace is ``rows`` x window whatever their lengths): the generator's key of
+    an utterance is its item index, as in the pipeline, so the wav does not depend on which of the two paths wrote it.
+    Returns the number of utterances written."""
+    from .fileio import IoPool
+    from .windows import WindowConverter
+    conv = WindowConverter(net_g, rows, window_frames, seed=seed, noise_scale=noise_scale)
+    pool = IoPool(io_threads)
+    try:
+        for i in sorted(idxs, key=lambda i: (-int(lengths[i]), i)):       # longest first: the buffers are sized once
+            u = np.load(src_paths[i]).astype(np.float32, copy=False)
+            if u.ndim != 2 or u.shape[1] != 256 or u.shape[0] != int(lengths[i]):
+                raise ValueError(f"{src_paths[i]}: expected ({int(lengths[i])}, 256), got {u.shape}")
+            wave = conv.convert([torch.from_numpy(u)], g_rows[i:i + 1], keys=[i])[0]
+            pool.write_wavs([out_paths[i]], wave.cpu().reshape(1, -1), [int(wave.numel())], rate)
+    finally:
+        pool.close()
+    return len(idxs)
 
 
 if __name__ == "__main__":

@@ -76,6 +76,9 @@ struct HipBackend {
   int copy_batch(const CopyDesc* d, int n) { return launch_copy_batch(d, n, stream); }
   static constexpr bool kStreamTick = true;       // stream_tick, live_tick: copy_batch's job with the bytes per slot taken from device counts
   int copy_counted(const CountedHead& h, const CountedDesc* d, int n) { return launch_copy_counted(h, d, n, stream); }
+  static constexpr bool kWindows = true;          // infer_windows: the table-driven gather and delivery around the window
+  int window_gather(const WindowArgs& a) { return launch_window_gather(a, stream); }
+  int window_deliver(const WindowArgs& a) { return launch_window_deliver(a, stream); }
 };
 using Ctx = Path<HipBackend>;
 
@@ -349,6 +352,19 @@ int snapshot_api(bool import, const qvc_config* cfg, void* state, int64_t state_
                  int32_t n_slots, int32_t* pos_dev, int32_t* len_dev, void* snap_dev, int64_t snap_bytes, void* stream) {
   HipBackend be(stream);
   const int rc = snapshot_slots(import, be, cfg, state, state_bytes, batch, hop, slots_host, n_slots, pos_dev, len_dev, snap_dev, snap_bytes);
+  return rc != QVC_OK ? rc : be.finish();
+}
+
+// qvc_infer_windows_fm / _rng_fm: infer_windows of qvc_stream.h (the checks, then gather, the window, deliver) on the
+// caller's stream.  Exactly one of noise_packed / rng; a descriptor without keys counts as no draw.
+int windows_api(const qvc_config* cfg, const void* blob_dev, const float* unit_fm_packed, const float* noise_packed, const qvc_noise_rng* rng,
+                const qvc_window* win_dev, const float* g, float* out_packed, int32_t rows, int32_t window_frames, int32_t total_frames,
+                void* workspace, int64_t workspace_bytes, void* stream) {
+  HipBackend be(stream);
+  NoiseRng rv;
+  if (rng) rng_view(rng, rv);
+  const int rc = infer_windows(be, cfg, blob_dev, unit_fm_packed, noise_packed, rng ? &rv : nullptr, win_dev, g, out_packed, rows, window_frames,
+                               total_frames, workspace, workspace_bytes, debug_get(DBG_LIVE_TRIM) != 0);
   return rc != QVC_OK ? rc : be.finish();
 }
 
@@ -696,6 +712,27 @@ int qvc_live_tick_rng(const qvc_config* cfg, const void* blob_dev, void* state, 
 int qvc_live_tick_reset_slot(const qvc_config* cfg, void* state, int64_t state_bytes, int32_t batch, int32_t hop, int32_t look_ahead,
                              int32_t slot, int32_t length, int32_t* pos_dev, int32_t* len_dev, void* stream) {
   return qvc_live_reset_slot(cfg, state, state_bytes, batch, hop, look_ahead, slot, length, pos_dev, len_dev, stream);
+}
+
+int64_t qvc_windows_workspace_bytes(const qvc_config* cfg, int32_t rows, int32_t window_frames) {
+  Plan P; LiveGeom G;
+  const int st = rows > 0 && rows <= 65535 ? window_plan(cfg, window_frames, P, G) : QVC_ERR_BAD_ARG;
+  return st != QVC_OK ? st : carve_window_scratch(P, G, rows).bytes;
+}
+
+int qvc_infer_windows_fm(const qvc_config* cfg, const void* blob_dev, const float* unit_fm_packed, const float* noise_packed,
+                         const qvc_window* win_dev, const float* g, float* out_packed, int32_t rows, int32_t window_frames,
+                         int32_t total_frames, void* workspace, int64_t workspace_bytes, void* stream) {
+  return windows_api(cfg, blob_dev, unit_fm_packed, noise_packed, nullptr, win_dev, g, out_packed, rows, window_frames, total_frames, workspace,
+                     workspace_bytes, stream);
+}
+
+int qvc_infer_windows_rng_fm(const qvc_config* cfg, const void* blob_dev, const float* unit_fm_packed, const qvc_noise_rng* rng,
+                             const qvc_window* win_dev, const float* g, float* out_packed, int32_t rows, int32_t window_frames,
+                             int32_t total_frames, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!rng) return QVC_ERR_BAD_ARG;
+  return windows_api(cfg, blob_dev, unit_fm_packed, nullptr, rng, win_dev, g, out_packed, rows, window_frames, total_frames, workspace,
+                     workspace_bytes, stream);
 }
 
 int qvc_infer_batch_timed(const qvc_config* cfg, const void* blob_dev, const float* unit, const float* g,

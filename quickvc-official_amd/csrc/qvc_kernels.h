@@ -459,6 +459,43 @@ QVC_HD int counted_len(const CountedHead& h, int b, int n) {
   return h.len_cap && end < len ? end : len;
 }
 int launch_copy_counted(const CountedHead& h, const CountedDesc* d, int n, void* stream);
+
+// ---- exact windows over packed utterances (qvc_stream.h: infer_windows): the rows of a call are windows of W = 2C + n
+//      frames cut from utterances that lie back to back in packed buffers, named by a table in device memory (qvc_window,
+//      include/qvc.h).  One definition of the clamp for the two kernels and the host twin: whatever the table holds,
+//      0 <= base <= total, 0 <= length <= total - base, 0 <= start <= length, 0 <= count <= min(n, length - start) -- so
+//      every frame a row reads lies in [base, base + length) and every frame it delivers in [base + start, base + start + count).
+struct WindowRow { int32_t base, length, start, count; };
+QVC_HD WindowRow window_row(const qvc_window* win, int r, int n, int total) {
+  WindowRow w{win[r].base, win[r].length, win[r].start, win[r].count};
+  w.base = w.base < 0 ? 0 : (w.base < total ? w.base : total);
+  const int room = total - w.base;
+  w.length = w.length < 0 ? 0 : (w.length < room ? w.length : room);
+  w.start = w.start < 0 ? 0 : (w.start < w.length ? w.start : w.length);
+  const int most = w.length - w.start < n ? w.length - w.start : n;
+  w.count = w.count < 0 ? 0 : (w.count < most ? w.count : most);
+  return w;
+}
+// The two launches around the path.  Row r's window row i is frame start - C + i of its utterance.
+//   gather   unit_win [rows][W][unit_channels] <- unit_packed [total][unit_channels]; with noise_packed (inter, total):
+//            noise_win (rows, inter, W) <- its columns; window rows outside [0, length) are written as 0.0.  pos_eff /
+//            len_eff: what the path's launches see -- start + C at buffer row W - n and length; an idle row (count 0) gets
+//            W and 0, an empty sequence in every segment as an idle tick slot's, and none of its window is written
+//   deliver  out_packed[(base + start) * spf ...] <- rows [first, first + count) of the row's waveform in
+//            wave (rows, wave_rows * spf)
+struct WindowArgs {
+  const qvc_window* win = nullptr;
+  int32_t rows = 0, n = 0, C = 0, W = 0, total = 0;
+  const float* unit_packed = nullptr; float* unit_win = nullptr; int32_t unit_channels = 0;
+  const float* noise_packed = nullptr; float* noise_win = nullptr; int32_t inter = 0;
+  int32_t* pos_eff = nullptr; int32_t* len_eff = nullptr;
+  const float* wave = nullptr; int32_t wave_rows = 0, first = 0, spf = 0; float* out_packed = nullptr;
+};
+// the most total_frames a call takes: start + C and every frame index stay inside int32
+constexpr int32_t kWindowMaxTotal = INT32_MAX - (1 << 25);
+int launch_window_gather(const WindowArgs& a, void* stream);
+int launch_window_deliver(const WindowArgs& a, void* stream);
+
 int launch_sample(const SampleArgs& a, void* stream);
 int launch_sample_rows(const SampleRowsArgs& a, void* stream);
 // (rows, channels, frames) fp32 in the reference's layout, frames [frame0, frame0 + frames): the tensor the draw sites would compute

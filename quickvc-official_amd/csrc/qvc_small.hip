@@ -10,6 +10,9 @@
 //                          (models.py:394-406, pqmf.py:106-117) -- no complex tensors, no
 //                          zero-stuffed intermediate, each post-conv frame read once (+halo).
 //   * fm_to_cm_kernel    : frame-major -> (B,C,T) for the unit-test conv entry point.
+//   * copy_batch_kernel / copy_counted_kernel : the batched strided copies of the streaming drivers (qvc_stream.h)
+//   * window_gather_kernel / window_deliver_kernel : the table-driven movers around the exact windows over packed
+//                          utterances (qvc_stream.h: infer_windows)
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <type_traits>
@@ -555,6 +558,120 @@ int launch_copy_counted(const CountedHead& h, const CountedDesc* d, int n, void*
   if (a.n == 0) return h.pos_eff || h.pos_add ? QVC_ERR_BAD_ARG : QVC_OK;     // bookkeeping rides on a copy: none to ride on
   a.first[a.n] = (uint32_t)wgs;
   hipLaunchKernelGGL(copy_counted_kernel, dim3((unsigned)wgs), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
+}
+
+// ------------------------------------------------------------------ windows over packed utterances (qvc_stream.h: infer_windows)
+// Pure byte movers around the path, driven by the table in device memory: a workgroup serves one 1024-element chunk of
+// ONE row (blockIdx.y), so the row's clamped table entry (window_row) is uniform in it and an idle row's early return is
+// not divergent.  V = float4 where the channel count / samples per frame and the caller's pointers allow it, else float.
+// Every address is formed from the clamped entry: reads stay in [base, base + length) <= total frames of the packed
+// buffers, the delivery in [base + start, base + start + count), everything else in the workspace's own rows.
+constexpr int kWinPerThread = 4;
+constexpr unsigned kWinChunk = 256u * kWinPerThread;
+
+template <typename V>
+__global__ __launch_bounds__(256) void window_gather_kernel(const WindowArgs a, unsigned unit_chunks) {
+  constexpr int VE = (int)(sizeof(V) / 4);
+  const int r = blockIdx.y;
+  const WindowRow w = window_row(a.win, r, a.n, a.total);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    a.pos_eff[r] = w.count > 0 ? w.start + a.C : a.W;
+    a.len_eff[r] = w.count > 0 ? w.length : 0;
+  }
+  if (w.count == 0) return;
+  const int f0 = w.start - a.C;                          // the frame of window row 0
+  if (blockIdx.x < unit_chunks) {
+    // ---- units: [total][Cu] -> [W][Cu], whole frames, coalesced along the channels on both sides
+    const unsigned cv = (unsigned)a.unit_channels / VE;
+    const size_t total = (size_t)a.W * cv;
+    const float* src = a.unit_packed + (size_t)w.base * a.unit_channels;
+    float* dst = a.unit_win + (size_t)r * a.W * a.unit_channels;
+    V v[kWinPerThread];
+    size_t at[kWinPerThread];
+#pragma unroll
+    for (int k = 0; k < kWinPerThread; ++k) {
+      const size_t e = (size_t)blockIdx.x * kWinChunk + (unsigned)k * 256u + threadIdx.x;
+      const size_t row = e / cv;
+      const unsigned c = (unsigned)(e - row * cv) * VE;
+      const int f = f0 + (int)row;
+      at[k] = e < total ? row * a.unit_channels + c : ~(size_t)0;
+      v[k] = V{};
+      if (e < total && f >= 0 && f < w.length) v[k] = *reinterpret_cast<const V*>(src + (size_t)f * a.unit_channels + c);
+    }
+#pragma unroll
+    for (int k = 0; k < kWinPerThread; ++k)
+      if (at[k] != ~(size_t)0) *reinterpret_cast<V*>(dst + at[k]) = v[k];
+    return;
+  }
+  // ---- noise (pointer form): (inter, total) -> (inter, W), coalesced along the frames on both sides
+  const size_t total = (size_t)a.inter * a.W;
+  float* dst = a.noise_win + (size_t)r * total;
+  float v[kWinPerThread];
+  size_t at[kWinPerThread];
+#pragma unroll
+  for (int k = 0; k < kWinPerThread; ++k) {
+    const size_t e = (size_t)(blockIdx.x - unit_chunks) * kWinChunk + (unsigned)k * 256u + threadIdx.x;
+    const size_t c = e / (unsigned)a.W;
+    const int f = f0 + (int)(e - c * (unsigned)a.W);
+    at[k] = e < total ? e : ~(size_t)0;
+    v[k] = 0.f;
+    if (e < total && f >= 0 && f < w.length) v[k] = a.noise_packed[c * (size_t)a.total + (size_t)w.base + (size_t)f];
+  }
+#pragma unroll
+  for (int k = 0; k < kWinPerThread; ++k)
+    if (at[k] != ~(size_t)0) dst[at[k]] = v[k];
+}
+
+template <typename V>
+__global__ __launch_bounds__(256) void window_deliver_kernel(const WindowArgs a) {
+  constexpr int VE = (int)(sizeof(V) / 4);
+  const int r = blockIdx.y;
+  const WindowRow w = window_row(a.win, r, a.n, a.total);
+  const size_t total = (size_t)w.count * ((unsigned)a.spf / VE);      // elements of the row's delivered frames: one run
+  if ((size_t)blockIdx.x * kWinChunk >= total) return;
+  const float* src = a.wave + ((size_t)r * a.wave_rows + a.first) * a.spf;
+  float* dst = a.out_packed + ((size_t)w.base + (size_t)w.start) * a.spf;
+  V v[kWinPerThread];
+#pragma unroll
+  for (int k = 0; k < kWinPerThread; ++k) {
+    const size_t e = (size_t)blockIdx.x * kWinChunk + (unsigned)k * 256u + threadIdx.x;
+    v[k] = V{};
+    if (e < total) v[k] = *reinterpret_cast<const V*>(src + e * VE);
+  }
+#pragma unroll
+  for (int k = 0; k < kWinPerThread; ++k) {
+    const size_t e = (size_t)blockIdx.x * kWinChunk + (unsigned)k * 256u + threadIdx.x;
+    if (e < total) *reinterpret_cast<V*>(dst + e * VE) = v[k];
+  }
+}
+
+// what both launches check of the geometry: the grid's y is the row, first + n rows of the waveform exist
+static bool window_args_ok(const WindowArgs& a) {
+  return a.win && a.rows >= 1 && a.rows <= 65535 && a.n >= 1 && a.C >= 0 && a.W == 2 * a.C + a.n && a.total >= 1 && a.total <= kWindowMaxTotal;
+}
+
+int launch_window_gather(const WindowArgs& a, void* stream) {
+  if (!window_args_ok(a) || !a.unit_packed || !a.unit_win || a.unit_channels < 1 || !a.pos_eff || !a.len_eff) return QVC_ERR_BAD_ARG;
+  if (a.noise_packed && (!a.noise_win || a.inter < 1)) return QVC_ERR_BAD_ARG;
+  const bool wide = a.unit_channels % 4 == 0 && !((reinterpret_cast<uintptr_t>(a.unit_packed) | reinterpret_cast<uintptr_t>(a.unit_win)) & 15u);
+  const uint64_t unit_chunks = ((uint64_t)a.W * (a.unit_channels / (wide ? 4 : 1)) + kWinChunk - 1) / kWinChunk;
+  const uint64_t noise_chunks = a.noise_packed ? ((uint64_t)a.W * a.inter + kWinChunk - 1) / kWinChunk : 0;
+  if (unit_chunks + noise_chunks >= (1ull << 31)) return QVC_ERR_BAD_ARG;
+  const dim3 grid((unsigned)(unit_chunks + noise_chunks), (unsigned)a.rows);
+  if (wide) hipLaunchKernelGGL(window_gather_kernel<float4>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a, (unsigned)unit_chunks);
+  else hipLaunchKernelGGL(window_gather_kernel<float>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a, (unsigned)unit_chunks);
+  return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
+}
+
+int launch_window_deliver(const WindowArgs& a, void* stream) {
+  if (!window_args_ok(a) || !a.wave || !a.out_packed || a.spf < 1 || a.first < 0 || a.wave_rows < a.first + a.n) return QVC_ERR_BAD_ARG;
+  const bool wide = a.spf % 4 == 0 && !((reinterpret_cast<uintptr_t>(a.wave) | reinterpret_cast<uintptr_t>(a.out_packed)) & 15u);
+  const uint64_t chunks = ((uint64_t)a.n * (a.spf / (wide ? 4 : 1)) + kWinChunk - 1) / kWinChunk;
+  if (chunks >= (1ull << 31)) return QVC_ERR_BAD_ARG;
+  const dim3 grid((unsigned)chunks, (unsigned)a.rows);
+  if (wide) hipLaunchKernelGGL(window_deliver_kernel<float4>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  else hipLaunchKernelGGL(window_deliver_kernel<float>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
   return hipGetLastError() == hipSuccess ? QVC_OK : QVC_ERR_LAUNCH;
 }
 

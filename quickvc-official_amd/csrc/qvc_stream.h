@@ -41,6 +41,8 @@
 //                   flush   what was queued since the last flush runs as ONE launch;  ok / st: the first error
 //   Segments      the factory of a step's Path segments.
 //   stream_checks the pure-host checks of an entry point (the C ABI's scaffold in qvc_api.hip and the CPU twin call it).
+// A third driver, at the end of the file, is offline: infer_windows runs live_window over windows cut from packed
+// utterances of any lengths, named by a table in device memory (no state, no rings: one gather and one deliver launch).
 #pragma once
 #include "qvc_path.h"
 
@@ -724,10 +726,12 @@ inline LiveScratch carve_live_scratch(const Plan& P, const LiveGeom& G, int B, b
 // the plain form or the three trimmed segments.  `unit` / `noise`: the rings (noise == nullptr: the generator form, rng).
 // pos / lens: buffer row T - hop of a segment over the window's last T rows is absolute frame pos[b].  The window's
 // waveform ends up in X.wave: wave_rows rows per stream, the hop delivered ones from row `first` on.
+// unit_fm: the window's unit frames are [B][W][unit_channels] (infer_windows gathers them as they are on disk) instead of
+// the rings' (B, unit_channels, W).
 template <class Backend>
 int live_window(const Plan& P, const LiveGeom& G, const LiveScratch& X, const char* blob, char* ws, const float* unit, const float* g,
                 const float* noise, int B, const int32_t* pos, const int32_t* lens, Backend& be, const NoiseRng* rng, bool trim,
-                size_t& wave_rows, size_t& first) {
+                size_t& wave_rows, size_t& first, bool unit_fm = false) {
   const qvc_config& c = P.cfg;
   const size_t W = (size_t)G.W;
   CopyQueue<Backend> q(be, B, G.hop);        // one strided copy per hand-off, each a launch of its own
@@ -737,6 +741,7 @@ int live_window(const Plan& P, const LiveGeom& G, const LiveScratch& X, const ch
   if (!trim) {
     Path<Backend> p = seg.make(G.W);
     if (!noise && rng) p.rng = *rng;         // (neither: enc_p refuses)
+    p.unit_fm = unit_fm;
     p.infer(unit, g, noise, wave);
     q.ok(p.status);
   } else {
@@ -745,6 +750,7 @@ int live_window(const Plan& P, const LiveGeom& G, const LiveScratch& X, const ch
     {   // E: the conditioning table (every segment's workspace keeps it at the same place) and enc_p
       Path<Backend> p = seg.make(G.W);
       if (!noise && rng) p.rng = *rng;
+      p.unit_fm = unit_fm;
       p.cond_table(g);
       p.enc_p(unit, noise, p.template wsp<float>(p.W.z));
       q.ok(p.status);
@@ -847,6 +853,99 @@ int live_tick(const Plan& P, const LiveGeom& G, const char* blob, char* state, c
   if constexpr (stream_tick_backend<Backend>) {
     CountedQueue<Backend> q(be, n_new, B, G.hop);
     return live_run(q, P, G, blob, state, ws, unit_new, g, noise_new, out, B, pos, lens, rng, trim);
+  } else {
+    return QVC_ERR_BAD_CONFIG;
+  }
+}
+
+// ---------------------------------------------------------------- exact windows over packed utterances (infer_windows)
+// The offline form of the window.  Every other whole-path call sizes its buffers by rows x longest utterance; here the
+// rows of a call are WINDOWS, cut from utterances of any lengths that lie back to back in packed buffers and named by a
+// table in device memory (qvc_window: base, length, start, count), so the memory is rows x window whatever the lengths,
+// one long recording runs at batch rate, and every row has its own g row.  With n = window_frames it is live_window at
+// hop = n and L = C, over the W = 2C + n frames [start - C, start + n + C) of the row's utterance:
+//
+//     row:   0 ............. C ........... C+n ............ W = 2C+n
+//            |  left context  |  delivered  |  right context  |
+//     frame: start-C        start        start+n          start+n+C        pos = start + C sits at buffer row W - n
+//
+// Property P2 of the window (L = C: the conversion of the prefix that ends with the window and the whole-utterance
+// conversion agree on the delivered rows, for every decoder validate() accepts) makes the delivered frames those of the
+// whole-utterance conversion; the sequence's own two ends inside a window are exact through pos / lens as everywhere, and
+// the generator draws at the absolute frame of every row.  Four steps: the plan -- live_plan(cfg, n, C) --, ONE gather
+// launch (units, the noise in the pointer form, the rows' pos / len), live_window as it is (trimmed, or plain), ONE
+// deliver launch.  The decoder still runs over the C rows of right context: trimming them on the right as the trimmed
+// form trims on the left is the obvious follow-up and not done here.
+// Per delivered frame a row costs (2C + n) / n of the offline cost in enc_p, (2C + n - He) / n in the flow and
+// (Hdec + C + n) / n in the decoder (trimmed form).
+// Backend adds:  static constexpr bool kWindows = true  with  int window_gather(const WindowArgs&)  and
+//                int window_deliver(const WindowArgs&)  (qvc_kernels.h) -- one that does not say so gets QVC_ERR_BAD_CONFIG.
+template <class B, class = void> constexpr bool windows_backend = false;
+template <class B> constexpr bool windows_backend<B, std::void_t<decltype(B::kWindows)>> = B::kWindows;
+
+// The plan and the window for (cfg, n): live_plan(cfg, n, C), C read off the first geometry instead of a second plan.
+inline int window_plan(const qvc_config* cfg, int n, Plan& P, LiveGeom& G) {
+  const int st = live_plan(cfg, n, 0, P, G);
+  if (st != QVC_OK) return st;
+  const int C = G.C();
+  if ((int64_t)2 * C + n > (1 << 24)) return G.status = QVC_ERR_BAD_ARG;
+  G.L = C; G.W = 2 * C + n;
+  return QVC_OK;
+}
+
+struct WindowScratch {   // the window's own scratch (a tick's: pos_eff / len_eff are the rows' pos / len), then the gathered windows
+  LiveScratch X;
+  int64_t unit = 0;         // fp32 [B][W][unit_channels]
+  int64_t noise = 0;        // fp32 (B, inter_channels, W): the pointer form only (carved always: the size query has no form)
+  int64_t bytes = 0;
+};
+
+inline WindowScratch carve_window_scratch(const Plan& P, const LiveGeom& G, int B) {
+  WindowScratch S;
+  S.X = carve_live_scratch(P, G, B, true);
+  Carver cv{S.X.bytes};
+  S.unit = cv.take((int64_t)B * G.W * P.cfg.unit_channels * 4);
+  S.noise = cv.take((int64_t)B * P.cfg.inter_channels * G.W * 4);
+  S.bytes = cv.off;
+  return S;
+}
+
+// What qvc_infer_windows_fm / _rng_fm (and the CPU twin's) do on backend `be`: the checks in the order the status codes are
+// pinned to -- pointers, counts and the draw; the plan; the workspace size (stream_checks, no state); the alignments --
+// and then the four steps.  Exactly one of noise_packed / rng.  A refused call launches nothing.
+template <class Backend>
+int infer_windows(Backend& be, const qvc_config* cfg, const void* blob_, const float* unit_packed, const float* noise_packed, const NoiseRng* rng,
+                  const qvc_window* win, const float* g, float* out_packed, int rows, int n, int total, void* ws_, int64_t ws_bytes, bool trim) {
+  Plan P; LiveGeom G;
+  const bool draw = rng ? (!noise_packed && rng->keys) : noise_packed != nullptr;
+  const bool args_ok = blob_ && unit_packed && draw && win && g && out_packed && ws_ && rows <= 65535 && n >= 1 && total >= 1 && total <= kWindowMaxTotal;
+  const int st = stream_checks(args_ok, rows, 0, ws_bytes, [&](StreamBytes& b) {
+    const int gs = window_plan(cfg, n, P, G);
+    if (gs != QVC_OK) return gs;
+    if (!windows_backend<Backend>) return (int)QVC_ERR_BAD_CONFIG;
+    b = {0, carve_window_scratch(P, G, rows).bytes};
+    return gs;
+  });
+  if (st != QVC_OK) return st;
+  if ((reinterpret_cast<uintptr_t>(ws_) & 255) || (reinterpret_cast<uintptr_t>(blob_) & 255)) return QVC_ERR_BAD_ARG;
+  if constexpr (windows_backend<Backend>) {
+    const char* blob = static_cast<const char*>(blob_);
+    char* ws = static_cast<char*>(ws_);
+    const WindowScratch S = carve_window_scratch(P, G, rows);
+    WindowArgs a;
+    a.win = win; a.rows = rows; a.n = n; a.C = G.C(); a.W = G.W; a.total = total;
+    a.unit_packed = unit_packed; a.unit_win = reinterpret_cast<float*>(ws + S.unit); a.unit_channels = P.cfg.unit_channels;
+    a.noise_packed = noise_packed; a.noise_win = reinterpret_cast<float*>(ws + S.noise); a.inter = P.cfg.inter_channels;
+    a.pos_eff = reinterpret_cast<int32_t*>(ws + S.X.pos_eff); a.len_eff = reinterpret_cast<int32_t*>(ws + S.X.len_eff);
+    a.out_packed = out_packed; a.spf = samples_per_frame(P);
+    int rc = be.window_gather(a);
+    if (rc != QVC_OK) return rc;
+    size_t wave_rows = 0, first = 0;
+    rc = live_window(P, G, S.X, blob, ws, a.unit_win, g, noise_packed ? a.noise_win : nullptr, rows, a.pos_eff, a.len_eff, be, rng, trim, wave_rows,
+                     first, /*unit_fm=*/true);
+    if (rc != QVC_OK) return rc;
+    a.wave = reinterpret_cast<const float*>(ws + S.X.wave); a.wave_rows = (int32_t)wave_rows; a.first = (int32_t)first;
+    return be.window_deliver(a);
   } else {
     return QVC_ERR_BAD_CONFIG;
   }

@@ -411,6 +411,36 @@ class QvcEngine:
         """qvc_live_tick_reset_slot: zero slot `slot`'s ring rows, pos[slot] = 0, lens[slot] = length (on the current stream)."""
         self._stream_reset_slot("live_tick", state, batch, (hop, int(look_ahead)), slot, length, pos, lens)
 
+    # ---- exact windows over packed utterances (qvc_infer_windows_*): recordings of any length at bounded memory
+    def windows_sizes(self, rows: int, window_frames: int):
+        """(workspace_bytes, context_frames) for calls of `rows` windows that deliver `window_frames` frames each."""
+        return self._stream_sizes("windows", ("windows_workspace_bytes", "live_context_frames"), rows, window_frames)
+
+    @_on_device
+    def infer_windows(self, ws: torch.Tensor, unit_packed: torch.Tensor, noise_packed: Optional[torch.Tensor], table: torch.Tensor,
+                      g: torch.Tensor, out_packed: torch.Tensor, window_frames: int, rng=None) -> None:
+        """One call of `rows` windows (all tensors contiguous on this device; see include/qvc.h): ``unit_packed``
+        (total_frames, unit_channels) fp32, ``noise_packed`` (inter, total_frames) fp32 or None with ``rng = (seed, keys,
+        scale)`` (keys: an int64 tensor of one key per ROW on this device), ``table`` (rows, 4) int32 -- base, length,
+        start, count per row --, ``g`` (rows, gin), ``out_packed`` (total_frames * samples_per_frame,) fp32: row r writes
+        its ``count`` frames from frame base + start on and nothing else."""
+        mc = self.model_config
+        rows, total = int(table.shape[0]), int(unit_packed.shape[0])
+        if table.dtype != torch.int32 or tuple(table.shape) != (rows, 4) or unit_packed.dim() != 2 or unit_packed.shape[1] != mc.get("unit_channels", 256) \
+                or tuple(g.shape) != (rows, mc["gin_channels"]) or out_packed.numel() != total * self.samples_per_frame:
+            raise ValueError(f"bad input shapes: table {tuple(table.shape)}, unit_packed {tuple(unit_packed.shape)}, g {tuple(g.shape)}, "
+                             f"out_packed {tuple(out_packed.shape)}")
+        for t in (table, unit_packed, g, out_packed) + (() if noise_packed is None else (noise_packed,)):
+            if t.device.type != "cuda" or not t.is_contiguous() or (t is not table and t.dtype != torch.float32):
+                raise ValueError("infer_windows needs contiguous fp32 / int32 tensors on the engine's device")
+        if rng is not None and not (torch.is_tensor(rng[1]) and rng[1].device == self.device):
+            raise ValueError("infer_windows needs the rng keys as an int64 tensor on the engine's device")
+        noise_packed, desc, _ = self._draw(noise_packed, rng, rows, (mc["inter_channels"], total))
+        fn, draw = (self.lib.qvc_infer_windows_fm, noise_packed.data_ptr()) if desc is None else (self.lib.qvc_infer_windows_rng_fm, ctypes.byref(desc))
+        st = fn(ctypes.byref(self.cfg), self.blob.data_ptr(), unit_packed.data_ptr(), draw, table.data_ptr(), g.data_ptr(), out_packed.data_ptr(),
+                rows, int(window_frames), total, ws.data_ptr(), ws.numel(), torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib, st, "qvc_infer_windows_fm")
+
     def _pack_spk(self) -> None:
         if self._spk_blob is None:
             if not self._spk_sd:

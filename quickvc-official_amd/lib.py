@@ -212,6 +212,16 @@ def declare(lib: ctypes.CDLL, prefix: str = "qvc") -> None:
             fn = getattr(lib, prefix + name)
             fn.restype = ctypes.c_int
             fn.argtypes = [cfgp, V, L, I, I, P(I), I, V, V, V, L, V]
+    # exact windows over packed utterances (qvc_infer_windows_fm / _rng_fm): (cfg, blob, unit_fm_packed, noise_packed | rng,
+    # win_dev, g, out_packed, rows, window_frames, total_frames, workspace, workspace_bytes, stream)
+    if hasattr(lib, prefix + "_windows_workspace_bytes"):
+        fn = getattr(lib, prefix + "_windows_workspace_bytes")
+        fn.restype = L
+        fn.argtypes = [cfgp, I, I]
+        for name, draw in (("_infer_windows_fm", V), ("_infer_windows_rng_fm", P(QvcNoiseRng))):
+            fn = getattr(lib, prefix + name)
+            fn.restype = ctypes.c_int
+            fn.argtypes = [cfgp, V, V, draw, V, V, V, I, I, I, V, L, V]
     for name in ("_stream_lag_frames", "_stream_noise_lag_frames", "_live_context_frames"):
         if hasattr(lib, prefix + name):
             fn = getattr(lib, prefix + name)

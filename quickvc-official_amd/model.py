@@ -294,6 +294,26 @@ class SynthesizerTrn(nn.Module):
         return self.infer_batch(unit, g, noise)
 
     @torch.no_grad()
+    def infer_long(self, unit: Tensor, g_or_mel: Tensor, window_frames: int = 1024, rows: int = 32, noise: Optional[Tensor] = None,
+                   seed: Optional[int] = None, key: int = 0, noise_scale: float = 1.0) -> Tensor:
+        """``infer`` for ONE recording of any length at bounded memory: unit (1,256,F), ``g_or_mel`` the speaker embedding
+        (1,gin) / (1,gin,1) or the target's mel (1,80,F') -> (1,1,320*F) fp32, equal to ``infer`` on the whole recording.
+        The recording is cut into windows of ``window_frames`` delivered frames that run ``rows`` at a time
+        (windows.WindowConverter); the converter is kept for the next call of the same geometry.
+        ``noise`` (1, inter, F) / ``seed``, ``key``, ``noise_scale``: as ``infer_batch``."""
+        from .windows import WindowConverter
+        if noise is not None and seed is not None:
+            raise ValueError("pass noise or seed, not both")
+        mel = g_or_mel.dim() == 3 and g_or_mel.shape[-1] > 1                      # (1, n_mel, F'), not (1, gin, 1)
+        g = self.speaker_embed(g_or_mel) if mel else g_or_mel.reshape(1, -1)
+        at = (self._weights_version(), int(rows), int(window_frames), seed, float(noise_scale))
+        if getattr(self, "_long", None) is None or self._long[0] != at:
+            self._long = (at, WindowConverter(self, rows, window_frames, seed=seed, noise_scale=noise_scale))
+        frames = unit.reshape(-1, unit.shape[-1]).t().contiguous()                # (F, 256): as on disk
+        out = self._long[1].convert([frames], g, keys=[key], noise=None if noise is None else [noise.reshape(noise.shape[-2], -1)])
+        return out[0].reshape(1, 1, -1)
+
+    @torch.no_grad()
     def posterior(self, spec: Tensor, g: Tensor, noise: Optional[Tensor] = None):
         """The analysis half of ``forward`` (models.py:617-618): z ~ enc_q(spec | g), z_p = flow(z, g).
 

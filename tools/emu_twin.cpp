@@ -11,6 +11,8 @@
 // or stream_tick, descriptor by descriptor (qvc_emu_stream_moves; tests/test_stream_moves_host.py).  The slot snapshots
 // (snapshot_slots: qvc_emu_stream_export_slots / _import_slots) run on the same host copy_batch.  The emulation's
 // backend has no single-band tail and no generator form of the noise: band-synthesis decoders, pointer form only.
+// WindowsEmuBackend derives from CountingBackend, states kWindows and restates the two table-driven kernels of the exact
+// windows over packed utterances (qvc_emu_infer_windows_fm; tests/test_windows_host.py).
 // TraceBackend stands alone: it computes nothing and writes down every backend call of a Path, field by field
 // (qvc_emu_path_trace; tests/test_path_trace_host.py) -- every decoder and every form, since nothing is run.
 // SelectBackend walks the same calls and writes down, per launch, the choice its family's chooser returns
@@ -66,6 +68,45 @@ int64_t g_counted[2] = {0, 0};      // calls of copy_counted, descriptors in the
 struct CountingBackend : TickEmuBackend {
   int copy_batch(const qvc::CopyDesc* d, int n) { ++g_counts[0]; g_counts[1] += n; return TickEmuBackend::copy_batch(d, n); }
   int copy_counted(const qvc::CountedHead& h, const qvc::CountedDesc* d, int n) { ++g_counted[0]; g_counted[1] += n; return TickEmuBackend::copy_counted(h, d, n); }
+};
+
+// The backend of qvc_emu_infer_windows_fm: states kWindows and restates the two table-driven kernels of
+// csrc/qvc_small.hip (window_gather_kernel, window_deliver_kernel) in plain C++, row by row on the same clamp (window_row).
+struct WindowsEmuBackend : CountingBackend {
+  static constexpr bool kWindows = true;
+  int window_gather(const qvc::WindowArgs& a) {
+    if (!a.win || !a.unit_packed || !a.unit_win || !a.pos_eff || !a.len_eff || (a.noise_packed && !a.noise_win)) return QVC_ERR_BAD_ARG;
+    for (int r = 0; r < a.rows; ++r) {
+      const qvc::WindowRow w = qvc::window_row(a.win, r, a.n, a.total);
+      a.pos_eff[r] = w.count > 0 ? w.start + a.C : a.W;
+      a.len_eff[r] = w.count > 0 ? w.length : 0;
+      if (w.count == 0) continue;
+      const size_t Cu = (size_t)a.unit_channels, W = (size_t)a.W;
+      for (size_t i = 0; i < W; ++i) {
+        const int f = w.start - a.C + (int)i;
+        float* dst = a.unit_win + ((size_t)r * W + i) * Cu;
+        if (f >= 0 && f < w.length) std::memcpy(dst, a.unit_packed + ((size_t)w.base + (size_t)f) * Cu, Cu * 4);
+        else std::fill(dst, dst + Cu, 0.f);
+      }
+      if (!a.noise_packed) continue;
+      for (size_t c = 0; c < (size_t)a.inter; ++c)
+        for (size_t i = 0; i < W; ++i) {
+          const int f = w.start - a.C + (int)i;
+          a.noise_win[((size_t)r * a.inter + c) * W + i] = f >= 0 && f < w.length ? a.noise_packed[c * (size_t)a.total + (size_t)w.base + (size_t)f] : 0.f;
+        }
+    }
+    return QVC_OK;
+  }
+  int window_deliver(const qvc::WindowArgs& a) {
+    if (!a.win || !a.wave || !a.out_packed || a.wave_rows < a.first + a.n) return QVC_ERR_BAD_ARG;
+    for (int r = 0; r < a.rows; ++r) {
+      const qvc::WindowRow w = qvc::window_row(a.win, r, a.n, a.total);
+      if (w.count > 0)
+        std::memcpy(a.out_packed + ((size_t)w.base + (size_t)w.start) * a.spf, a.wave + ((size_t)r * a.wave_rows + a.first) * a.spf,
+                    (size_t)w.count * a.spf * 4);
+    }
+    return QVC_OK;
+  }
 };
 
 bool g_trim = true;
@@ -570,6 +611,36 @@ int qvc_emu_live_tick(const qvc_config* cfg, const void* blob, void* state, int6
                       const int32_t* n_new, int32_t* pos, const int32_t* lens, void* workspace, int64_t workspace_bytes) {
   return live_call(cfg, blob, state, state_bytes, unit_new, g, noise_new, out, batch, hop, look_ahead, true, n_new, pos, lens,
                    workspace, workspace_bytes);
+}
+
+// Same signature as qvc_infer_windows_fm, host pointers (the table too), no stream: infer_windows (csrc/qvc_stream.h) on
+// WindowsEmuBackend, trimmed or plain by qvc_emu_live_trim.  The pointer form only: the emulation has no generator.
+int qvc_emu_infer_windows_fm(const qvc_config* cfg, const void* blob, const float* unit_fm_packed, const float* noise_packed,
+                             const qvc_window* win, const float* g, float* out_packed, int32_t rows, int32_t window_frames,
+                             int32_t total_frames, void* workspace, int64_t workspace_bytes) {
+  WindowsEmuBackend be;
+  return qvc::infer_windows(be, cfg, blob, unit_fm_packed, noise_packed, nullptr, win, g, out_packed, rows, window_frames, total_frames, workspace,
+                            workspace_bytes, g_trim);
+}
+
+// ... and what a backend without kWindows gets from the same driver (the frozen one): nothing is touched.
+int qvc_emu_infer_windows_frozen(const qvc_config* cfg, int32_t rows, int32_t window_frames) {
+  EmuBackend be;
+  char* a = reinterpret_cast<char*>(uintptr_t(1) << 20);     // any aligned non-null address: never followed
+  return qvc::infer_windows(be, cfg, a, reinterpret_cast<const float*>(a), reinterpret_cast<const float*>(a), nullptr,
+                            reinterpret_cast<const qvc_window*>(a), reinterpret_cast<const float*>(a), reinterpret_cast<float*>(a), rows,
+                            window_frames, 1, a, INT64_MAX, true);
+}
+
+// Same signature as qvc_infer_batch_ragged_fm, host pointers, no stream: the frozen emulation's whole path over units as
+// they are on disk ([B][max_frames][unit_channels]) -- what a window's delivered frames are compared with.
+int qvc_emu_infer_batch_ragged_fm(const qvc_config* cfg, const void* blob, const float* unit_fm, const float* g, const float* noise,
+                                  float* out, int32_t batch, int32_t max_frames, const int32_t* frames_host, void* workspace,
+                                  int64_t workspace_bytes) {
+  if (!cfg || !blob || !unit_fm || !g || !noise || !out || !frames_host || !workspace || batch <= 0 || max_frames <= 1) return QVC_ERR_BAD_ARG;
+  return std::min(0, run_path(cfg, blob, batch, max_frames, workspace, workspace_bytes, Window(), [&](qvc::Path<EmuBackend>& c) {
+    c.lens = frames_host; c.unit_fm = true; c.infer(unit_fm, g, noise, out);
+  }));
 }
 
 // Same signature as qvc_live_reset_slot / qvc_live_tick_reset_slot, host pointers, no stream.
