@@ -643,6 +643,33 @@ int qvc_trim_bounds(const float* wave, const int32_t* samples_dev, int32_t* star
                     int32_t utterances, int32_t max_samples, float top_db, int32_t frame_length, int32_t hop_length,
                     void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- sample formats either side of the float path: wav payloads in, 16-bit PCM out ----------
+ * qvc_pcm_to_wave_ragged is frontend.load_wav's int -> float conversion and channel mean for a batch
+ * of RAW wav payloads (what qvc_io_load_wavs of qvc_io.h puts into byte slots), in front of
+ * qvc_trim_bounds: slot u of pcm (utterances slots of slot_bytes bytes each; pcm 16-byte aligned and
+ * slot_bytes a multiple of 16, else QVC_ERR_BAD_ARG) holds interleaved little-endian frames in the
+ * format rows_dev[u] names.  rows_dev is a DEVICE array and is never read on the host:
+ *   code      1 u8, 2 s16, 3 s24 (packed), 4 s32, 5 f32   (QVC_PCM_* of qvc_io.h)
+ *   channels  1 or 2
+ *   frames    frames in the slot
+ * Row u of wave (utterances, max_samples) fp32 receives n = clamp(frames, 0, min(max_samples,
+ * slot_bytes / (bytes per sample * channels))) samples, samples [n, max_samples) are written as 0.0f
+ * and samples_dev[u] = n; a row with another code or channel count gets n = 0.  Arithmetic, bit for
+ * bit load_wav's: s16 (float)v / 32768, s24 (float)v / 8388608, s32 (float)v / 2147483648 (the
+ * conversion rounds to nearest even), u8 ((float)v - 128) / 128, f32 the bits as they are; two
+ * channels: (a + b) * 0.5f of the converted values.  One streaming launch sized by max_samples: the
+ * payload is read once, the floats are written once, no workspace.  utterances <= 65535.
+ *
+ * qvc_wave_to_pcm16 is the 16-bit writer's conversion, element-wise over n floats:
+ *   q = clamp(rint(x * 32768), -32768, 32767), halves to even, NaN -> 0
+ * (numpy: np.clip(np.rint(x * np.float32(32768)), -32768, 32767).astype(np.int16)).  The scale is a
+ * power of two, so nothing rounds twice, and it inverts the s16 reader above: a signal that came from
+ * a 16-bit file survives write -> read unchanged. */
+typedef struct { int32_t code, channels, frames; } qvc_pcm_row;
+int qvc_pcm_to_wave_ragged(const void* pcm, int64_t slot_bytes, const qvc_pcm_row* rows_dev,
+                           float* wave, int32_t* samples_dev, int32_t utterances, int32_t max_samples, void* stream);
+int qvc_wave_to_pcm16(const float* wave, int16_t* pcm, int64_t n, void* stream);
+
 /* ---- posterior direction: enc_q and the forward flow (models.py:617-618) -------
  * z ~ enc_q(spec | g) = CondNormalWN with speaker conditioning (models.py:75-95,582), then
  * z_p = flow(z, g) = ResidualCouplingBlock.forward(reverse=False) (models.py:39-51; x1 <- m + x1,

@@ -25,8 +25,8 @@ enum {
   QVC_IO_OK = 0,
   QVC_IO_ERR_BAD_ARG = -1,
   QVC_IO_ERR_OPEN = -2,      /* a file could not be opened / created              */
-  QVC_IO_ERR_FORMAT = -3,    /* not a little-endian float32 C-ordered 2-D .npy    */
-  QVC_IO_ERR_SHAPE = -4,     /* wrong column count, or more frames than the slot  */
+  QVC_IO_ERR_FORMAT = -3,    /* not a little-endian float32 C-ordered 2-D .npy / not a wav the header reader accepts */
+  QVC_IO_ERR_SHAPE = -4,     /* wrong column count, or more frames than the slot / a wav payload larger than its slot */
   QVC_IO_ERR_IO = -5         /* short read / write                                 */
 };
 
@@ -54,6 +54,33 @@ int qvc_io_load_units(qvc_io_pool* pool, const char* const* paths, int32_t n, fl
  * scipy.io.wavfile.write(paths[i], rate, that float32 array) writes (convert.py:84-86). */
 int qvc_io_write_wavs(qvc_io_pool* pool, const char* const* paths, int32_t n, const float* src, int64_t stride,
                       const int32_t* samples, int32_t rate);
+
+/* ---- target recordings: wav headers and raw payloads (the float conversion is the device's: qvc.h, qvc_pcm_to_wave_ragged)
+ * A header as the reader below understands it.  `code` is the sample format (the qvc_pcm_row code of qvc.h), `bits` the
+ * container width, `frames` the number of WHOLE frames present -- min(declared data size, bytes left in the file) /
+ * block_align, what scipy.io.wavfile.read returns for a truncated file --, `data_offset` the payload's first byte. */
+typedef struct { int32_t rate, channels, code, bits; int64_t frames, data_offset; } qvc_wav_header;
+enum { QVC_PCM_U8 = 1, QVC_PCM_S16 = 2, QVC_PCM_S24 = 3, QVC_PCM_S32 = 4, QVC_PCM_F32 = 5 };   /* `code` */
+
+/* Headers of n wav files, on the pool.  Accepted: little-endian RIFF / WAVE; chunks are walked (unknown ones skipped, the
+ * pad byte after an odd-sized chunk honoured) up to the data chunk; `fmt ` with format tag 1 (integer PCM), 3 (IEEE float)
+ * or 0xFFFE (extensible: the tag is the first two bytes of the sub-format); u8, s16, s24, s32 or f32 samples; any channel
+ * count >= 1.  Everything else -- RIFX, f64, ADPCM and other tags, other bit depths, no `fmt ` in front of `data`, no
+ * `data`, a block_align that is not channels * bits / 8, a file too short to say -- is QVC_IO_ERR_FORMAT for THAT file:
+ * status[i] (may be null) receives file i's own status, out[i] is written only where it is QVC_IO_OK, and the call returns
+ * the first non-OK status in file order (QVC_IO_OK when there is none).  Whatever bytes a file holds, nothing throws. */
+int qvc_io_wav_headers(qvc_io_pool* pool, const char* const* paths, int32_t n, qvc_wav_header* out, int32_t* status);
+
+/* Raw payloads of n wav files into byte slots: file i's frames_i * block_align payload bytes land at dst + i * slot_bytes
+ * exactly as they are on disk (no conversion); the rest of the slot is left untouched.  out (may be null) and status (may
+ * be null) as above; a payload larger than slot_bytes is QVC_IO_ERR_SHAPE, a short read QVC_IO_ERR_IO. */
+int qvc_io_load_wavs(qvc_io_pool* pool, const char* const* paths, int32_t n, uint8_t* dst, int64_t slot_bytes,
+                     qvc_wav_header* out, int32_t* status);
+
+/* qvc_io_write_wavs for 16-bit output: file i holds samples[i] int16 values from src + i * stride -- byte for byte what
+ * scipy.io.wavfile.write(paths[i], rate, that int16 array) writes (the format of the reference's downsample.py). */
+int qvc_io_write_wavs_pcm16(qvc_io_pool* pool, const char* const* paths, int32_t n, const int16_t* src, int64_t stride,
+                            const int32_t* samples, int32_t rate);
 
 #ifdef __cplusplus
 }

@@ -27,7 +27,7 @@ EMU_TWIN_LIB = os.path.join(EMU_DIR, "libqvc_emu_twin.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-SOURCES = ["qvc_conv_f16.hip", "qvc_conv_bf16.hip", "qvc_wn2.hip", "qvc_chain.hip", "qvc_small.hip", "qvc_spk.hip", "qvc_mel.hip", "qvc_api.hip", "qvc_pack.cpp"]
+SOURCES = ["qvc_conv_f16.hip", "qvc_conv_bf16.hip", "qvc_wn2.hip", "qvc_chain.hip", "qvc_small.hip", "qvc_spk.hip", "qvc_mel.hip", "qvc_pcm.hip", "qvc_api.hip", "qvc_pack.cpp"]
 # translation units whose gfx950 assembly is kept next to the resource remarks (tests/test_pair_kloop_waits.py reads the
 # wait counts of the pair kernels' K loops from it)
 ASM_SOURCES = ["qvc_conv_f16.hip", "qvc_conv_bf16.hip"]
@@ -90,7 +90,7 @@ def build_hip(force: bool = False, verbose: bool = False, variant: str = "") -> 
 
 
 def build_io(force: bool = False) -> str:
-    """libqvc_io.so: host-side batch file I/O (unit .npy in, float32 wav out) -- plain C++, no GPU code."""
+    """libqvc_io.so: host-side batch file I/O (unit .npy and target wav payloads in, float32 / 16-bit wav out) -- plain C++, no GPU code."""
     src = os.path.join(CSRC, "qvc_io.cpp")
     hdr = os.path.join(ROOT, "include", "qvc_io.h")
     if force or not _newer(IO_LIB, [src, hdr]):

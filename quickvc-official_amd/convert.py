@@ -12,7 +12,11 @@ speaker, the usual any-to-many list -- is read, uploaded and encoded once: ``qvc
 whatever ``--batch``, ``--fanout``, the number of GPUs, or whether it is converted alone), ``--noise-scale`` and
 ``--max-frames N`` (with ``--noise native``: sources longer than N unit frames -- an audiobook chapter -- stay out of the
 batches, whose buffers are sized by ``batch x longest``, and are converted in exact windows of N frames at bounded
-memory, ``windows.WindowConverter``; the wav is the one the batch would have written).
+memory, ``windows.WindowConverter``; the wav is the one the batch would have written), ``--target-io`` (``auto``: the
+target recordings' headers and raw payloads are read by the native I/O pool and decoded on the device,
+``SynthesizerTrn.speaker_embed_files``; ``scipy``: one ``load_wav`` per target on the host, the earlier route -- the
+embeddings are bit-equal either way) and ``--pcm16`` (16-bit PCM output files, the format of the reference's data
+preparation, downsample.py, instead of float32: half the bytes downloaded and written).
 
 Corpus scale (BASELINE.json configs[3]): the per-line loop of the reference (convert.py:58-86: load, infer, write, one
 utterance at a time) becomes a three-stage pipeline (``CorpusPipeline``): a loader thread reads the next batches' unit
@@ -41,7 +45,7 @@ import torch
 from .checkpoint import load_checkpoint
 from .dist import env_world, shard_indices
 from .config import get_hparams_from_file
-from .frontend import MelFrontend, load_wav
+from .frontend import MelFrontend, load_wav, wave_to_pcm16
 from .model import SynthesizerTrn
 
 
@@ -175,9 +179,11 @@ class CorpusPipeline:
     """
 
     def __init__(self, net_g, batch: int, max_frames: int, sampling_rate: int, slots: int = 4, io_threads: int = 8,
-                 seed: int = 0, lanes: int = 2, fanout: bool = True, noise: str = "torch", noise_scale: float = 1.0):
+                 seed: int = 0, lanes: int = 2, fanout: bool = True, noise: str = "torch", noise_scale: float = 1.0, pcm16: bool = False):
         """``noise``: "torch" -- one ``batch_noise`` tensor per batch; "native" -- no noise tensor at all: the draw is
-        computed on the device from (seed, the utterance's item index, channel, frame), scaled by ``noise_scale``."""
+        computed on the device from (seed, the utterance's item index, channel, frame), scaled by ``noise_scale``.
+        ``pcm16``: 16-bit output files -- the floats are quantised on the lane's stream after the conversion
+        (``frontend.wave_to_pcm16``), the download and the pinned output buffers hold int16."""
         from .fileio import IoPool
         if noise not in ("torch", "native"):
             raise ValueError(f"noise must be 'torch' or 'native', got {noise!r}")
@@ -185,6 +191,8 @@ class CorpusPipeline:
             raise ValueError("noise_scale needs noise='native'")
         self.noise, self.noise_scale = noise, float(noise_scale)
         self.fanout = bool(fanout)
+        self.pcm16 = bool(pcm16)
+        out_dtype = torch.int16 if self.pcm16 else torch.float32
         self.net_g, self.engine = net_g, net_g.engine()
         self.dev = self.engine.device
         self.batch, self.max_frames, self.rate, self.seed = int(batch), int(max_frames), int(sampling_rate), int(seed)
@@ -200,7 +208,7 @@ class CorpusPipeline:
                 unit_pin=torch.empty(B * Tm * self.uc, dtype=torch.float32).pin_memory(),
                 lens_pin=torch.empty(B, dtype=torch.int32).pin_memory(),
                 src_pin=torch.empty(B, dtype=torch.int32).pin_memory(),
-                out_pin=torch.empty(B * Tm * self.spf, dtype=torch.float32).pin_memory(),
+                out_pin=torch.empty(B * Tm * self.spf, dtype=out_dtype).pin_memory(),
                 unit_dev=torch.empty(B * Tm * self.uc, dtype=torch.float32, device=self.dev),
                 lens_dev=torch.empty(B, dtype=torch.int32, device=self.dev),
                 src_dev=torch.empty(B, dtype=torch.int32, device=self.dev),
@@ -208,6 +216,8 @@ class CorpusPipeline:
                 done=torch.cuda.Event()))
         for s in self.slots:
             s["up"], s["comp"] = torch.cuda.Event(), torch.cuda.Event()
+            if self.pcm16:
+                s["out16_dev"] = torch.empty(B * Tm * self.spf, dtype=torch.int16, device=self.dev)
         self.ws = [self.engine.alloc_workspace(B, Tm, sources=1) for _ in range(self.lanes)]   # serves both entry points
         # uploads, kernels and downloads on streams of their own: batch k+1 travels to the GPU and batch k-1 back to
         # the host while batch k computes (one stream would serialise 1 GB of PCIe traffic with the kernels)
@@ -270,7 +280,8 @@ class CorpusPipeline:
                     s["done"].synchronize()
                     t0w = time.perf_counter()
                     out = s["out_pin"][:n * tmax * self.spf].view(n, tmax * self.spf)
-                    self.write_pool.write_wavs([out_paths[i] for i in idxs], out, [int(lengths[i]) * self.spf for i in idxs], self.rate)
+                    write = self.write_pool.write_wavs_pcm16 if self.pcm16 else self.write_pool.write_wavs
+                    write([out_paths[i] for i in idxs], out, [int(lengths[i]) * self.spf for i in idxs], self.rate)
                     free_q.put(s)
                     t1w = time.perf_counter()
                     self.stats["write_wait_s"] += tg - tw
@@ -333,6 +344,8 @@ class CorpusPipeline:
                             self.engine.infer_fanout_ragged(unit, lens, src, g, noise, out=out, ws=self.ws[lane], unit_fm=True, rng=rng)
                         else:
                             self.engine.infer_batch_ragged(unit, g, noise, lens, out=out, ws=self.ws[lane], unit_fm=True, rng=rng)
+                        if self.pcm16:                        # quantise where the floats are: the download carries int16
+                            out = wave_to_pcm16(out.view(-1), out=s["out16_dev"][:n * tmax * self.spf])
                         s["comp"].record(stream)
                         # the caching allocator hands noise / g back to THIS stream's pool once they go out of scope
                     bi += 1
@@ -378,6 +391,11 @@ def main(argv=None):
     p.add_argument("--max-frames", type=int, default=0,
                    help="sources longer than this many unit frames are converted in exact windows of that many frames "
                         "(windows.WindowConverter) instead of riding a batch, so no buffer is sized by them; needs --noise native; 0 = off")
+    p.add_argument("--target-io", default="auto", choices=["auto", "scipy"],
+                   help="auto: target wavs are read by the native I/O pool and decoded on the GPU (files that need resampling, f64 "
+                        "and more than two channels still go through scipy); scipy: every target through scipy on the host. "
+                        "The embeddings are bit-equal either way")
+    p.add_argument("--pcm16", default=False, action="store_true", help="write 16-bit PCM wav files instead of float32")
     args = p.parse_args(argv)
     if args.noise != "native" and args.noise_scale != 1.0:
         p.error("--noise-scale needs --noise native")
@@ -408,19 +426,26 @@ def main(argv=None):
     print("Synthesizing...")
     return convert_items(net_g, hps.data, items, args.outdir, rank, world, args.batch, seed, args.use_timestamp, args.io_threads,
                          lanes=args.lanes, fanout=args.fanout != "off", noise=args.noise,
-                         noise_scale=args.noise_scale, max_frames=args.max_frames)   # the pipeline's stats, for callers in-process
+                         noise_scale=args.noise_scale, max_frames=args.max_frames, target_io=args.target_io,
+                         pcm16=args.pcm16)                                           # the pipeline's stats, for callers in-process
 
 
 def convert_items(net_g, d, items, outdir: str, rank: int = 0, world: int = 1, batch: int = 32, seed: int = 0,
                   use_timestamp: bool = False, io_threads: int = 8, timings: dict = None, lanes: int = 2, fanout: bool = True,
-                  noise: str = "torch", noise_scale: float = 1.0, max_frames: int = 0, window_rows: int = 32):
+                  noise: str = "torch", noise_scale: float = 1.0, max_frames: int = 0, window_rows: int = 32,
+                  target_io: str = "auto", pcm16: bool = False):
     """Convert this rank's shard of ``items`` = [(title, src, tgt)] into ``outdir`` (the body of convert.py:58-86).
     ``noise="native"``: the key of an utterance is its index in ``items`` -- taken before sharding and length-sorting.
     ``max_frames`` > 0 (needs ``noise="native"``): this rank's sources longer than that stay out of the ragged pipeline --
     whose buffers are then sized by the longest remaining source -- and are converted afterwards in exact windows of
     ``max_frames`` frames, ``window_rows`` at a time (windows.WindowConverter), under the same keys and with the same writer;
-    a long source still belongs to one rank."""
-    from .fileio import IoPool
+    a long source still belongs to one rank.
+    ``target_io``: "auto" -- the targets are staged by the native I/O pool and decoded on the device
+    (SynthesizerTrn.stage_target_files / speaker_embed_staged); "scipy" -- one load_wav per target, the earlier route.
+    ``pcm16``: 16-bit PCM output files instead of float32, on both paths."""
+    from .fileio import PCM_BYTES, IoPool
+    if target_io not in ("auto", "scipy"):
+        raise ValueError(f"target_io must be 'auto' or 'scipy', got {target_io!r}")
     t0 = time.perf_counter()
     with torch.no_grad():
         # Shard FIRST: the split only needs every source's length, read from the .npy headers; units are loaded
@@ -456,31 +481,69 @@ def convert_items(net_g, d, items, outdir: str, rank: int = 0, world: int = 1, b
             # lengths): the speaker encoder is latency-bound, a batch costs about what one target costs.  Sorted by
             # sample count (wav headers only) so that a chunk pads little; the next chunk's files are read on a helper
             # thread while this one is embedded.
-            counts = [wav_samples(t, d.sampling_rate) for t in tgts]
+            table = torch.empty(len(tgts), net_g.model_config["gin_channels"], device="cuda")
+            if target_io == "scipy":
+                counts = [wav_samples(t, d.sampling_rate) for t in tgts]
+            else:
+                # every header in one call on the pool; a file the device decodes has its frame count there, the others
+                # (another rate, f64, more than two channels, refused by the reader) keep the scipy count
+                tpool = IoPool(io_threads)
+                hdr, hst = tpool.wav_headers(tgts)
+                native = [hst[r] == 0 and hdr[r].rate == d.sampling_rate and hdr[r].channels in (1, 2) for r in range(len(tgts))]
+                counts = [int(hdr[r].frames) if native[r] else wav_samples(tgts[r], d.sampling_rate) for r in range(len(tgts))]
+                nbytes = [counts[r] * (PCM_BYTES[hdr[r].code] * hdr[r].channels if native[r] else 4) for r in range(len(tgts))]
             order = sorted(range(len(tgts)), key=lambda r: (counts[r], r))
             chunks = target_chunks([counts[r] for r in order])
-            table = torch.empty(len(tgts), net_g.model_config["gin_channels"], device="cuda")
             loaded = queue.Queue(maxsize=1)
+            free_bufs, stop = queue.Queue(), []
 
             def reader():
                 try:
+                    if target_io != "scipy":
+                        # two pinned byte buffers of the largest chunk's size (slots of 16-byte multiples + the row table):
+                        # one fills while the other embeds
+                        cap = max((hi - lo) * (-(-max(max(nbytes[r] for r in order[lo:hi]), 1) // 16) * 16 + 12) for lo, hi in chunks)
+                        for _ in range(2):
+                            free_bufs.put(torch.empty(cap, dtype=torch.uint8).pin_memory())
                     for lo, hi in chunks:
-                        loaded.put([load_wav(tgts[r], d.sampling_rate) for r in order[lo:hi]])
+                        if stop:
+                            return
+                        if target_io == "scipy":
+                            loaded.put([load_wav(tgts[r], d.sampling_rate) for r in order[lo:hi]])
+                        else:
+                            rows = order[lo:hi]
+                            loaded.put(net_g.stage_target_files([tgts[r] for r in rows], d.sampling_rate, tpool,
+                                                                headers=([hdr[r] for r in rows], [hst[r] for r in rows]), buf=free_bufs.get()))
                 except Exception as exc:                                  # noqa: BLE001 -- re-raised by the consumer
                     loaded.put(exc)
 
             rt = threading.Thread(target=reader, daemon=True)
             rt.start()
-            for lo, hi in chunks:
-                waves = loaded.get()
-                if isinstance(waves, Exception):
-                    raise waves
-                try:
-                    g = net_g.speaker_embed_waves(waves, front, trim_top_db=20)
-                except ValueError as exc:
-                    raise ValueError(f"{exc} (targets {[tgts[r] for r in order[lo:hi]]})") from exc
-                table[torch.as_tensor(order[lo:hi], device=table.device)] = g
-            rt.join()
+            try:
+                for lo, hi in chunks:
+                    waves = loaded.get()
+                    if isinstance(waves, Exception):
+                        raise waves
+                    try:
+                        if target_io == "scipy":
+                            g = net_g.speaker_embed_waves(waves, front, trim_top_db=20)
+                        else:
+                            g = net_g.speaker_embed_staged(waves, front, trim_top_db=20)
+                            free_bufs.put(waves["buf"])                   # uploaded: the read-back at the end of the call has passed
+                    except ValueError as exc:
+                        raise ValueError(f"{exc} (targets {[tgts[r] for r in order[lo:hi]]})") from exc
+                    table[torch.as_tensor(order[lo:hi], device=table.device)] = g
+                rt.join()
+            finally:
+                if target_io != "scipy":
+                    stop.append(True)                                     # after an error: the reader ends at its next chunk,
+                    free_bufs.put(None)                                   # whether it waits for a buffer
+                    while rt.is_alive():                                  # or for room in the queue
+                        try:
+                            loaded.get(timeout=0.05)
+                        except queue.Empty:
+                            pass
+                    tpool.close()
             rows = tgts
             g_rows = torch.zeros(len(items), table.shape[1], device=table.device)
             g_rows[torch.as_tensor(mine, device=table.device)] = table[torch.as_tensor([tgt_row[items[i][2]] for i in mine], device=table.device)]
@@ -503,7 +566,7 @@ def convert_items(net_g, d, items, outdir: str, rank: int = 0, world: int = 1, b
                         return
                     box["pipe"] = CorpusPipeline(net_g, min(batch, max(len(b) for b in batches)), max(lengths[i] for b in batches for i in b),
                                                  d.sampling_rate, io_threads=io_threads, seed=seed, lanes=lanes, fanout=fanout,
-                                                 noise=noise, noise_scale=noise_scale)
+                                                 noise=noise, noise_scale=noise_scale, pcm16=pcm16)
             except Exception as exc:                                      # noqa: BLE001 -- re-raised below
                 box["error"] = exc
 
@@ -526,7 +589,7 @@ def convert_items(net_g, d, items, outdir: str, rank: int = 0, world: int = 1, b
         if long_items:
             stats["pipeline_max_frames"] = pipe.max_frames if pipe is not None else 0
             stats["windowed"] = convert_long_items(net_g, long_items, src_paths, out_paths, lengths, g_rows, max_frames, window_rows, seed, noise_scale,
-                                                   d.sampling_rate, io_threads)
+                                                   d.sampling_rate, io_threads, pcm16=pcm16)
             stats["utterances"] += len(long_items)
             stats["samples"] += sum(int(lengths[i]) for i in long_items) * net_g.samples_per_frame
         t3 = time.perf_counter()
@@ -536,7 +599,7 @@ def convert_items(net_g, d, items, outdir: str, rank: int = 0, world: int = 1, b
 
 
 def convert_long_items(net_g, idxs, src_paths, out_paths, lengths, g_rows, window_frames: int, rows: int, seed: int, noise_scale: float,
-                       rate: int, io_threads: int = 8) -> int:
+                       rate: int, io_threads: int = 8, pcm16: bool = False) -> int:
     """The sources ``--max-frames`` keeps out of the ragged pipeline, one at a time through ONE WindowConverter (its
     buffers grow to the longest of them; its workspace is ``rows`` x window whatever their lengths): the generator's key of
     an utterance is its item index, as in the pipeline, so the wav does not depend on which of the two paths wrote it.
@@ -551,7 +614,10 @@ def convert_long_items(net_g, idxs, src_paths, out_paths, lengths, g_rows, windo
             if u.ndim != 2 or u.shape[1] != 256 or u.shape[0] != int(lengths[i]):
                 raise ValueError(f"{src_paths[i]}: expected ({int(lengths[i])}, 256), got {u.shape}")
             wave = conv.convert([torch.from_numpy(u)], g_rows[i:i + 1], keys=[i])[0]
-            pool.write_wavs([out_paths[i]], wave.cpu().reshape(1, -1), [int(wave.numel())], rate)
+            if pcm16:
+                pool.write_wavs_pcm16([out_paths[i]], wave_to_pcm16(wave).cpu().reshape(1, -1), [int(wave.numel())], rate)
+            else:
+                pool.write_wavs([out_paths[i]], wave.cpu().reshape(1, -1), [int(wave.numel())], rate)
     finally:
         pool.close()
     return len(idxs)

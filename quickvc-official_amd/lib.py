@@ -222,6 +222,14 @@ def declare(lib: ctypes.CDLL, prefix: str = "qvc") -> None:
             fn = getattr(lib, prefix + name)
             fn.restype = ctypes.c_int
             fn.argtypes = [cfgp, V, V, draw, V, V, V, I, I, I, V, L, V]
+    # sample formats either side of the float path: raw wav payloads -> the padded fp32 batch, fp32 -> 16-bit PCM
+    if hasattr(lib, prefix + "_pcm_to_wave_ragged"):
+        fn = getattr(lib, prefix + "_pcm_to_wave_ragged")
+        fn.restype = ctypes.c_int
+        fn.argtypes = [V, L, V, V, V, I, I, V]
+        fn = getattr(lib, prefix + "_wave_to_pcm16")
+        fn.restype = ctypes.c_int
+        fn.argtypes = [V, V, L, V]
     for name in ("_stream_lag_frames", "_stream_noise_lag_frames", "_live_context_frames"):
         if hasattr(lib, prefix + name):
             fn = getattr(lib, prefix + name)

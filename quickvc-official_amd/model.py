@@ -346,7 +346,6 @@ class SynthesizerTrn(nn.Module):
         ``speaker_embed(front(trim(w)))`` of that recording alone.  The frame counts are read back once at the end: a
         recording too short for one mel frame raises ``ValueError`` (as it does alone)."""
         import numpy as np
-        from .frontend import trim_bounds
         eng = self.engine()
         rows = [torch.as_tensor(np.asarray(w, dtype=np.float32) if not torch.is_tensor(w) else w).reshape(-1) for w in waves]
         if not rows:
@@ -359,15 +358,95 @@ class SynthesizerTrn(nn.Module):
             host[u, :lens[u]] = r.to(device="cpu", dtype=torch.float32)
         wave = host.to(eng.device, non_blocking=True)
         samples = torch.tensor(lens, dtype=torch.int32).pin_memory().to(eng.device, non_blocking=True)
+        g, empty = self._embed_wave_batch(wave, samples, front, trim_top_db)
+        if empty:
+            raise ValueError(f"waveforms {empty} are too short for one mel frame after trimming")
+        return g
+
+    def _embed_wave_batch(self, wave: Tensor, samples: Tensor, front, trim_top_db: Optional[float]):
+        """The device side of ``speaker_embed_waves`` and ``speaker_embed_files``: wave (U, max_samples) fp32 and samples
+        (U,) int32, both on the device -> (g (U, gin), the rows without a mel frame).  Trim, mel and the speaker encoder
+        run back to back on the device lengths; the frame counts are the one read-back, after everything is enqueued."""
+        from .frontend import trim_bounds
         start = None
         if trim_top_db is not None:
             start, samples = trim_bounds(wave, samples, top_db=trim_top_db)
         mel, frames = front.ragged(wave, samples, start)
-        g = eng.speaker_embed_ragged(mel, frames)
-        empty = [u for u, f in enumerate(frames.tolist()) if f <= 0]          # the one read-back, after everything is enqueued
+        g = self.engine().speaker_embed_ragged(mel, frames)
+        return g, [u for u, f in enumerate(frames.tolist()) if f <= 0]
+
+    def stage_target_files(self, paths, sr: int, pool, headers=None, buf: Optional[Tensor] = None) -> dict:
+        """The host half of ``speaker_embed_files``: the recordings ``paths`` as ONE pinned byte buffer -- U slots of raw
+        payload and the (code, channels, frames) row table behind them -- ready for one upload.  ``pool`` is a
+        ``fileio.IoPool``; ``headers`` = ``pool.wav_headers(paths)`` when the caller has read them already; ``buf`` a
+        pinned uint8 tensor to fill when it is large enough (a caller that stages the next batch while this one embeds
+        keeps two).  Needs no GPU: a helper thread may run it.
+
+        A file takes the native route -- its payload read by the pool straight into its slot, as it is on disk -- when
+        the header reader accepted it, its rate is ``sr`` and it has one or two channels.  Every other file (another rate,
+        f64, more channels, anything the reader refused) goes through ``frontend.load_wav`` as before, so a broken file
+        raises what it raised before, and its floats are stored in its slot as an f32 mono row."""
+        import numpy as np
+        from .fileio import PCM_BYTES, PCM_F32, QVC_IO_OK
+        from .frontend import load_wav
+        paths = list(paths)
+        if not paths:
+            raise ValueError("no waveform given")
+        hdr, st = pool.wav_headers(paths) if headers is None else headers
+        native = [u for u in range(len(paths)) if st[u] == QVC_IO_OK and hdr[u].rate == int(sr) and hdr[u].channels in (1, 2)]
+        is_native = set(native)
+        hosted = [u for u in range(len(paths)) if u not in is_native]
+        host_waves = [np.ascontiguousarray(load_wav(paths[u], int(sr)), dtype=np.float32).reshape(-1) for u in hosted]
+        order = native + hosted                                               # row r of the batch is file order[r]: one pool call fills rows 0 .. len(native)-1
+        rows = [(hdr[u].code, hdr[u].channels, int(hdr[u].frames)) for u in native] + [(PCM_F32, 1, int(w.size)) for w in host_waves]
+        if max(r[2] for r in rows) >= 1 << 31:
+            raise ValueError("a recording of 2^31 samples or more does not fit a row")
+        need = max(max(PCM_BYTES[c] * ch * n for c, ch, n in rows), 1)
+        slot_bytes = -(-need // 16) * 16
+        U = len(rows)
+        total = U * slot_bytes + U * 12
+        if buf is None or buf.numel() < total:
+            buf = torch.empty(total, dtype=torch.uint8).pin_memory()
+        if native:
+            got, st2 = pool.load_wavs([paths[u] for u in native], buf, slot_bytes)
+            for r, u in enumerate(native):
+                if st2[r] != QVC_IO_OK or (got[r].code, got[r].channels, int(got[r].frames)) != rows[r]:
+                    raise ValueError(f"{paths[u]}: changed since its header was read (status {st2[r]})")
+        for r, w in enumerate(host_waves, start=len(native)):
+            buf[r * slot_bytes:r * slot_bytes + 4 * w.size] = torch.from_numpy(w).view(torch.uint8)
+        buf[U * slot_bytes:total].view(torch.int32).view(U, 3).copy_(torch.tensor(rows, dtype=torch.int32))
+        return dict(buf=buf, total=total, slot_bytes=slot_bytes, rows=U, order=order, counts=[r[2] for r in rows],
+                    max_samples=max(max(r[2] for r in rows), 1))
+
+    @torch.no_grad()
+    def speaker_embed_staged(self, staged: dict, front, trim_top_db: Optional[float] = 20.0) -> Tensor:
+        """The device half of ``speaker_embed_files`` for what ``stage_target_files`` prepared: one upload (payload bytes
+        and row table), one decode launch (``frontend.pcm_to_wave``), then what ``speaker_embed_waves`` runs."""
+        from .frontend import pcm_to_wave
+        eng = self.engine()
+        U, order, counts = staged["rows"], staged["order"], staged["counts"]
+        if max(counts) <= (front.n_fft - front.hop) // 2:                     # host-known (header counts): not even the longest row has a frame
+            raise ValueError(f"waveforms {list(range(U))} are too short for one mel frame")
+        dev = staged["buf"][:staged["total"]].to(eng.device, non_blocking=True)
+        nb = U * staged["slot_bytes"]
+        rows_dev = dev[nb:].view(torch.int32).view(U, 3)
+        wave, samples = pcm_to_wave(dev[:nb], staged["slot_bytes"], rows_dev, staged["max_samples"])
+        g_rows, empty = self._embed_wave_batch(wave, samples, front, trim_top_db)
         if empty:
-            raise ValueError(f"waveforms {empty} are too short for one mel frame after trimming")
+            raise ValueError(f"waveforms {sorted(order[r] for r in empty)} are too short for one mel frame after trimming")
+        g = torch.empty_like(g_rows)
+        g[torch.as_tensor(order, device=g_rows.device)] = g_rows
         return g
+
+    @torch.no_grad()
+    def speaker_embed_files(self, paths, front, pool, trim_top_db: Optional[float] = 20.0) -> Tensor:
+        """``speaker_embed_waves([load_wav(p, sr) for p in paths], front, trim_top_db)`` bit for bit, without the host
+        decode: the recordings' headers and raw payloads are read on ``pool`` (a ``fileio.IoPool``) into one pinned byte
+        buffer, uploaded once and turned into the padded fp32 batch by one launch -> g (U, gin).  Files that need
+        resampling, f64 files, files of more than two channels and files the native header reader refuses are decoded by
+        ``load_wav`` as before and ride the same batch (``stage_target_files``).  ``front`` is a ``MelFrontend`` (its
+        sampling rate is the model's).  The "too short for one mel frame" errors are ``speaker_embed_waves``'s."""
+        return self.speaker_embed_staged(self.stage_target_files(paths, front.sr, pool), front, trim_top_db)
 
     @torch.no_grad()
     def infer_batch(self, unit: Tensor, g: Tensor, noise: Optional[Tensor] = None, seed: Optional[int] = None, keys=None,

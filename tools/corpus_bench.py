@@ -47,6 +47,8 @@ def main() -> None:
     ap.add_argument("--scratch", default=None, help="parent of the scratch directory (default: the system temp dir)")
     ap.add_argument("--fanout", type=int, default=1, metavar="K", help="every source is listed K times, with K different targets")
     ap.add_argument("--pipeline-fanout", default="auto", choices=["auto", "off"], help="the CLI's --fanout: off = every line encodes its source")
+    ap.add_argument("--target-io", default="auto", choices=["auto", "scipy"], help="the CLI's --target-io: scipy = every target decoded on the host")
+    ap.add_argument("--pcm16", default=False, action="store_true", help="the CLI's --pcm16: 16-bit output files")
     ap.add_argument("--repeat", type=int, default=2, help="end-to-end passes; the last one is reported (the first warms the page cache)")
     args = ap.parse_args()
 
@@ -96,12 +98,12 @@ def main() -> None:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             stats = cli.convert_items(net_g, d, items, outdir, 0, 1, args.batch, seed=7, io_threads=args.io_threads, timings=timings, lanes=args.lanes,
-                                      fanout=args.pipeline_fanout != "off")
+                                      fanout=args.pipeline_fanout != "off", target_io=args.target_io, pcm16=args.pcm16)
             torch.cuda.synchronize()
             wall = time.perf_counter() - t0
             e2e.append(dict(wall_s=wall, **timings, stages={k: round(v, 4) for k, v in stats.items() if k.endswith("_s")}))
         written = len(os.listdir(outdir))
-        sizes_ok = all(os.path.getsize(os.path.join(outdir, f"o{i:05d}.wav")) == 58 + int(lens[i]) * 320 * 4 for i in range(0, args.n, 97))
+        sizes_ok = all(os.path.getsize(os.path.join(outdir, f"o{i:05d}.wav")) == (44 + int(lens[i]) * 320 * 2 if args.pcm16 else 58 + int(lens[i]) * 320 * 4) for i in range(0, args.n, 97))
 
         # ---- host share of the target side: reading (and converting) the distinct target wavs, page cache warm
         from quickvc_official_amd.frontend import load_wav
@@ -152,7 +154,8 @@ def main() -> None:
             "kernel_only": {"wall_s": kernel_s, "samples_per_s": samples / kernel_s},
             "pipeline_vs_kernel_only": kernel_s / last["pipeline_s"], "end_to_end_vs_kernel_only": kernel_s / last["wall_s"],
             "lanes": args.lanes, "fanout": K, "pipeline_fanout": args.pipeline_fanout, "encodes_saved": int(stats.get("encodes_saved", 0)),
-            "io": {"input_MB": float(src_lens.sum()) * 1024 / 1e6, "output_MB": samples * 4 / 1e6, "io_threads": args.io_threads,
+            "target_io": args.target_io, "pcm16": bool(args.pcm16),
+            "io": {"input_MB": float(src_lens.sum()) * 1024 / 1e6, "output_MB": samples * (2 if args.pcm16 else 4) / 1e6, "io_threads": args.io_threads,
                    "scratch": os.path.dirname(td), "corpus_generation_s": gen_s},
         }
         print(json.dumps(res))
